@@ -5,7 +5,7 @@ RuntimeError is raised.  ``load()`` only dlopens; compute entry points need a GP
 """
 import ctypes
 import os
-from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_size_t, c_uint64,
+from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64,
                     c_void_p)
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -112,6 +112,8 @@ _SIGNATURES = {
     "cer_l2norm_rows_bwd": (c_int, [_P, _P, _P, c_int, c_int, _P]),
     "cer_maxpool2x2_nhwc": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "cer_sgd_nesterov_flat": (c_int, [_P, _P, _P, c_size_t, c_float, c_float, c_float, c_float, c_int, c_int, _P]),
+    "cer_adam_flat": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_double, c_double, c_double, c_double, c_double, c_int, c_int64,
+                              _P]),
     "cer_gather_rows": (c_int, [_P, _P, _P, c_int, c_int, c_uint64, _P]),
     "cer_frames_band_rows": (c_int, []),
     "cer_frames_transform": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int,

@@ -7,10 +7,18 @@
 // _single_tensor_sgd operation by operation (grad + wd*p; buf = mu*buf + (1-damp)*d, or d on the first step;
 // d + mu*buf; p - lr*d) so the result is bit-identical to it.
 //
+// adam_flat: the reference's other optimiser, torch.optim.Adam(betas, eps, weight_decay, amsgrad) with L2 weight decay
+// (instantiators.py:81-92), as ONE launch over the same flat buffers plus the moment buffers (20 B read + 12 B written
+// per parameter, 28 B + 8 B with AMSGrad) instead of torch's ~10 multi-tensor passes.  Per element it follows the
+// non-capturable branch of torch's _multi_tensor_adam operation by operation; the step-dependent terms
+// step_size = -lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) are computed on the host in double as torch does.
+//
 // gather_rows: out[i] = src[index[i]] (zeros for index < 0): token -> frame spreading of the BERT features
 // (abaw5_pre_processing/base/speech.py:690-738) and the edge-padded frame indexing of VGGish rows
 // (base/preprocessing.py:992-1018); the index plan is host logic (feature_extractor.py).
 #include <stdint.h>
+
+#include <cmath>
 
 #include "cer_internal.h"
 
@@ -36,6 +44,38 @@ __global__ void sgd_nesterov_flat_kernel(float4 *__restrict__ p, const float4 *_
     }
     p[i] = pv;
     if (mu != 0.f) buf[i] = bv;
+}
+
+// sqrtf and '/' are correctly rounded here (no fast-math; HIP's default -fhip-fp32-correctly-rounded-divide-sqrt); the
+// __f*_rn intrinsics spell out every other rounding so no contraction can change the result.
+__global__ void adam_flat_kernel(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m_,
+                                 float4 *__restrict__ v_, float4 *__restrict__ vmax_, size_t n4, float one_m_b1, float b2,
+                                 float one_m_b2, float eps, float wd, float step_size, float bc2_sqrt) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    float4 pv = p[i], mv = m_[i], vv = v_[i];
+    const float4 gv = g[i];
+    float4 xv = vmax_ ? vmax_[i] : make_float4(0, 0, 0, 0);
+    float *pp = reinterpret_cast<float *>(&pv), *mm = reinterpret_cast<float *>(&mv), *vs = reinterpret_cast<float *>(&vv),
+          *xx = reinterpret_cast<float *>(&xv);
+    const float *gg = reinterpret_cast<const float *>(&gv);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const float d = wd != 0.f ? __fmaf_rn(wd, pp[e], gg[e]) : gg[e];         // grads + wd * params
+        mm[e] = __fmaf_rn(one_m_b1, __fsub_rn(d, mm[e]), mm[e]);                 // exp_avg.lerp_(d, 1-b1) (small weight)
+        vs[e] = __fmaf_rn(one_m_b2, __fmul_rn(d, d), __fmul_rn(b2, vs[e]));      // exp_avg_sq.mul_(b2).addcmul_(d, d, 1-b2)
+        float s = vs[e];
+        if (vmax_) {
+            xx[e] = (s != s || s > xx[e]) ? s : xx[e];                            // torch.maximum (NaN propagates)
+            s = xx[e];
+        }
+        const float denom = __fadd_rn(sqrtf(s) / bc2_sqrt, eps);                 // sqrt(v) / bc2_sqrt + eps
+        pp[e] = __fmaf_rn(step_size, mm[e] / denom, pp[e]);                       // params.addcdiv_(exp_avg, denom, step_size)
+    }
+    p[i] = pv;
+    m_[i] = mv;
+    v_[i] = vv;
+    if (vmax_) vmax_[i] = xv;
 }
 
 __global__ void gather_rows_kernel(const float4 *__restrict__ src, const int64_t *__restrict__ index, float4 *__restrict__ out,
@@ -110,6 +150,29 @@ extern "C" int cer_sgd_nesterov_flat(float *param, const float *grad, float *mom
         return cer_set_error(CER_ERR_INVALID_ARG, "sgd_nesterov_flat: Nesterov momentum requires a momentum and zero dampening");
     CER_LAUNCH(sgd_nesterov_flat_kernel, dim3(cer_blocks(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, (float4 *)param,
                (const float4 *)grad, (float4 *)momentum_buf, n / 4, lr, momentum, dampening, weight_decay, nesterov, first_step);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_adam_flat(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *max_exp_avg_sq,
+                             size_t n, double lr, double beta1, double beta2, double eps, double weight_decay, int amsgrad,
+                             int64_t step, void *stream) {
+    if (!param || !grad || !exp_avg || !exp_avg_sq || n == 0 || (n & 3) || (amsgrad && !max_exp_avg_sq))
+        return cer_set_error(CER_ERR_INVALID_ARG,
+                             "adam_flat: needs param, grad, exp_avg, exp_avg_sq, (max_exp_avg_sq), n a positive multiple of 4");
+    if (((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq |
+         (uintptr_t)(amsgrad ? max_exp_avg_sq : nullptr)) & 15)
+        return cer_set_error(CER_ERR_INVALID_ARG, "adam_flat: buffers must be 16-byte aligned");
+    if (step < 1 || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return cer_set_error(CER_ERR_INVALID_ARG, "adam_flat: needs step >= 1 and betas in [0, 1)");
+    // torch computes these in Python floats (double: `lr / bc * -1`, `bc ** 0.5`) and hands them to the foreach kernels as
+    // float scalars
+    const double step_size = lr / (1.0 - std::pow(beta1, (double)step)) * -1.0;
+    const double bc2_sqrt = std::pow(1.0 - std::pow(beta2, (double)step), 0.5);
+    CER_LAUNCH(adam_flat_kernel, dim3(cer_blocks(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, (float4 *)param,
+               (const float4 *)grad, (float4 *)exp_avg, (float4 *)exp_avg_sq, amsgrad ? (float4 *)max_exp_avg_sq : nullptr, n / 4,
+               (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)step_size,
+               (float)bc2_sqrt);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }

@@ -240,21 +240,47 @@ class ClipDataParallel:
         return global_batch_indices[rank::self.world]
 
 
-class FlatNesterovSGD:
+class _FlatOptimizer(torch.optim.Optimizer):
+    """A ``torch.optim.Optimizer`` over ``ddp.params`` whose update is one HIP launch over the flat parameter / gradient
+    buffers of a ``ClipDataParallel``.  Being an ``Optimizer`` is what lets torch's schedulers (and the reference's
+    ``MyStepLR`` / ``MyCosineLR``, base/scheduler.py:167-256) drive it: they type-check for it and read / write
+    ``param_groups[*]['lr']`` and ``initial_lr``.  The state lives in flat buffers, not in ``self.state``, so ``state_dict``
+    / ``load_state_dict`` are the subclasses' own."""
+
+    def __init__(self, ddp, defaults):
+        super().__init__(ddp.params, defaults)
+        self.ddp = ddp
+        self.flat_param = ddp.flatten_parameters()
+
+    def zero_grad(self, set_to_none=False):
+        self.ddp.zero_grad()
+
+    def _bump_versions(self):
+        # the kernel wrote through raw pointers: move the version counters like an in-place torch op would, so caches keyed
+        # on (data_ptr, _version) see the update.  Semantics note: every trainable parameter always has a (dense) gradient
+        # view in the bucket, so weight decay and momentum apply to all of them every step -- torch's optimisers skip a
+        # parameter whose grad is None after zero_grad(set_to_none=True); the two only differ for a parameter that
+        # receives no gradient at all in a step, which the models here do not have.
+        torch.autograd.graph.increment_version(self.ddp.params)
+
+    def _groups_state(self):
+        return [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
+
+    def _load_groups(self, sd):
+        for g, h in zip(self.param_groups, sd["param_groups"]):
+            g.update(h)
+
+
+class FlatNesterovSGD(_FlatOptimizer):
     """torch.optim.SGD(momentum, nesterov, weight_decay) of the reference (instantiators.py:74-92) as ONE HIP launch over
     the flat parameter / gradient / momentum buffers of a ``ClipDataParallel`` (bit-identical arithmetic, tested against
     torch.optim.SGD).  ``param_groups[0]['lr']`` is what the reference's scheduler mutates (base/scheduler.py:167-197)."""
 
     def __init__(self, ddp, lr=1e-3, momentum=0.9, dampening=0.0, weight_decay=1e-4, nesterov=True):
-        self.ddp = ddp
-        self.param_groups = [{"params": ddp.params, "lr": lr, "momentum": momentum, "dampening": dampening,
-                              "weight_decay": weight_decay, "nesterov": nesterov}]
-        self.flat_param = ddp.flatten_parameters()
+        super().__init__(ddp, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                   nesterov=nesterov))
         self.buf = torch.zeros_like(self.flat_param)
         self.steps = 0
-
-    def zero_grad(self, set_to_none=False):
-        self.ddp.zero_grad()
 
     def step(self):
         from . import ops
@@ -263,19 +289,52 @@ class FlatNesterovSGD:
         ops.sgd_nesterov_flat(self.flat_param, self.ddp.flat, self.buf, g["lr"], g["momentum"], g["dampening"],
                               g["weight_decay"], g["nesterov"], first_step=self.steps == 0)
         self.steps += 1
-        # the kernel wrote through raw pointers: move the version counters like an in-place torch op would, so caches keyed
-        # on (data_ptr, _version) see the update.  Semantics note: every trainable parameter always has a (dense) gradient
-        # view in the bucket, so weight decay and momentum apply to all of them every step -- torch.optim.SGD skips a
-        # parameter whose grad is None after zero_grad(set_to_none=True); the two only differ for a parameter that
-        # receives no gradient at all in a step, which the models here do not have.
-        torch.autograd.graph.increment_version(self.ddp.params)
+        self._bump_versions()
 
     def state_dict(self):
-        return {"momentum_buffer": self.buf, "steps": self.steps, "param_groups": [{k: v for k, v in g.items() if k != "params"}
-                                                                                   for g in self.param_groups]}
+        return {"momentum_buffer": self.buf, "steps": self.steps, "param_groups": self._groups_state()}
 
     def load_state_dict(self, sd):
         self.buf.copy_(sd["momentum_buffer"])
         self.steps = int(sd["steps"])
-        for g, h in zip(self.param_groups, sd["param_groups"]):
-            g.update(h)
+        self._load_groups(sd)
+
+
+class FlatAdam(_FlatOptimizer):
+    """torch.optim.Adam(betas, eps, weight_decay, amsgrad) of the reference (instantiators.py:81-92; L2 weight decay, not
+    AdamW) as ONE HIP launch over the flat buffers of a ``ClipDataParallel`` plus flat moment buffers beside them.  Per
+    element the arithmetic is the non-capturable branch of torch's ``_multi_tensor_adam``; ``steps`` is the one step count
+    of all parameters (torch keeps one per parameter, all equal here)."""
+
+    def __init__(self, ddp, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False):
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid betas: {betas}")
+        super().__init__(ddp, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=amsgrad))
+        self.exp_avg = torch.zeros_like(self.flat_param)
+        self.exp_avg_sq = torch.zeros_like(self.flat_param)
+        self.max_exp_avg_sq = torch.zeros_like(self.flat_param) if amsgrad else None
+        self.steps = 0
+
+    def step(self):
+        from . import ops
+        self.ddp.gather_gradients()
+        g = self.param_groups[0]
+        ops.adam_flat(self.flat_param, self.ddp.flat, self.exp_avg, self.exp_avg_sq, self.max_exp_avg_sq, g["lr"],
+                      self.steps + 1, betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], amsgrad=g["amsgrad"])
+        self.steps += 1
+        self._bump_versions()
+
+    def state_dict(self):
+        sd = {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "steps": self.steps,
+              "param_groups": self._groups_state()}
+        if self.max_exp_avg_sq is not None:
+            sd["max_exp_avg_sq"] = self.max_exp_avg_sq
+        return sd
+
+    def load_state_dict(self, sd):
+        self.exp_avg.copy_(sd["exp_avg"])
+        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        if self.max_exp_avg_sq is not None:
+            self.max_exp_avg_sq.copy_(sd["max_exp_avg_sq"])
+        self.steps = int(sd["steps"])
+        self._load_groups(sd)

@@ -793,6 +793,24 @@ def sgd_nesterov_flat(param, grad, buf, lr, momentum=0.9, dampening=0.0, weight_
           "cer_sgd_nesterov_flat")
 
 
+def adam_flat(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+              amsgrad=False):
+    """torch.optim.Adam's update over flat fp32 buffers in one launch; ``step`` is the count after this update (>= 1)."""
+    bufs = [(param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")]
+    if amsgrad:
+        if max_exp_avg_sq is None:
+            raise ValueError("max_exp_avg_sq: required with amsgrad")
+        bufs.append((max_exp_avg_sq, "max_exp_avg_sq"))
+    for t, nme in bufs:
+        _dev_f32(t, nme)
+        if t.numel() != param.numel():
+            raise ValueError(f"{nme}: expected {param.numel()} elements, got {t.numel()}")
+    check(_lib.load().cer_adam_flat(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq),
+                                    ptr(max_exp_avg_sq) if amsgrad else None, param.numel(), float(lr), float(betas[0]),
+                                    float(betas[1]), float(eps), float(weight_decay), int(amsgrad), int(step),
+                                    current_stream()), "cer_adam_flat")
+
+
 # ------------------------------------------------------------------ trainable tail
 def weight_norm_fwd(v, g):
     """v [Cout,Cin,k], g [Cout,1,1] -> (w [Cout,Cin,k], norm [Cout])."""

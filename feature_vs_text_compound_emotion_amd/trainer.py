@@ -19,6 +19,7 @@ Two ways in:
 Logging (dllogger), pickled outputs, PerfTracker reports and best-model files stay with the reference's trainer: they are
 its control plane, not this path.
 """
+import math
 from collections import Counter
 from types import SimpleNamespace
 
@@ -198,6 +199,72 @@ class DeviceEvalMixin:
         return metrics.compute_perf(per_video, self.ignore_classes), per_video
 
 
+_SCHEDULER_DEFAULTS = {"gamma": 0.1, "step_size": 40, "last_epoch": -1, "min_lr": 1e-7, "t_max": 100}   # default_config.py
+
+
+class FlooredStepLR(torch.optim.lr_scheduler.LRScheduler):
+    """base/scheduler.py:167-197 ``MyStepLR``: ``max(base_lr * gamma ** (last_epoch // step_size), min_lr)``."""
+
+    def __init__(self, optimizer, step_size, gamma=0.1, last_epoch=-1, min_lr=1e-6):
+        self.step_size, self.gamma, self.min_lr = step_size, gamma, min_lr
+        super().__init__(optimizer, last_epoch)
+
+    def get_lr(self):
+        return [max(base * self.gamma ** (self.last_epoch // self.step_size), self.min_lr) for base in self.base_lrs]
+
+
+class CosineFromEpochOneLR(torch.optim.lr_scheduler.LRScheduler):
+    """base/scheduler.py:200-243 ``MyCosineLR``: ``max(base_lr * coef * (1 + cos((last_epoch - 1) * pi / max_epochs)),
+    min_lr)``."""
+
+    def __init__(self, optimizer, coef, max_epochs, min_lr=1e-9, last_epoch=-1):
+        if not isinstance(coef, float) or coef <= 0.0:
+            raise ValueError(f"MYCOSINE: `coef` must be a float > 0, got {coef!r}")
+        if not max_epochs > 0:
+            raise ValueError(f"MYCOSINE: `max_epochs` must be > 0, got {max_epochs!r}")
+        self.coef, self.max_epochs, self.min_lr = coef, float(max_epochs), min_lr
+        super().__init__(optimizer, last_epoch)
+
+    def get_lr(self):
+        return [max(base * self.coef * (1.0 + math.cos((self.last_epoch - 1) * math.pi / self.max_epochs)), self.min_lr)
+                for base in self.base_lrs]
+
+
+def make_lr_scheduler(optimizer, hp):
+    """instantiators.py:140-185 on the ``opt__`` hyper-parameters ``hp`` (prefix stripped).  Keys ``default_config.py``
+    defines fall back to its values; ``coef``, ``max_epochs`` and ``milestones`` (read by MYCOSINE / MULTISTEP, defined
+    nowhere in the reference's defaults) must be given."""
+    name = str(hp.get("name_lr_scheduler")).upper()
+
+    def get(key):
+        if key in hp:
+            return hp[key]
+        if key in _SCHEDULER_DEFAULTS:
+            return _SCHEDULER_DEFAULTS[key]
+        raise ValueError(f"lr scheduler {name}: missing hyper-parameter `opt__{key}`")
+
+    if name == "MYWARMUP":
+        raise NotImplementedError("lr scheduler MYWARMUP: MyWarmupScheduler.step(epoch, metrics) needs the validation metric, "
+                                  "but the reference's training loop calls scheduler.step() without arguments "
+                                  "(trainer.py:694)")
+    if not isinstance(optimizer, torch.optim.Optimizer):
+        raise TypeError(f"lr scheduler {name} cannot drive {type(optimizer).__name__}: not a torch.optim.Optimizer")
+    sch = torch.optim.lr_scheduler
+    if name == "STEP":
+        return sch.StepLR(optimizer, step_size=get("step_size"), gamma=get("gamma"), last_epoch=get("last_epoch"))
+    if name == "MYSTEP":
+        return FlooredStepLR(optimizer, step_size=get("step_size"), gamma=get("gamma"), last_epoch=get("last_epoch"),
+                             min_lr=get("min_lr"))
+    if name == "COSINE":
+        return sch.CosineAnnealingLR(optimizer, T_max=get("t_max"), eta_min=get("min_lr"), last_epoch=get("last_epoch"))
+    if name == "MYCOSINE":
+        return CosineFromEpochOneLR(optimizer, coef=get("coef"), max_epochs=get("max_epochs"), min_lr=get("min_lr"),
+                                    last_epoch=get("last_epoch"))
+    if name == "MULTISTEP":
+        return sch.MultiStepLR(optimizer, milestones=get("milestones"), gamma=get("gamma"), last_epoch=get("last_epoch"))
+    raise ValueError(f"Unsupported learning rate scheduler `{hp.get('name_lr_scheduler')}`")
+
+
 _REFERENCE_KWARGS = ("device", "emotion", "model_name", "models", "save_path", "fold", "min_epoch", "max_epoch",
                      "early_stopping", "learning_rate", "min_learning_rate", "patience", "train_batch_size",
                      "eval_batch_size", "criterion", "factor", "verbose", "milestone", "metrics",
@@ -270,13 +337,15 @@ class Trainer(DeviceEvalMixin):
         return [p for _, p in self.model.named_parameters() if p.requires_grad]
 
     def init_optimizer_and_scheduler(self, epoch=0):
-        """trainer.py:127-134 -> instantiators.py:62-140: ``opt__``-prefixed hyper-parameters; SGD is built WITHOUT ``lr``
-        (instantiators.py:74-79: torch's default 1e-3 applies until a scheduler changes it).  With ``data_parallel`` the
-        same update runs as ONE fused launch over the flat bucket (``FlatNesterovSGD``, bit-identical to torch.optim.SGD)."""
+        """trainer.py:127-134 -> instantiators.py:62-185: ``opt__``-prefixed hyper-parameters, names compared
+        case-insensitively (the reference's constants are ``'SGD'`` / ``'MYSTEP'`` ...).  SGD and Adam are built WITHOUT
+        ``lr`` (instantiators.py:74-92: torch's default 1e-3 applies until a scheduler changes it).  With ``data_parallel``
+        the same update runs as ONE fused launch over the flat bucket (``FlatNesterovSGD`` / ``FlatAdam``), and the
+        scheduler drives that optimiser like any other."""
         a = {k.split("__", 1)[1] if k.startswith("opt") and "__" in k else k: v for k, v in vars(self.args).items()}
-        name = a.get("name_optimizer", "sgd")
+        name = str(a.get("name_optimizer", "sgd")).upper()
         params = self.get_parameters()
-        if name == "sgd":
+        if name == "SGD":
             hp = dict(momentum=a.get("momentum", 0.9), dampening=a.get("dampening", 0.0),
                       weight_decay=a.get("weight_decay", 1e-4), nesterov=a.get("nesterov", True))
             if self.ddp is not None and hp["nesterov"] and hp["dampening"] == 0.0:
@@ -284,23 +353,17 @@ class Trainer(DeviceEvalMixin):
                 self.optimizer = FlatNesterovSGD(self.ddp, lr=1e-3, momentum=hp["momentum"], weight_decay=hp["weight_decay"])
             else:
                 self.optimizer = torch.optim.SGD(params=params, **hp)
-        elif name == "adam":
-            self.optimizer = torch.optim.Adam(params=params, betas=(a.get("beta1", 0.9), a.get("beta2", 0.999)),
-                                              eps=a.get("eps_adam", 1e-8), weight_decay=a.get("weight_decay", 0.0),
-                                              amsgrad=a.get("amsgrad", False))
-        else:
-            raise ValueError(f"Unsupported optimizer `{name}`")
-        self.scheduler = None
-        if a.get("lr_scheduler") and isinstance(self.optimizer, torch.optim.Optimizer):
-            sched = a.get("name_lr_scheduler")
-            if sched in ("step", "mystep"):
-                self.scheduler = torch.optim.lr_scheduler.StepLR(self.optimizer, step_size=a.get("step_size", 1),
-                                                                 gamma=a.get("gamma", 0.1))
-            elif sched == "cosine":
-                self.scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(self.optimizer, T_max=a.get("t_max", 1),
-                                                                            eta_min=a.get("min_lr", 0.0))
+        elif name == "ADAM":
+            hp = dict(betas=(a.get("beta1", 0.9), a.get("beta2", 0.999)), eps=a.get("eps_adam", 1e-8),
+                      weight_decay=a.get("weight_decay", 0.0), amsgrad=a.get("amsgrad", False))
+            if self.ddp is not None:
+                from .data_parallel import FlatAdam
+                self.optimizer = FlatAdam(self.ddp, lr=1e-3, **hp)
             else:
-                raise NotImplementedError(f"lr scheduler {sched!r} (base/scheduler.py) stays with the reference's trainer")
+                self.optimizer = torch.optim.Adam(params=params, **hp)
+        else:
+            raise ValueError(f"Unsupported optimizer `{a.get('name_optimizer')}`")
+        self.scheduler = make_lr_scheduler(self.optimizer, a) if a.get("lr_scheduler") else None
 
     # ------------------------------------------------------------------ training
     def _split(self, X):

@@ -396,6 +396,16 @@ int cer_fold_bn_3x3(const float *w_packed, const float *scale, const float *shif
 int cer_sgd_nesterov_flat(float *param, const float *grad, float *momentum_buf, size_t n, float lr, float momentum,
                           float dampening, float weight_decay, int nesterov, int first_step, void *stream);
 
+/* torch.optim.Adam(betas, eps, weight_decay, amsgrad) over flat buffers (reference instantiators.py:81-92; L2 weight decay,
+ * not AdamW), step `step` >= 1 (the count AFTER this update, as torch's state['step']): d = grad + wd*p; m = lerp(m, d, 1-b1);
+ * v = b2*v + (1-b2)*d*d; amsgrad: vmax = max(vmax, v); p += step_size * m / (sqrt(v or vmax) / bc2_sqrt + eps) with
+ * step_size = -lr / (1 - b1^step), bc2_sqrt = sqrt(1 - b2^step) computed here in double -- the non-capturable branch of
+ * torch's _multi_tensor_adam element by element, one launch.  max_exp_avg_sq may be NULL unless amsgrad; n % 4 == 0,
+ * 16-byte aligned buffers. */
+int cer_adam_flat(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float *max_exp_avg_sq, size_t n,
+                  double lr, double beta1, double beta2, double eps, double weight_decay, int amsgrad, int64_t step,
+                  void *stream);
+
 /* out[i][:] = src[index[i]][:], zeros where index[i] < 0 or >= n_src: the token -> frame spreading of the BERT rows
  * (abaw5_pre_processing/base/speech.py:690-738) and the edge-padded frame indexing of VGGish rows
  * (base/preprocessing.py:992-1018); the index plan is host logic.  cols % 4 == 0. */
