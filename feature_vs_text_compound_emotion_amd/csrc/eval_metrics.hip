@@ -32,6 +32,35 @@ __global__ void window_stitch_kernel(const float *__restrict__ win, const int *_
     out[i] = cnt > 0 ? s / (float)cnt : 0.f;
 }
 
+// The windows of V videos in one launch: rows [frame_offsets[v], frame_offsets[v+1]) of `out` are video v, whose windows
+// are [win_offsets[v], win_offsets[v+1]) of `win` (starts relative to the video).  One thread per (row, class); the row's
+// video comes from a binary search over frame_offsets.  The per-frame sum walks the video's windows in ascending order and
+// divides by (float)cnt exactly like window_stitch_kernel, so each element is bit-identical to a one-video launch.
+__global__ void window_stitch_multi_kernel(const float *__restrict__ win, const int *__restrict__ starts,
+                                           const int *__restrict__ win_off, const int *__restrict__ frame_off, int V, int nw,
+                                           int Lw, int C, int R, float *__restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)R * C) return;
+    const int row = (int)(i / C), c = (int)(i - (size_t)row * C);
+    int lo = 0, hi = V - 1;                       // last v with frame_off[v] <= row
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (frame_off[mid] <= row) lo = mid; else hi = mid - 1;
+    }
+    const int f = row - frame_off[lo];
+    const int w0 = max(win_off[lo], 0), w1 = min(win_off[lo + 1], nw);
+    float s = 0.f;
+    int cnt = 0;
+    for (int w = w0; w < w1; ++w) {
+        const int r = f - starts[w];
+        if (r >= 0 && r < Lw) {
+            s += win[((size_t)w * Lw + r) * C + c];
+            ++cnt;
+        }
+    }
+    out[i] = cnt > 0 ? s / (float)cnt : 0.f;
+}
+
 __device__ __forceinline__ int argmax_first(const float *z, int n) {
     int b = 0;
     float m = z[0];
@@ -136,6 +165,17 @@ extern "C" int cer_window_stitch(const float *win_out, const int *starts, int nw
         return cer_set_error(CER_ERR_INVALID_ARG, "window_stitch: bad argument");
     const size_t n = (size_t)total * C;
     CER_LAUNCH(window_stitch_kernel, dim3(cer_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, win_out, starts, nw, Lw, C, total, out);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_window_stitch_multi(const float *win_out, const int *win_start, const int *win_offsets,
+                                       const int *frame_offsets, int V, int nw, int Lw, int C, int R, float *out, void *stream) {
+    if (!win_out || !win_start || !win_offsets || !frame_offsets || !out || V <= 0 || nw < V || Lw <= 0 || C <= 0 || R < V)
+        return cer_set_error(CER_ERR_INVALID_ARG, "window_stitch_multi: bad argument");
+    const size_t n = (size_t)R * C;
+    CER_LAUNCH(window_stitch_multi_kernel, dim3(cer_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, win_out, win_start,
+               win_offsets, frame_offsets, V, nw, Lw, C, R, out);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }

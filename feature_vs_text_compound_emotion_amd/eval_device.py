@@ -31,6 +31,48 @@ def stitch_windows(win_out, starts, total):
     return out
 
 
+def _offsets(name, offsets, end):
+    offsets = [int(o) for o in offsets]
+    if len(offsets) < 2 or offsets[0] != 0 or any(b <= a for a, b in zip(offsets, offsets[1:])) or \
+            (end is not None and offsets[-1] != end):
+        raise ValueError(f"stitch_windows_multi: {name} must rise strictly from 0"
+                         + ("" if end is None else f" to {end}") + f", got {offsets}")
+    return offsets
+
+
+def stitch_windows_multi(win_out, starts, win_offsets, frame_offsets):
+    """``stitch_windows`` for V videos in ONE launch.  win_out [nw, Lw, C] (GPU) holds the videos' windows, video after video;
+    video v owns windows ``win_offsets[v]:win_offsets[v+1]``, whose start frames ``starts`` are relative to the video, and rows
+    ``frame_offsets[v]:frame_offsets[v+1]`` of the result [R = frame_offsets[-1], C] -- the concatenation
+    ``DeviceEvalAccumulator.add(..., video_offsets=frame_offsets)`` takes.  Every row is bit-identical to ``stitch_windows`` on
+    its video alone.  All arguments are checked here, before the launch."""
+    if not (isinstance(win_out, torch.Tensor) and win_out.is_cuda and win_out.dtype == torch.float32 and win_out.dim() == 3):
+        raise ValueError("stitch_windows_multi: expected a [n_windows, window_length, n_classes] float32 GPU tensor")
+    nw, lw, c = win_out.shape
+    starts = [int(s) for s in starts]
+    if len(starts) != nw:
+        raise ValueError(f"stitch_windows_multi: {nw} windows but {len(starts)} start frames")
+    woff = _offsets("win_offsets", win_offsets, nw)
+    foff = _offsets("frame_offsets", frame_offsets, None)
+    if len(woff) != len(foff):
+        raise ValueError(f"stitch_windows_multi: {len(woff) - 1} videos in win_offsets, {len(foff) - 1} in frame_offsets")
+    for v in range(len(woff) - 1):
+        total = foff[v + 1] - foff[v]
+        for w in range(woff[v], woff[v + 1]):
+            if starts[w] < 0 or starts[w] + lw > total:
+                raise ValueError(f"stitch_windows_multi: window {w} ({lw} frames from {starts[w]}) leaves video {v} "
+                                 f"({total} frames)")
+    dev = win_out.device
+    st = torch.tensor(starts, dtype=torch.int32, device=dev)
+    wo = torch.tensor(woff, dtype=torch.int32, device=dev)
+    fo = torch.tensor(foff, dtype=torch.int32, device=dev)
+    r = foff[-1]
+    out = torch.empty((r, c), device=dev, dtype=torch.float32)
+    check(_lib.load().cer_window_stitch_multi(ptr(win_out.contiguous()), ptr(st), ptr(wo), ptr(fo), len(woff) - 1, nw, lw, c,
+                                              r, ptr(out), current_stream()), "cer_window_stitch_multi")
+    return out
+
+
 def scores_from_confusion(cm):
     """Counts [C, C] (rows = targets, columns = predictions) -> the four entries the reference derives with sklearn."""
     cm = np.asarray(cm, dtype=np.float64)
@@ -78,6 +120,19 @@ class DeviceEvalAccumulator:
                                           ptr(cm[0]), ptr(cm[1:]), ptr(vp), ptr(self.bad), current_stream()), "cer_eval_accumulate")
             if self.keep:
                 self.video_predictions.append((ic, vp))
+
+    def all_reduce(self, group=None):
+        """Sum the counts of every rank (sharded evaluation): every ignore-class's [4, C, C] counts and the ``bad`` counter go
+        in ONE int64 buffer through ONE ``all_reduce(SUM)``.  Afterwards every rank holds the global counts, so ``compute``
+        gives the same scores everywhere -- and raises on every rank if any rank saw a bad label."""
+        import torch.distributed as dist
+        cms = list(self.cm.values())
+        flat = torch.cat([cm.reshape(-1) for cm in cms] + [self.bad.to(torch.int64)])
+        dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+        n = 4 * self.c * self.c
+        for i, cm in enumerate(cms):
+            cm.copy_(flat[i * n:(i + 1) * n].view_as(cm))
+        self.bad.copy_(flat[-1:])
 
     def compute(self):
         """One device -> host copy per ignore-class setting; the reference's nested score dictionary."""

@@ -83,10 +83,18 @@ class DeviceEvalMixin:
     kernel and folds every video into device-side confusion counts; "host" is the reference's own sequence (one forward
     per window, indexed adds, numpy scores) and the checker of the device path.  ``self.eval_frame_budget`` bounds the frames
     one forward may carry when windows are batched (default: ``train_batch_size x window_length``, the training
-    footprint), so a long video never needs more activation memory than a training step."""
+    footprint), so a long video never needs more activation memory than a training step.
+
+    ``self.eval_video_batch`` > 1 (device aggregation, LFAN, videos of at least one window): the windows of several videos
+    share forwards -- groups of at most ``eval_frame_budget`` frames that may span videos -- and every ``eval_video_batch``
+    videos are stitched with one launch and folded into the counts with one call.  ``self.eval_shard`` under an initialised
+    ``torch.distributed`` with world > 1: rank r evaluates the videos at loader positions p % world == r, the device counts
+    are summed with one all-reduce and the per-video logits are gathered back into loader order."""
 
     eval_aggregate = None          # None -> "device" on a GPU, "host" otherwise
     eval_frame_budget = None
+    eval_video_batch = 1           # 1: one forward (group) per video, as the reference
+    eval_shard = False             # True: split the videos over the torch.distributed ranks
     eval_keep_logits = True        # the reference always returns (and pickles) the per-video logits (trainer.py:500-523)
     ignore_classes = (None,)
 
@@ -155,22 +163,58 @@ class DeviceEvalMixin:
         final[:, where, ...] = final[:, where, ...] / freqs
         return final
 
+    def _eval_shard_rank_world(self):
+        """(rank, world) of sharded evaluation, read from torch.distributed (the mixin also serves trainers without
+        ``self.ddp``); (0, 1) when ``eval_shard`` is off or no process group is initialised."""
+        if not self.eval_shard:
+            return 0, 1
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return 0, 1
+        return dist.get_rank(), dist.get_world_size()
+
     @torch.no_grad()
     def inference(self, dataloader, keep_logits=None, aggregate=None):
         """Trainer.inference (trainer.py:436-523): returns ``(current_perf, per_video_frame_logits)``.  Device path: each
         video is folded into device-side confusion counts (``DeviceEvalAccumulator``) and the scores come from one small
         copy at the end; the per-video ``{labels, logits}`` dictionary the reference returns is filled when
-        ``keep_logits`` (default ``self.eval_keep_logits`` = True, as the reference; False skips the per-video copies)."""
+        ``keep_logits`` (default ``self.eval_keep_logits`` = True, as the reference; False skips the per-video copies).
+        ``eval_video_batch`` / ``eval_shard``: see the class docstring; the returned dictionary has the same keys in the
+        same (loader) order either way."""
         aggregate = self._aggregate(aggregate)
         keep_logits = self.eval_keep_logits if keep_logits is None else keep_logits
+        video_batch = int(self.eval_video_batch or 1)
+        if video_batch < 1:
+            raise ValueError(f"eval_video_batch must be >= 1, got {self.eval_video_batch!r}")
         self.model.eval()
-        per_video = {}
+        rank, world = self._eval_shard_rank_world()
+        entries = []                                      # (loader position, trial, {labels, logits})
         acc = None
         if aggregate == "device":
             from .eval_device import DeviceEvalAccumulator
             acc = DeviceEvalAccumulator(self.number_classes, self.ignore_classes, device=self.device)
         amp = bool(self._arg("amp", False)) and _is_gpu(self.device)
-        for X, trials, lengths, indices in dataloader:
+        wlen = int(self._arg("window_length"))
+
+        def forward(batch):
+            with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
+                return self.model(batch)
+
+        batched = None
+        if acc is not None and video_batch > 1 and self._arg("model_name") == "LFAN":
+            budget = self.eval_frame_budget or max(1, int(self._arg("train_batch_size", 1))) * wlen
+            batched = _VideoWindowBatch(forward, max(1, budget // wlen))
+
+        def fold(logits, labels, offsets, keys):
+            acc.add(logits, labels, video_offsets=offsets)
+            if keep_logits:
+                lg, lb = logits.cpu().numpy(), labels.long().cpu().numpy()
+                for (pos, trial), a, b in zip(keys, offsets, offsets[1:]):
+                    entries.append((pos, trial, {"labels": lb[a:b], "logits": lg[a:b]}))
+
+        for pos, (X, trials, lengths, indices) in enumerate(dataloader):
+            if pos % world != rank:
+                continue
             inputs = {k: v.to(self.device) for k, v in X.items()}
             labels = inputs.pop("continuous_label", None)
             if labels is None:
@@ -181,8 +225,14 @@ class DeviceEvalMixin:
                 nframes = _num_frames(m, t)
             if labels.numel() == self.train_batch_size:     # the reference's "todo : fix this." label hack (:468-472)
                 labels = torch.zeros((self.train_batch_size, len(indices[0]), 1), dtype=torch.float32, device=self.device)
+            if batched is not None and nframes >= wlen:
+                assert tuple(labels.shape) == (1, nframes, 1), tuple(labels.shape)
+                batched.add((pos, trials[0]), self.window_input(inputs), labels)
+                if len(batched) >= video_batch:
+                    fold(*batched.flush())
+                continue
             with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
-                if nframes > self._arg("window_length") and self._arg("model_name") == "LFAN":
+                if nframes > wlen and self._arg("model_name") == "LFAN":
                     outputs = self.inference_forward_windows(inputs, aggregate)
                 else:
                     outputs = self.model(inputs)
@@ -192,11 +242,71 @@ class DeviceEvalMixin:
             if acc is not None:
                 acc.add(outputs.contiguous().view(bsz * nfms, -1), labels.contiguous().view(bsz * nfms))
             if keep_logits or acc is None:
-                per_video[trials[0]] = {"labels": labels.contiguous().view(bsz * nfms).long().cpu().numpy().flatten(),
-                                        "logits": outputs.contiguous().view(bsz * nfms, -1).cpu().numpy()}
+                entries.append((pos, trials[0], {"labels": labels.contiguous().view(bsz * nfms).long().cpu().numpy().flatten(),
+                                                 "logits": outputs.contiguous().view(bsz * nfms, -1).cpu().numpy()}))
+        if batched is not None and len(batched):
+            fold(*batched.flush())
+        if world > 1:                                   # every rank takes part, with or without videos of its own
+            import torch.distributed as dist
+            if acc is not None:
+                acc.all_reduce()
+            if keep_logits or acc is None:
+                parts = [None] * world
+                dist.all_gather_object(parts, entries)
+                entries = [e for part in parts for e in part]
+        per_video = {}
+        for _, trial, entry in sorted(entries, key=lambda e: e[0]):   # loader order; a repeated trial id: the last one wins
+            per_video[trial] = entry
         if acc is not None:
             return acc.compute(), per_video
         return metrics.compute_perf(per_video, self.ignore_classes), per_video
+
+
+class _VideoWindowBatch:
+    """The videos of one ``eval_video_batch`` on the batched LFAN path.  Their windows go through ``forward`` in groups of
+    ``group`` windows as soon as a group is full (a group may span videos; at most one group of inputs is held beyond the
+    current video's windows), only the window outputs are kept, and ``flush`` stitches every video with ONE launch."""
+
+    def __init__(self, forward, group):
+        self.forward, self.group = forward, group
+        self._reset()
+
+    def _reset(self):
+        self.pending, self.outs = [], []             # window inputs not forwarded yet; [g, Lw, C] float32 outputs
+        self.starts, self.win_off, self.frame_off = [], [0], [0]
+        self.labels, self.keys = [], []
+
+    def __len__(self):
+        return len(self.keys)
+
+    def add(self, key, windows, labels):
+        """``windows``: ``window_input``'s [(inputs, frame indices)] of one video; ``labels`` [1, n, 1] on the device."""
+        for chunk, wd in windows:
+            self.pending.append(chunk)
+            self.starts.append(int(wd[0]))
+            if len(self.pending) == self.group:
+                self._run()
+        self.win_off.append(len(self.starts))
+        self.frame_off.append(self.frame_off[-1] + labels.numel())
+        self.labels.append(labels.reshape(-1))
+        self.keys.append(key)
+
+    def _run(self):
+        part, self.pending = self.pending, []
+        out = self.forward({m: torch.cat([c[m] for c in part], dim=0).contiguous() for m in part[0]})
+        assert out.ndim == 3 and out.shape[0] == len(part), tuple(out.shape)
+        self.outs.append(out.detach().float())
+
+    def flush(self):
+        """-> (stitched logits [R, C], labels [R], frame offsets [V+1], keys [V]); the batch is empty afterwards."""
+        from .eval_device import stitch_windows_multi
+        if self.pending:
+            self._run()
+        out = self.outs[0] if len(self.outs) == 1 else torch.cat(self.outs, dim=0)
+        logits = stitch_windows_multi(out, self.starts, self.win_off, self.frame_off)
+        res = (logits, torch.cat(self.labels), list(self.frame_off), list(self.keys))
+        self._reset()
+        return res
 
 
 _SCHEDULER_DEFAULTS = {"gamma": 0.1, "step_size": 40, "last_epoch": -1, "min_lr": 1e-7, "t_max": 100}   # default_config.py
@@ -417,7 +527,12 @@ class Trainer(DeviceEvalMixin):
 
         def master(perf):
             return perf[self.ignore_classes[0]][metrics.W_F1][metrics.FRAME_LEVEL]["master"]
-        perf, _ = self.inference(dataloader_dict[VALIDSET], keep_logits=False)
+
+        def evaluate(loader, **kwargs):
+            if self.eval_shard and self.ddp is not None:   # one set of BatchNorm statistics: every shard scores the same model
+                self.ddp.sync_buffers()
+            return self.inference(loader, **kwargs)
+        perf, _ = evaluate(dataloader_dict[VALIDSET], keep_logits=False)
         history["valid"].append(perf)
         best, best_state, best_epoch = master(perf), {k: v.detach().clone() for k, v in self.model.state_dict().items()}, -1
         for epoch in range(int(self.max_epoch)):
@@ -426,7 +541,7 @@ class Trainer(DeviceEvalMixin):
                 self.scheduler.step()
             if parameter_controller is not None and hasattr(parameter_controller, "step"):
                 parameter_controller.step(epoch)
-            perf, _ = self.inference(dataloader_dict[VALIDSET], keep_logits=False)
+            perf, _ = evaluate(dataloader_dict[VALIDSET], keep_logits=False)
             history["valid"].append(perf)
             if master(perf) > best:
                 best, best_epoch = master(perf), epoch
@@ -434,6 +549,6 @@ class Trainer(DeviceEvalMixin):
         self.fit_finished = True
         if TESTSET in dataloader_dict:
             self.model.load_state_dict(best_state, strict=True)
-            history["test"], history["test_logits"] = self.inference(dataloader_dict[TESTSET])
+            history["test"], history["test_logits"] = evaluate(dataloader_dict[TESTSET])
         history["best_epoch"] = best_epoch
         return history

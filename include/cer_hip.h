@@ -460,6 +460,13 @@ int cer_attention_bwd(const float *q, const float *k, const float *v, const floa
  * win_out [nw][Lw][C], starts [nw] (device int32), out [total][C]. */
 int cer_window_stitch(const float *win_out, const int *starts, int nw, int Lw, int C, int total, float *out, void *stream);
 
+/* cer_window_stitch for V videos in one launch.  win_out [nw][Lw][C] holds the videos' windows, video after video, each in
+ * window order; video v owns windows [win_offsets[v], win_offsets[v+1]) and rows [frame_offsets[v], frame_offsets[v+1]) of
+ * out [R][C]; win_start[w] is window w's start frame inside its own video.  All pointers are device pointers (int32 offsets,
+ * V+1 entries each).  Every element equals the one-video cer_window_stitch result bit for bit. */
+int cer_window_stitch_multi(const float *win_out, const int *win_start, const int *win_offsets, const int *frame_offsets,
+                            int V, int nw, int Lw, int C, int R, float *out, void *stream);
+
 /* Accumulate (+=) the confusion counts of a batch of V videos: logits [R][C] (the videos' frames concatenated), labels [R]
  * (float class ids), video_offsets [V+1] (device int32 row offsets).  frame_cm [C][C]: counts[label][argmax]; video_cm
  * [3][C][C]: the same per video for the reference's three frame -> video decisions (majority vote / mean logits / mean
