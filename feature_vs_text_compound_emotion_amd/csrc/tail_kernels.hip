@@ -678,13 +678,19 @@ extern "C" size_t cer_col_sum_workspace_bytes(int R, int C) {
     return slabs > 1 ? (size_t)2 * slabs * C * sizeof(float) : 0;   // two partial arrays: the paired sums below
 }
 
-// out1 / out2 = the two column sums of col_sum_pair4_kernel (dense rows, C % 4 == 0, more than one slab); false = not applicable
+// the float4 column-sum kernels load 16 bytes at base + r * ld + c (c % 4 == 0): pitch AND base must be 16-byte aligned -- a column
+// slice starting at a column that is not a multiple of 4 has an aligned pitch but a 4-byte-aligned base.  NULL counts as aligned.
+static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+// out1 / out2 = the two column sums of col_sum_pair4_kernel (dense rows, C % 4 == 0, more than one slab, 16-byte-aligned
+// pointers); false = not applicable
 static bool col_sum_pair(const float *a, const float *b, const float *mean, const float *invstd, float *out1, float *out2, int R, int C,
                          void *workspace, size_t workspace_bytes, void *stream) {
     int rows_per_slab = 256;
     if ((R + 255) / 256 > 1024) rows_per_slab = ((R + 1023) / 1024 + 31) / 32 * 32;
     const int slabs = (R + rows_per_slab - 1) / rows_per_slab;
     if (slabs <= 1 || (C & 3) || !workspace || workspace_bytes < (size_t)2 * slabs * C * sizeof(float)) return false;
+    if (!aligned16(a) || !aligned16(b) || !aligned16(mean) || !aligned16(invstd)) return false;
     float *p1 = (float *)workspace, *p2 = p1 + (size_t)slabs * C;
     CER_LAUNCH(col_sum_pair4_kernel, dim3((C + 127) / 128, slabs), dim3(256), 0, ST, a, b, mean, invstd, p1, p2, R, C, rows_per_slab);
     CER_LAUNCH(col_sum_kernel, dim3((C + 31) / 32, 1), dim3(256), 0, ST, (const float *)p1, C, (const float *)nullptr, 0,
@@ -705,7 +711,8 @@ extern "C" int cer_col_sum(const float *a, int a_ld, const float *b, int b_ld, c
     if ((R + 255) / 256 > 1024) rows_per_slab = ((R + 1023) / 1024 + 31) / 32 * 32;
     const int slabs = (R + rows_per_slab - 1) / rows_per_slab;
     dim3 grid((C + 31) / 32, slabs);
-    const bool vec4 = slabs > 1 && (C & 3) == 0 && (!a || (a_ld & 3) == 0) && (!b || (b_ld & 3) == 0);
+    const bool vec4 = slabs > 1 && (C & 3) == 0 && (!a || (a_ld & 3) == 0) && (!b || (b_ld & 3) == 0) && aligned16(a) &&
+                      aligned16(b) && aligned16(mean) && aligned16(invstd);
     if (slabs == 1) {
         CER_LAUNCH(col_sum_kernel, grid, dim3(256), 0, ST, a, a_ld, b, b_ld, mean, invstd, out, R, C, rows_per_slab);
     } else {

@@ -27,6 +27,7 @@ from .visual_backbone import VisualBackbone
 CLASSIFICATION, REGRESSION = "CLASSIFICATION", "REGRESSION"  # reference constants.py:17-20
 TASKS = [CLASSIFICATION, REGRESSION]
 LN_EPS, BN_EPS, BN_MOMENTUM = 1e-5, 1e-5, 0.1
+ATTN_HEAD_DIMS, ATTN_MAX_MODALITIES = (8, 16, 32, 64), 4  # what cer_lfan_attn_* dispatches on
 
 
 def _linear_T(dy, w, residual=None):
@@ -137,6 +138,13 @@ class MultimodalMultiheadAttention(nn.Module):
         assert modal_dim % num_heads == 0, "Embedding dimension must be 0 modulo number of heads."
         self.modalities, self.embed_dim, self.num_heads = list(modalities), modal_dim, num_heads
         self.head_dim = modal_dim // num_heads
+        # refused here, not at the first forward: by then the train-mode BatchNorm would already have moved its running stats
+        if self.head_dim not in ATTN_HEAD_DIMS:
+            raise ValueError(f"modal_dim / num_heads = {self.head_dim}: the cross-modal attention kernel supports head dims "
+                             f"{{8, 16, 32, 64}} only")
+        if not 1 <= len(self.modalities) <= ATTN_MAX_MODALITIES:
+            raise ValueError(f"{len(self.modalities)} modalities: the cross-modal attention kernel supports 1 to "
+                             f"{ATTN_MAX_MODALITIES}")
         self.qkv_proj = nn.ModuleDict({m: nn.Linear(input_dim[m], 3 * modal_dim) for m in modalities})
         self.o_proj = nn.Linear(modal_dim * len(modalities), modal_dim * len(modalities))
         for m in modalities:

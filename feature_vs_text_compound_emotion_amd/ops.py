@@ -15,12 +15,24 @@ from ._lib import (ACT_GELU, ACT_LEAKY, ACT_NONE, ACT_PRELU, ACT_RELU, STORE_BF1
 LEAKY_SLOPE = 0.01
 
 
-def _dev_f32(t, name, contiguous=True):
+def _dev_f32(t, name, contiguous=True, shape=None):
+    """None passes (optional arguments); otherwise a float32 GPU tensor, contiguous unless told otherwise, and of
+    exactly ``shape`` when one is given."""
     if t is None:
         return
     if not (t.is_cuda and t.dtype == torch.float32 and (t.is_contiguous() or not contiguous)):
         raise ValueError(f"{name}: expected a contiguous float32 tensor on the GPU, got "
                          f"{t.dtype} {t.device} contiguous={t.is_contiguous()}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def _dense2d(t, name):
+    """A contiguous [R,C] float32 GPU tensor (the kernel hard-codes pitch C).  Returns (rows, cols)."""
+    _dev_f32(t, name)
+    if t.dim() != 2:
+        raise ValueError(f"{name}: expected a 2-D [R, C] tensor, got shape {tuple(t.shape)}")
+    return t.shape[0], t.shape[1]
 
 
 def _rows(t, name):
@@ -895,8 +907,9 @@ def col_sum(a):
 
 
 def act_mask_bwd(dy, y, mask=None, slope=LEAKY_SLOPE):
-    for t, n in ((dy, "dy"), (y, "y"), (mask, "mask")):
-        _dev_f32(t, n)
+    _dev_f32(dy, "dy")
+    for t, n in ((y, "y"), (mask, "mask")):
+        _dev_f32(t, n, shape=dy.shape)
     dz = torch.empty_like(dy)
     check(_lib.load().cer_act_mask_bwd(ptr(dy), ptr(y), ptr(mask), ptr(dz), dy.numel(), slope, current_stream()),
           "cer_act_mask_bwd")
@@ -904,8 +917,9 @@ def act_mask_bwd(dy, y, mask=None, slope=LEAKY_SLOPE):
 
 
 def tblock_tail_bwd(dout, out, a2, mask2=None, slope=LEAKY_SLOPE):
-    for t, n in ((dout, "dout"), (out, "out"), (a2, "a2"), (mask2, "mask2")):
-        _dev_f32(t, n)
+    _dev_f32(dout, "dout")
+    for t, n in ((out, "out"), (a2, "a2"), (mask2, "mask2")):
+        _dev_f32(t, n, shape=dout.shape)
     du, dz2 = torch.empty_like(dout), torch.empty_like(dout)
     check(_lib.load().cer_tblock_tail_bwd(ptr(dout), ptr(out), ptr(a2), ptr(mask2), ptr(du), ptr(dz2),
                                           dout.numel(), slope, current_stream()), "cer_tblock_tail_bwd")
@@ -917,10 +931,11 @@ def bn_rows_fwd(x, w, b, running_mean, running_var, train, eps=1e-5, momentum=0.
     None in eval mode.  Running stats are updated in place when ``train``."""
     r, c, x_ld = _rows(x, "x")
     for t, n in ((w, "w"), (b, "b"), (running_mean, "running_mean"), (running_var, "running_var")):
-        _dev_f32(t, n)
+        _dev_f32(t, n, shape=(c,))
     if out is None:
         out = _empty((r, c), x)
     _, _, y_ld = _rows(out, "out")
+    _dev_f32(out, "out", contiguous=False, shape=(r, c))
     sm = _empty((c,), x) if train else None
     si = _empty((c,), x) if train else None
     lib = _lib.load()
@@ -936,8 +951,8 @@ def bn_rows_stats(x, running_mean, running_var, eps=1e-5, momentum=0.1):
     """Train-mode statistics of the rows of x [R,C] alone: (save_mean, save_invstd), running buffers updated in place like
     ``bn_rows_fwd(train=True)``; no output tensor is written."""
     r, c, x_ld = _rows(x, "x")
-    _dev_f32(running_mean, "running_mean")
-    _dev_f32(running_var, "running_var")
+    _dev_f32(running_mean, "running_mean", shape=(c,))
+    _dev_f32(running_var, "running_var", shape=(c,))
     sm, si = _empty((c,), x), _empty((c,), x)
     lib = _lib.load()
     nbytes = lib.cer_bn_rows_fwd_workspace_bytes(r, c)
@@ -950,10 +965,13 @@ def bn_rows_stats(x, running_mean, running_var, eps=1e-5, momentum=0.1):
 def bn_rows_bwd(dy, x, save_mean, save_invstd, w, train=True, split_out=False, add=None):
     """``split_out`` (train mode, dense rows): dx as a Split tensor written by the apply pass itself.  ``add`` (train mode,
     dense rows, C % 4 == 0): dx = BatchNorm-backward(dy) + add in the same pass."""
+    r, c, _ = _rows(dy, "dy")
+    for t, nme in ((save_mean, "save_mean"), (save_invstd, "save_invstd"), (w, "w")):
+        _dev_f32(t, nme, shape=(c,))
     if add is not None:
-        for t, nme in ((dy, "dy"), (x, "x"), (add, "add")):
-            _dev_f32(t, nme)
-        r, c = dy.shape
+        for t, nme in ((dy, "dy"), (x, "x")):
+            _dev_f32(t, nme, shape=(r, c))
+        _dev_f32(add, "add")
         if split_out or tuple(add.shape) != (r, c) or c % 4:
             raise ValueError("bn_rows_bwd(add=...): fp32 result, add of the rows' shape, C % 4 == 0")
         dx, dw, db = _empty((r, c), x), _empty((c,), x), _empty((c,), x)
@@ -963,8 +981,7 @@ def bn_rows_bwd(dy, x, save_mean, save_invstd, w, train=True, split_out=False, a
         return dx, dw, db
     if split_out:
         _dev_f32(dy, "dy")
-        _dev_f32(x, "x")
-        r, c = dy.shape
+        _dev_f32(x, "x", shape=(r, c))
         dx, dw, db = Split.empty((r, c), x.device), _empty((c,), x), _empty((c,), x)
         ws, nbytes = _col_ws(r, c, x)
         check(_lib.load().cer_bn_rows_bwd_split(ptr(dy), ptr(x), ptr(save_mean), ptr(save_invstd), ptr(w), ptr(dx.hi), ptr(dx.lo),
@@ -972,6 +989,7 @@ def bn_rows_bwd(dy, x, save_mean, save_invstd, w, train=True, split_out=False, a
         return dx, dw, db
     r, c, dy_ld = _rows(dy, "dy")
     _, _, x_ld = _rows(x, "x")
+    _dev_f32(x, "x", contiguous=False, shape=(r, c))
     dx, dw, db = _empty((r, c), x), _empty((c,), x), _empty((c,), x)
     ws, nbytes = _col_ws(r, c, x)
     check(_lib.load().cer_bn_rows_bwd(ptr(dy), dy_ld, ptr(x), x_ld, ptr(save_mean), ptr(save_invstd), ptr(w),
@@ -987,11 +1005,20 @@ def _ptr_array(tensors):
     return arr
 
 
+def _check_qkv(qkv_list, num_heads, head_dim):
+    """Every modality's qkv a contiguous [R, H*3*hd] tensor with the same R.  Returns (R, M).  The head dim and the
+    modality count (1..4) are the C dispatcher's to refuse."""
+    if len(qkv_list) == 0:
+        raise ValueError("qkv_list: expected at least one modality")
+    r = qkv_list[0].shape[0] if qkv_list[0].dim() == 2 else -1
+    for i, t in enumerate(qkv_list):
+        _dev_f32(t, f"qkv[{i}]", shape=(r, num_heads * 3 * head_dim))
+    return r, len(qkv_list)
+
+
 def lfan_attn_fwd(qkv_list, num_heads, head_dim):
     """qkv_list: per modality [R, H*3*hd] -> (vals [R, H*M*hd], probs [R,H,M,M])."""
-    for t in qkv_list:
-        _dev_f32(t, "qkv")
-    r, m = qkv_list[0].shape[0], len(qkv_list)
+    r, m = _check_qkv(qkv_list, num_heads, head_dim)
     vals = _empty((r, num_heads * m * head_dim), qkv_list[0])
     probs = _empty((r, num_heads, m, m), qkv_list[0])
     check(_lib.load().cer_lfan_attn_fwd(_ptr_array(qkv_list), ptr(vals), ptr(probs), r, num_heads, m, head_dim,
@@ -1000,8 +1027,9 @@ def lfan_attn_fwd(qkv_list, num_heads, head_dim):
 
 
 def lfan_attn_bwd(qkv_list, dvals, probs, num_heads, head_dim):
-    _dev_f32(dvals, "dvals")
-    r, m = qkv_list[0].shape[0], len(qkv_list)
+    r, m = _check_qkv(qkv_list, num_heads, head_dim)
+    _dev_f32(dvals, "dvals", shape=(r, num_heads * m * head_dim))
+    _dev_f32(probs, "probs", shape=(r, num_heads, m, m))
     dqkv = [torch.empty_like(t) for t in qkv_list]
     check(_lib.load().cer_lfan_attn_bwd(_ptr_array(qkv_list), ptr(dvals), ptr(probs), _ptr_array(dqkv), r,
                                         num_heads, m, head_dim, current_stream()), "cer_lfan_attn_bwd")
@@ -1009,12 +1037,15 @@ def lfan_attn_bwd(qkv_list, dvals, probs, num_heads, head_dim):
 
 
 def layernorm_fwd(x, gamma, beta, mask=None, eps=1e-5, out=None, save=True):
-    _dev_f32(x, "x")
-    _dev_f32(mask, "mask")
-    r, c = x.shape
+    """y = LN(x * mask) * gamma + beta over the rows of a dense x [R,C]; ``out`` may be a column slice of a wider buffer."""
+    r, c = _dense2d(x, "x")
+    _dev_f32(mask, "mask", shape=(r, c))
+    _dev_f32(gamma, "gamma", shape=(c,))
+    _dev_f32(beta, "beta", shape=(c,))
     if out is None:
         out = _empty((r, c), x)
     _, _, y_ld = _rows(out, "out")
+    _dev_f32(out, "out", contiguous=False, shape=(r, c))
     mean = _empty((r,), x) if save else None
     rstd = _empty((r,), x) if save else None
     check(_lib.load().cer_layernorm_fwd(ptr(x), ptr(mask), ptr(gamma), ptr(beta), ptr(out), y_ld, ptr(mean),
@@ -1023,7 +1054,13 @@ def layernorm_fwd(x, gamma, beta, mask=None, eps=1e-5, out=None, save=True):
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, mask=None):
+    """dy may be a column slice of a wider buffer; x and mask are read at pitch C, so they must be dense."""
     r, c, dy_ld = _rows(dy, "dy")
+    _dev_f32(x, "x", shape=(r, c))
+    _dev_f32(mask, "mask", shape=(r, c))
+    _dev_f32(gamma, "gamma", shape=(c,))
+    _dev_f32(mean, "mean", shape=(r,))
+    _dev_f32(rstd, "rstd", shape=(r,))
     dx, scratch = _empty((r, c), x), _empty((r, c), x)
     dg, db = _empty((c,), x), _empty((c,), x)
     ws, nbytes = _col_ws(r, c, x)
@@ -1071,9 +1108,8 @@ def cross_entropy(logits2d, labels_f32, want_grad=True, check_labels=True):
     """Mean CE over rows; labels are float32 class ids (cast like ``.long()``), -100 = ignore_index.  Returns
     (loss scalar tensor, dlogits or None).  Out-of-range labels raise IndexError -- from this call when the counter of an
     earlier call has arrived, at the latest from ``flush_label_check()``; the affected step's loss is NaN either way."""
-    _dev_f32(logits2d, "logits")
+    r, c = _dense2d(logits2d, "logits")
     _dev_f32(labels_f32, "labels")
-    r, c = logits2d.shape
     if labels_f32.numel() != r:
         raise ValueError(f"cross_entropy: {labels_f32.numel()} labels for {r} rows")
     loss = _empty((), logits2d)
@@ -1104,8 +1140,8 @@ def leaky_relu(x, slope=LEAKY_SLOPE):
 
 
 def softmax_gate_fwd(z, c):
-    _dev_f32(z, "z")
-    _dev_f32(c, "c")
+    _dense2d(z, "z")
+    _dev_f32(c, "c", shape=z.shape)
     out, prob = torch.empty_like(z), torch.empty_like(z)
     check(_lib.load().cer_softmax_gate_fwd(ptr(z), ptr(c), ptr(out), ptr(prob), z.shape[0], z.shape[1], current_stream()),
           "cer_softmax_gate_fwd")
@@ -1113,8 +1149,9 @@ def softmax_gate_fwd(z, c):
 
 
 def softmax_gate_bwd(dout, prob, c):
-    for t, n in ((dout, "dout"), (prob, "prob"), (c, "c")):
-        _dev_f32(t, n)
+    _dense2d(dout, "dout")
+    for t, n in ((prob, "prob"), (c, "c")):
+        _dev_f32(t, n, shape=dout.shape)
     dz, dc = torch.empty_like(dout), torch.empty_like(dout)
     check(_lib.load().cer_softmax_gate_bwd(ptr(dout), ptr(prob), ptr(c), ptr(dz), ptr(dc), dout.shape[0], dout.shape[1],
                                            current_stream()), "cer_softmax_gate_bwd")
@@ -1124,6 +1161,7 @@ def softmax_gate_bwd(dout, prob, c):
 def copy_cols(x, out):
     r, c, x_ld = _rows(x, "x")
     _, _, y_ld = _rows(out, "out")
+    _dev_f32(out, "out", contiguous=False, shape=(r, c))
     check(_lib.load().cer_copy_cols(ptr(x), x_ld, ptr(out), y_ld, r, c, current_stream()), "cer_copy_cols")
     return out
 

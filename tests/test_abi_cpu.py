@@ -84,3 +84,18 @@ def test_lfan_forward_without_gpu_raises():
     # write through the pointer of a CPU tensor (a GPU memory-access fault)
     with pytest.raises(ValueError, match="expected a GPU device"):
         m({"vggish": torch.zeros(1, 1, 4, 128)})
+
+
+@pytest.mark.parametrize("modal_dim,num_heads,n_mods,match", [
+    (24, 2, 3, r"\{8, 16, 32, 64\}"),     # head dim 12
+    (256, 2, 3, r"\{8, 16, 32, 64\}"),    # head dim 128
+    (32, 2, 5, "1 to 4"),                  # five modalities
+])
+def test_lfan_refuses_attention_shapes_the_kernel_lacks_at_construction(modal_dim, num_heads, n_mods, match):
+    """Refused when the model is built: at the first forward the train-mode BatchNorm would already have moved its running
+    statistics before the attention kernel refused the head dim."""
+    from feature_vs_text_compound_emotion_amd.lfan import MultimodalMultiheadAttention
+    mods = [f"m{i}" for i in range(n_mods)]
+    with pytest.raises(ValueError, match=match):
+        MultimodalMultiheadAttention(mods, {m: 32 for m in mods}, modal_dim, num_heads)
+    MultimodalMultiheadAttention(mods[:4], {m: 32 for m in mods[:4]}, 64, 4)   # head dim 16, 4 modalities: accepted
