@@ -54,6 +54,8 @@ _SIGNATURES = {
     "cer_bn_finalize_workspace_bytes": (c_size_t, [c_int, c_int]),
     "cer_bn_finalize": (c_int, [_P, c_int, c_int, c_double, _P, _P, _P, _P, c_float, c_float, _P, _P, _P, c_size_t,
                                 _P]),
+    "cer_bn_partial_sums": (c_int, [_P, c_int, c_int, _P, _P, c_size_t, _P]),
+    "cer_bn_finalize_sums": (c_int, [_P, c_int, c_double, _P, _P, _P, _P, c_float, c_float, _P, _P, _P]),
     "cer_bn_apply_stats_tiles": (c_int, [c_int]),
     "cer_bn_apply_nhwc": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
                                   c_int, _P]),
@@ -89,6 +91,11 @@ _SIGNATURES = {
                                 c_float, _P, c_size_t, _P]),
     "cer_bn_rows_bwd": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t,
                                 _P]),
+    "cer_bn_rows_moments": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "cer_bn_rows_merge": (c_int, [_P, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P]),
+    "cer_bn_rows_apply": (c_int, [_P, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "cer_bn_rows_bwd_sums": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
+    "cer_bn_rows_bwd_apply": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_double, _P, c_int, c_int, _P]),
     "cer_lfan_attn_fwd": (c_int, [POINTER(_P), _P, _P, c_int, c_int, c_int, c_int, _P]),
     "cer_lfan_attn_bwd": (c_int, [POINTER(_P), _P, _P, POINTER(_P), c_int, c_int, c_int, c_int, _P]),
     "cer_layernorm_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_float, _P]),

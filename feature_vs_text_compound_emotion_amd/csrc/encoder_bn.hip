@@ -28,14 +28,11 @@ __global__ void bn_partial_reduce_kernel(const float *__restrict__ partials, int
     }
 }
 
-// One wave per channel: lanes fold the group rows, then a double-precision wave reduction.
-__global__ void bn_finalize_kernel(const double *__restrict__ groups, int ngroups, int C, double count,
-                                   const float *__restrict__ gamma, const float *__restrict__ beta,
-                                   float *__restrict__ running_mean, float *__restrict__ running_var,
-                                   float momentum, float eps, float *__restrict__ scale, float *__restrict__ shift) {
-    const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (c >= C) return;
-    double s1 = 0.0, s2 = 0.0;
+// Per-channel (sum, sum of squares) of one channel: lanes fold the group rows, then a double-precision wave reduction.
+// The result is valid in lane 0 only.
+__device__ __forceinline__ void bn_fold_groups(const double *__restrict__ groups, int ngroups, int C, int c, int lane,
+                                               double &s1, double &s2) {
+    s1 = 0.0, s2 = 0.0;
     for (int t = lane; t < ngroups; t += 64) {
         s1 += groups[((size_t)t * 2 + 0) * C + c];
         s2 += groups[((size_t)t * 2 + 1) * C + c];
@@ -45,18 +42,64 @@ __global__ void bn_finalize_kernel(const double *__restrict__ groups, int ngroup
         s1 += __shfl_xor(s1, o);
         s2 += __shfl_xor(s2, o);
     }
-    if (lane != 0) return;
+}
+
+// (sum, sum of squares) over `count` elements -> scale / shift and torch's running-stat update.  Shared by the one-call
+// finalize and the finalize from (globally all-reduced) sums, so that the two give the same bits for the same sums.  FP
+// contraction is off and the two fused multiply-adds are spelled out: left to itself the compiler contracts the running
+// update into an FMA in one kernel and not in the other.
+__device__ __forceinline__ void bn_finalize_channel(int c, double s1, double s2, double count,
+                                                    const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                    float *__restrict__ running_mean, float *__restrict__ running_var,
+                                                    float momentum, float eps, float *__restrict__ scale,
+                                                    float *__restrict__ shift) {
+#pragma clang fp contract(off)
     const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
+    double var = fma(-mean, mean, s2 / count);
     if (var < 0.0) var = 0.0;
     const float sc = gamma[c] * (float)(1.0 / sqrt(var + (double)eps));
     scale[c] = sc;
-    shift[c] = beta[c] - (float)mean * sc;
+    shift[c] = fmaf(-(float)mean, sc, beta[c]);
     if (running_mean) {
         const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
         running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
         running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
     }
+}
+
+// One wave per channel.
+__global__ void bn_finalize_kernel(const double *__restrict__ groups, int ngroups, int C, double count,
+                                   const float *__restrict__ gamma, const float *__restrict__ beta,
+                                   float *__restrict__ running_mean, float *__restrict__ running_var,
+                                   float momentum, float eps, float *__restrict__ scale, float *__restrict__ shift) {
+    const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= C) return;
+    double s1, s2;
+    bn_fold_groups(groups, ngroups, C, c, lane, s1, s2);
+    if (lane != 0) return;
+    bn_finalize_channel(c, s1, s2, count, gamma, beta, running_mean, running_var, momentum, eps, scale, shift);
+}
+
+// Split form for synchronised statistics: the same fold, written out as sums [2][C] (sum | sum of squares) so that a
+// cross-rank all-reduce can sit between it and bn_finalize_sums_kernel.
+__global__ void bn_sums_kernel(const double *__restrict__ groups, int ngroups, int C, double *__restrict__ sums) {
+    const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= C) return;
+    double s1, s2;
+    bn_fold_groups(groups, ngroups, C, c, lane, s1, s2);
+    if (lane != 0) return;
+    sums[c] = s1;
+    sums[C + c] = s2;
+}
+
+__global__ void bn_finalize_sums_kernel(const double *__restrict__ sums, int C, double count,
+                                        const float *__restrict__ gamma, const float *__restrict__ beta,
+                                        float *__restrict__ running_mean, float *__restrict__ running_var,
+                                        float momentum, float eps, float *__restrict__ scale, float *__restrict__ shift) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    bn_finalize_channel(c, sums[c], sums[C + c], count, gamma, beta, running_mean, running_var, momentum, eps, scale,
+                        shift);
 }
 
 static int apply_rows_per_block(int P) {  // ~2048 blocks, 128..2048 rows each (multiple of 128)
@@ -354,6 +397,33 @@ extern "C" int cer_bn_finalize(const float *partials, int tiles, int C, double c
                rows_per_group, (double *)workspace);
     CER_LAUNCH(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const double *)workspace,
                used, C, count, gamma, beta, running_mean, running_var, momentum, eps, scale, shift);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_bn_partial_sums(const float *partials, int tiles, int C, double *sums, void *workspace,
+                                   size_t workspace_bytes, void *stream) {
+    if (!partials || tiles <= 0 || C <= 0 || !sums) return cer_set_error(CER_ERR_INVALID_ARG, "bn_partial_sums: bad argument");
+    if (!workspace || workspace_bytes < cer_bn_finalize_workspace_bytes(tiles, C) || ((uintptr_t)workspace & 7))
+        return cer_set_error(CER_ERR_WORKSPACE, "bn_partial_sums: workspace too small or not 8-byte aligned");
+    const int groups = tiles < FIN_MAX_GROUPS ? tiles : FIN_MAX_GROUPS;   // the same two stages as cer_bn_finalize
+    const int rows_per_group = (tiles + groups - 1) / groups;
+    const int used = (tiles + rows_per_group - 1) / rows_per_group;
+    CER_LAUNCH(bn_partial_reduce_kernel, dim3(used), dim3(256), 0, (hipStream_t)stream, partials, tiles, C,
+               rows_per_group, (double *)workspace);
+    CER_LAUNCH(bn_sums_kernel, dim3((C + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const double *)workspace, used, C, sums);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_bn_finalize_sums(const double *sums, int C, double count, const float *gamma, const float *beta,
+                                    float *running_mean, float *running_var, float momentum, float eps, float *scale,
+                                    float *shift, void *stream) {
+    if (!sums || C <= 0 || !(count > 0) || !gamma || !beta || !scale || !shift ||
+        ((running_mean == nullptr) != (running_var == nullptr)))
+        return cer_set_error(CER_ERR_INVALID_ARG, "bn_finalize_sums: bad argument");
+    CER_LAUNCH(bn_finalize_sums_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, sums, C, count, gamma, beta,
+               running_mean, running_var, momentum, eps, scale, shift);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }

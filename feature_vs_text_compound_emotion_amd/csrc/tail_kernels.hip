@@ -312,19 +312,91 @@ __global__ void bn_rows_apply_kernel(const float *__restrict__ x, int x_ld, cons
     y[(size_t)r * y_ld + c] = (x[(size_t)r * x_ld + c] - mean[c]) * is * w[c] + b[c];
 }
 
+// ---- synchronised (cross-rank) statistics: local moments -> exchange -> merge -> apply
+// A rank's statistics travel as (count, mean, M2 = sum (x - mean)^2) in float64, M2 taken about the rank's OWN mean (two
+// passes over an L2-resident tensor), and ranks are merged with Chan's pairwise update
+//   n = na + nb,  d = mb - ma,  mean = ma + d * nb / n,  M2 = M2a + M2b + d^2 * na * nb / n
+// whose terms are all non-negative: nothing cancels whatever the channel's offset.  Raw (sum x, sum x^2) would need
+// E[x^2] - E[x]^2, which loses log10(mean^2 / var) digits -- 6 of fp32's 7 at mean 1e3, std 1.  Every rank merges the
+// gathered [K][3][C] moments in rank order, so every rank computes the same bits.
+// moments [3][C]: count | mean | M2.  Block = 32 channels x 8 row lanes, as bn_rows_stats_kernel.
+__global__ void bn_rows_moments_kernel(const float *__restrict__ x, int x_ld, int R, int C, double *__restrict__ moments) {
+    __shared__ double red[8][33];
+    __shared__ double mu_s[32];
+    const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + cx;
+    double s = 0.0;
+    if (c < C)
+        for (int r = ry; r < R; r += 8) s += (double)x[(size_t)r * x_ld + c];
+    red[ry][cx] = s;
+    __syncthreads();
+    if (ry == 0) {
+        double t = 0.0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) t += red[i][cx];
+        mu_s[cx] = t / (double)R;
+    }
+    __syncthreads();
+    const double mu = mu_s[cx];
+    s = 0.0;
+    if (c < C)
+        for (int r = ry; r < R; r += 8) {
+            const double d = (double)x[(size_t)r * x_ld + c] - mu;
+            s += d * d;
+        }
+    __syncthreads();
+    red[ry][cx] = s;
+    __syncthreads();
+    if (ry == 0 && c < C) {
+        double t = 0.0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) t += red[i][cx];
+        moments[c] = (double)R;
+        moments[C + c] = mu;
+        moments[2 * C + c] = t;
+    }
+}
+
+// K moment blocks [K][3][C] -> save_mean / save_invstd of the union and the running update with its unbiased variance.
+// One thread per channel; blocks of zero rows (an empty shard) drop out of the merge.
+__global__ void bn_rows_merge_kernel(const double *__restrict__ moments, int K, int C, float eps, float momentum,
+                                     float *__restrict__ save_mean, float *__restrict__ save_invstd,
+                                     float *__restrict__ running_mean, float *__restrict__ running_var) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    double n = 0.0, mean = 0.0, m2 = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const double *mk = moments + (size_t)k * 3 * C;
+        const double nb = mk[c];
+        if (!(nb > 0.0)) continue;
+        const double mb = mk[C + c], tot = n + nb, d = mb - mean;
+        mean += d * (nb / tot);
+        m2 += mk[2 * C + c] + d * d * (n * nb / tot);
+        n = tot;
+    }
+    const double var = n > 0.0 ? m2 / n : 0.0;
+    save_mean[c] = (float)mean;
+    save_invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+    if (running_mean) {
+        const double unbiased = n > 1.0 ? m2 / (n - 1.0) : var;
+        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
+        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+    }
+}
+
 // dx = w*invstd/R * (R*dy - sum_dy - xhat * sum_dy_xhat)   (train); eval: dx = dy*w*invstd
 __global__ void bn_rows_bwd_kernel(const float *__restrict__ dy, int dy_ld, const float *__restrict__ x, int x_ld,
                                    const float *__restrict__ mean, const float *__restrict__ invstd,
                                    const float *__restrict__ w, const float *__restrict__ sum_dy,
                                    const float *__restrict__ sum_dy_xhat, float *__restrict__ dx, int R, int C,
-                                   int train) {
+                                   int train, float count) {
     size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)R * C) return;
     const int r = (int)(idx / C), c = (int)(idx - (size_t)r * C);
     const float is = invstd[c], g = dy[(size_t)r * dy_ld + c];
-    if (train) {
+    if (train) {  // count: the rows the statistics were taken over (R, or the global batch's rows under synchronised BN)
         const float xh = (x[(size_t)r * x_ld + c] - mean[c]) * is;
-        dx[idx] = w[c] * is * (g - (sum_dy[c] + xh * sum_dy_xhat[c]) / (float)R);
+        dx[idx] = w[c] * is * (g - (sum_dy[c] + xh * sum_dy_xhat[c]) / count);
     } else {
         dx[idx] = g * w[c] * is;
     }
@@ -842,7 +914,62 @@ extern "C" int cer_bn_rows_bwd(const float *dy, int dy_ld, const float *x, int x
         if (rc) return rc;
     }
     CER_LAUNCH(bn_rows_bwd_kernel, dim3(cer_blocks((size_t)R * C, 256)), dim3(256), 0, ST, dy, dy_ld, x, x_ld,
-                       save_mean, save_invstd, w, (const float *)db, (const float *)dw, dx, R, C, train);
+                       save_mean, save_invstd, w, (const float *)db, (const float *)dw, dx, R, C, train, (float)R);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_bn_rows_moments(const float *x, int x_ld, int R, int C, double *moments, void *stream) {
+    if (!x || !moments || R <= 0 || C <= 0 || x_ld < C) return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_moments: bad argument");
+    CER_LAUNCH(bn_rows_moments_kernel, dim3((C + 31) / 32), dim3(256), 0, ST, x, x_ld, R, C, moments);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_bn_rows_merge(const double *moments, int K, int C, float eps, float momentum, float *save_mean,
+                                 float *save_invstd, float *running_mean, float *running_var, void *stream) {
+    if (!moments || K <= 0 || C <= 0 || !save_mean || !save_invstd || ((running_mean == nullptr) != (running_var == nullptr)))
+        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_merge: bad argument");
+    CER_LAUNCH(bn_rows_merge_kernel, dim3((C + 255) / 256), dim3(256), 0, ST, moments, K, C, eps, momentum, save_mean, save_invstd,
+               running_mean, running_var);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_bn_rows_apply(const float *x, int x_ld, const float *mean, const float *invstd, const float *w, const float *b,
+                                 float *y, int y_ld, int R, int C, void *stream) {
+    if (!x || !mean || !invstd || !w || !b || !y || R <= 0 || C <= 0 || x_ld < C || y_ld < C)
+        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_apply: bad argument");
+    CER_LAUNCH(bn_rows_apply_kernel, dim3(cer_blocks((size_t)R * C, 256)), dim3(256), 0, ST, x, x_ld, mean, invstd, 0, 0.f, w, b,
+               y, y_ld, R, C);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_bn_rows_bwd_sums(const float *dy, int dy_ld, const float *x, int x_ld, const float *save_mean,
+                                    const float *save_invstd, float *sums, int R, int C, void *workspace, size_t workspace_bytes,
+                                    void *stream) {
+    if (!dy || !x || !save_mean || !save_invstd || !sums || R <= 0 || C <= 0 || dy_ld < C || x_ld < C)
+        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd_sums: bad argument");
+    float *db = sums, *dw = sums + C;   // the same reductions, in the same order, as cer_bn_rows_bwd
+    if (!(dy_ld == C && x_ld == C && col_sum_pair(dy, x, save_mean, save_invstd, db, dw, R, C, workspace, workspace_bytes, stream))) {
+        int rc = cer_col_sum(dy, dy_ld, nullptr, 0, nullptr, nullptr, db, R, C, workspace, workspace_bytes, stream);
+        if (rc) return rc;
+        rc = cer_col_sum(dy, dy_ld, x, x_ld, save_mean, save_invstd, dw, R, C, workspace, workspace_bytes, stream);
+        if (rc) return rc;
+    }
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_bn_rows_bwd_apply(const float *dy, int dy_ld, const float *x, int x_ld, const float *save_mean,
+                                     const float *save_invstd, const float *w, const float *sums, double count, float *dx, int R,
+                                     int C, void *stream) {
+    if (!dy || !x || !save_mean || !save_invstd || !w || !sums || !dx || R <= 0 || C <= 0 || dy_ld < C || x_ld < C ||
+        !(count > 0))
+        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd_apply: bad argument");
+    CER_LAUNCH(bn_rows_bwd_kernel, dim3(cer_blocks((size_t)R * C, 256)), dim3(256), 0, ST, dy, dy_ld, x, x_ld, save_mean,
+               save_invstd, w, sums, sums + C, dx, R, C, 1, (float)count);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }

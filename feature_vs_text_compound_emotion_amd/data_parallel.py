@@ -14,7 +14,10 @@ Semantics: each rank equals the single-process reference run on its shard of
 the global batch, and the applied gradient is the mean over ranks
 (== the gradient of the mean loss over the global batch when every rank holds
 the same number of frames).  BatchNorm statistics stay local to the rank, like
-torch DDP without SyncBN.
+torch DDP without SyncBN -- unless ``sync_bn`` is set: then every train-mode
+BatchNorm of the encoder and the tail normalises with the statistics of the
+GLOBAL batch (``BatchNormSync``), and N ranks x B/N clips compute the
+single-process step on B clips.
 """
 import os
 
@@ -40,11 +43,72 @@ def init_process_group_from_env(backend=None, single_rank_group=False):
     return rank, world, local
 
 
+class BatchNormSync:
+    """Synchronised batch statistics for the train-mode BatchNorms of the HIP modules (``IR50``, ``LFAN``, ``CAN`` / ``JMT``),
+    which call the methods below in place of their one-call BatchNorm ops while one of these is attached to them as
+    ``bn_sync``.  The collectives run on a process group of their own, so they never interleave with the gradient slices
+    that the overlapped exchange issues from autograd hooks on the default group; with RCCL they are stream-ordered (no
+    host synchronisation).
+
+    * encoder BatchNorm2d: float64 (sum, sum of squares) per channel, all-reduced, finalized over ``world x`` the local
+      element count;
+    * row BatchNorm1d forward: float64 (count, mean, M2) per rank, all-gathered and merged in rank order (identical bits on
+      every rank; see cer_bn_rows_merge);
+    * row BatchNorm1d backward: the float32 (sum dy, sum dy * x_hat) all-reduced, dx from the global sums over
+      ``world x`` the local rows; dw and db stay the rank's own (the gradient all-reduce averages them).
+
+    The element counts assume equal shards (what ``ClipDataParallel.shard`` gives when the global batch divides by the
+    world size) -- the same assumption under which the mean of the ranks' gradients is the full-batch gradient."""
+
+    def __init__(self, group, world, rank):
+        self.group, self.world, self.rank = group, world, rank
+
+    def __deepcopy__(self, memo):
+        return self      # a handle on the process group: a deep-copied model (best-model snapshots) shares it
+
+    def _all_reduce(self, t):
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t
+
+    def encoder_finalize(self, partials, count, bn):
+        """``ops.bn_finalize`` over the global batch: (scale, shift), running buffers updated with the global statistics."""
+        from . import ops
+        sums = self._all_reduce(ops.bn_partial_sums(partials))
+        return ops.bn_finalize_sums(sums, count * self.world, bn.weight.detach(), bn.bias.detach(), bn.running_mean,
+                                    bn.running_var, momentum=bn.momentum, eps=bn.eps)
+
+    def rows_fwd(self, x, w, b, running_mean, running_var, eps, momentum, out=None):
+        """``ops.bn_rows_fwd(train=True)`` over the global batch: (y, save_mean, save_invstd)."""
+        from . import ops
+        local = ops.bn_rows_moments(x)
+        gathered = torch.empty((self.world * 3, local.shape[1]), device=local.device, dtype=local.dtype)
+        dist.all_gather_into_tensor(gathered, local, group=self.group)
+        sm, si = ops.bn_rows_merge(gathered.view(self.world, 3, -1), running_mean, running_var, eps, momentum)
+        return ops.bn_rows_apply(x, sm, si, w, b, out=out), sm, si
+
+    def rows_bwd(self, dy, x, save_mean, save_invstd, w):
+        """``ops.bn_rows_bwd(train=True)`` over the global batch: (dx, dw, db), dw / db of the local rows."""
+        from . import ops
+        local = ops.bn_rows_bwd_sums(dy, x, save_mean, save_invstd)
+        total = self._all_reduce(local.clone())
+        dx = ops.bn_rows_bwd_apply(dy, x, save_mean, save_invstd, w, total, dy.shape[0] * self.world)
+        return dx, local[1], local[0]
+
+
+def _bn_sync_owners(model):
+    """The modules that run train-mode BatchNorms through HIP calls and read ``bn_sync``."""
+    return [m for m in model.modules() if hasattr(type(m), "bn_sync")]
+
+
 class ClipDataParallel:
     """Gradient bucket + collectives for a model whose trainable part is small."""
 
-    def __init__(self, model, world_size=None, broadcast=True, overlap=False, bucket_mb=25.0):
-        """``overlap``: cut the flat bucket into slices of ``bucket_mb`` (in parameter order) and start the all-reduce of a
+    def __init__(self, model, world_size=None, broadcast=True, overlap=False, bucket_mb=25.0, sync_bn=False):
+        """``sync_bn``: train-mode BatchNorms of the encoder and the tail normalise with the statistics of the global batch
+        (``BatchNormSync``; needs an initialised process group).  ``"force"`` runs the collectives with one rank too, like
+        ``overlap="force"``.  Off by default: each rank's BatchNorms see its own shard.
+
+        ``overlap``: cut the flat bucket into slices of ``bucket_mb`` (in parameter order) and start the all-reduce of a
         slice from an autograd hook as soon as the last gradient of the slice has been accumulated -- backward produces
         the gradients from the top of the model down, so with released encoder units (28-43 M parameters, 112-172 MB) the
         exchange of the tail's and the upper units' gradients runs under the backward of the units below.  Needs ONE
@@ -74,6 +138,13 @@ class ClipDataParallel:
         self.buckets, self._works = [], []
         if self.overlap:
             self._build_buckets(bucket_mb)
+        self.bn_sync = None
+        if sync_bn and (self.world > 1 or sync_bn == "force"):
+            if not dist.is_initialized():
+                raise RuntimeError("sync_bn needs an initialised process group (init_process_group_from_env)")
+            self.bn_sync = BatchNormSync(dist.new_group(), dist.get_world_size(), dist.get_rank())
+            for m in _bn_sync_owners(model):
+                m.bn_sync = self.bn_sync
 
     # ------------------------------------------------------------------ bucketed, overlapped exchange
     def _build_buckets(self, bucket_mb):

@@ -72,24 +72,34 @@ class LayerNormFn(torch.autograd.Function):
 
 
 class BNRowsFn(torch.autograd.Function):
+    """``sync``: None or a data_parallel.BatchNormSync -- in train mode the statistics (and the backward's sums) of all ranks'
+    rows."""
+
     @staticmethod
-    def forward(ctx, x, w, b, running_mean, running_var, train):
+    def forward(ctx, x, w, b, running_mean, running_var, train, sync=None):
         x = x.contiguous()
-        y, sm, si = ops.bn_rows_fwd(x, w, b, running_mean, running_var, train, BN_EPS, BN_MOMENTUM)
+        sync = sync if train else None
+        if sync is not None:
+            y, sm, si = sync.rows_fwd(x, w, b, running_mean, running_var, BN_EPS, BN_MOMENTUM)
+        else:
+            y, sm, si = ops.bn_rows_fwd(x, w, b, running_mean, running_var, train, BN_EPS, BN_MOMENTUM)
         if not train:
             sm, si = running_mean, torch.rsqrt(running_var + BN_EPS)
-        ctx.saved, ctx.train = (x, w, sm, si), train
+        ctx.saved, ctx.train, ctx.sync = (x, w, sm, si), train, sync
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w, sm, si = ctx.saved
-        dx, dw, db = ops.bn_rows_bwd(dy.contiguous(), x, sm, si, w, ctx.train)
-        return dx, dw, db, None, None, None
+        if ctx.sync is not None:
+            dx, dw, db = ctx.sync.rows_bwd(dy.contiguous(), x, sm, si, w)
+        else:
+            dx, dw, db = ops.bn_rows_bwd(dy.contiguous(), x, sm, si, w, ctx.train)
+        return dx, dw, db, None, None, None, None
 
 
-def batchnorm_rows(x, bn, train):
-    y = BNRowsFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, train)
+def batchnorm_rows(x, bn, train, sync=None):
+    y = BNRowsFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, train, sync)
     if train:
         bn.num_batches_tracked += 1
     return y
@@ -282,7 +292,14 @@ def _load_visual(root_dir, backbone_settings, head_hw, load_backbone):
 
 
 class _TailModel(nn.Module):
-    """Shared front: IR-50 on frames, one TCN + BatchNorm1d per modality (rows layout)."""
+    """Shared front: IR-50 on frames, one TCN + BatchNorm1d per modality (rows layout).
+
+    ``bn_sync`` (a data_parallel.BatchNormSync, attached by ClipDataParallel(sync_bn=...)): the BatchNorm1d of every modality
+    and ``bn1`` use the statistics of all ranks' rows.  For JMT / MT that does not make N ranks x B/N clips equal one process
+    on B clips: their final attention runs over all (frame, clip) tokens of a rank's batch, which no
+    BatchNorm exchange reconnects."""
+
+    bn_sync = None
 
     def _build_front(self, modalities, tcn_settings, backbone_settings, root_dir, head_hw, load_backbone):
         self.modalities = list(modalities)
@@ -315,6 +332,8 @@ class _TailModel(nn.Module):
         for m in self.modalities:
             if m not in X:
                 raise KeyError(m)
+        if "visual" in self.spatial:
+            self.spatial["visual"].backbone.check_sync_release()
         if self.training:
             self.dropout_seed += 1
         feats, bsz, length = {}, None, None
@@ -340,12 +359,12 @@ class _TailModel(nn.Module):
                 bsz, length = x.shape[0], x.shape[2]
                 rows = x.reshape(bsz * length, x.shape[-1])
             t = self.temporal[m].forward_rows(rows, bsz, length, seed=self.dropout_seed * 16 + i)
-            feats[m] = batchnorm_rows(t, self.bn[m], self.training)
+            feats[m] = batchnorm_rows(t, self.bn[m], self.training, self.bn_sync)
         return feats, bsz, length
 
     def _head(self, c, bsz, length):
         c = linear(c, self.fc1)
-        c = batchnorm_rows(c, self.bn1, self.training)
+        c = batchnorm_rows(c, self.bn1, self.training, self.bn_sync)
         c = linear(LeakyReLUFn.apply(c), self.fc2)
         c = c.view(bsz, length, -1)
         return torch.tanh(c) if self.task == REGRESSION else c

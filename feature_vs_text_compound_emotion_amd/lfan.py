@@ -46,13 +46,14 @@ class LFANHeadFunction(torch.autograd.Function):
 
     args: (meta, buffers, fusion_mask, *tensors) where tensors =
       [t_m for each modality] + per modality [bn_w, bn_b, qkv_w, qkv_b] + [o_w, o_b, ln_w, ln_b, r_w, r_b]
-    meta = (M, H, hd, train, sink); buffers = [(running_mean, running_var)] per modality (updated in place); ``sink``: None or a
-    list that receives the M BatchNorm outputs (detached views; what the reference leaves in the caller's dict).
+    meta = (M, H, hd, train, sink, sync); buffers = [(running_mean, running_var)] per modality (updated in place); ``sink``: None
+    or a list that receives the M BatchNorm outputs (detached views; what the reference leaves in the caller's dict); ``sync``:
+    None or a data_parallel.BatchNormSync -- the train-mode BatchNorms then use the statistics of all ranks' rows.
     """
 
     @staticmethod
     def forward(ctx, meta, buffers, fmask, *ts):
-        M, H, hd, train, sink = meta
+        M, H, hd, train, sink, sync = meta
         t = [x.contiguous() for x in ts[:M]]
         per = [ts[M + 4 * i:M + 4 * i + 4] for i in range(M)]
         o_w, o_b, ln_w, ln_b, r_w, r_b = ts[M + 4 * M:]
@@ -62,8 +63,11 @@ class LFANHeadFunction(torch.autograd.Function):
         for i in range(M):
             bn_w, bn_b, q_w, q_b = per[i]
             out = z[:, :enc0] if i == 0 else None
-            y, sm, si = ops.bn_rows_fwd(t[i], bn_w, bn_b, buffers[i][0], buffers[i][1], train, BN_EPS, BN_MOMENTUM,
-                                        out=out)
+            if train and sync is not None:
+                y, sm, si = sync.rows_fwd(t[i], bn_w, bn_b, buffers[i][0], buffers[i][1], BN_EPS, BN_MOMENTUM, out=out)
+            else:
+                y, sm, si = ops.bn_rows_fwd(t[i], bn_w, bn_b, buffers[i][0], buffers[i][1], train, BN_EPS, BN_MOMENTUM,
+                                            out=out)
             if not train:  # eval-mode backward (rare) needs the statistics actually used
                 sm, si = buffers[i][0], torch.rsqrt(buffers[i][1] + BN_EPS)
             ys.append(y)
@@ -75,7 +79,7 @@ class LFANHeadFunction(torch.autograd.Function):
         logits = ops.linear(z, _packed(r_w), bias=r_b)
         if sink is not None:
             sink.extend(y.detach() for y in ys)
-        ctx.meta, ctx.ts = meta[:4], ts
+        ctx.meta, ctx.sync, ctx.ts = meta[:4], sync, ts
         ctx.saved = (t, ys, stats, qkvs, vals, probs, o, ln_mean, ln_rstd, z, fmask, enc0)
         return logits
 
@@ -106,7 +110,10 @@ class LFANHeadFunction(torch.autograd.Function):
             if i == 0:  # the leader also feeds the regressor directly
                 lead = ops.copy_cols(dz[:, :enc0], torch.empty((rows, enc0), device=z.device, dtype=torch.float32))
             dy = _linear_T(dqkv[i], q_w, residual=lead)
-            dt, g[M + 4 * i + 0], g[M + 4 * i + 1] = ops.bn_rows_bwd(dy, t[i], stats[i][0], stats[i][1], bn_w, train)
+            if train and ctx.sync is not None:
+                dt, g[M + 4 * i + 0], g[M + 4 * i + 1] = ctx.sync.rows_bwd(dy, t[i], stats[i][0], stats[i][1], bn_w)
+            else:
+                dt, g[M + 4 * i + 0], g[M + 4 * i + 1] = ops.bn_rows_bwd(dy, t[i], stats[i][0], stats[i][1], bn_w, train)
             g[i] = dt if ctx.needs_input_grad[3 + i] else None
         return (None, None, None, *g)
 
@@ -169,6 +176,8 @@ class MultimodalTransformerEncoder(nn.Module):
 
 
 class LFAN(nn.Module):
+    bn_sync = None   # data_parallel.BatchNormSync (ClipDataParallel(sync_bn=...)): the temporal BatchNorms use global statistics
+
     def __init__(self, backbone_settings, output_dim: int, task: str, modality=("frame",), kernel_size=5,
                  example_length=300, tcn_attention=0,
                  tcn_channel={'video': [512, 256, 256, 128], 'cnn_res50': [512, 256, 256, 128],
@@ -249,6 +258,8 @@ class LFAN(nn.Module):
             if m not in X:
                 raise KeyError(m)                       # x[modal] in the fusion, transformer.py:137
         mods = list(self.modality)
+        if "visual" in self.spatial:
+            self.spatial["visual"].backbone.check_sync_release()
         masks = self.test_masks or {}
         if self.training:
             self.dropout_seed += 1
@@ -296,7 +307,7 @@ class LFAN(nn.Module):
                self.regressor.weight, self.regressor.bias]
         buffers = [(self.bn[m].running_mean, self.bn[m].running_var) for m in mods]
         sink = []
-        logits = LFANHeadFunction.apply((M, H, hd, self.training, sink), buffers, fmask, *ts)
+        logits = LFANHeadFunction.apply((M, H, hd, self.training, sink, self.bn_sync), buffers, fmask, *ts)
         if self.training:
             for m in mods:
                 self.bn[m].num_batches_tracked += 1

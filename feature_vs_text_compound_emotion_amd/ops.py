@@ -697,6 +697,49 @@ def bn_finalize(partials, count, gamma, beta, running_mean=None, running_var=Non
     return scale, shift
 
 
+def _dev_f64(t, name, shape):
+    if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+        raise ValueError(f"{name}: expected a contiguous float64 tensor on the GPU, got "
+                         f"{t.dtype} {t.device} contiguous={t.is_contiguous()}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+def bn_partial_sums(partials):
+    """[tiles,2,C] partial sums -> [2,C] float64 (sum | sum of squares), reduced exactly as ``bn_finalize`` reduces them.
+    The first half of ``bn_finalize`` for synchronised statistics: all-reduce the result, then ``bn_finalize_sums``."""
+    _dev_f32(partials, "partials")
+    if partials.dim() != 3 or partials.shape[1] != 2 or partials.shape[0] == 0 or partials.shape[2] == 0:
+        raise ValueError(f"partials: expected a [tiles, 2, C] tensor, got shape {tuple(partials.shape)}")
+    tiles, _, c = partials.shape
+    lib = _lib.load()
+    nbytes = lib.cer_bn_finalize_workspace_bytes(tiles, c)
+    ws = torch.empty((nbytes // 8,), device=partials.device, dtype=torch.float64)
+    sums = torch.empty((2, c), device=partials.device, dtype=torch.float64)
+    check(lib.cer_bn_partial_sums(ptr(partials), tiles, c, ptr(sums), ptr(ws), nbytes, current_stream()), "cer_bn_partial_sums")
+    return sums
+
+
+def bn_finalize_sums(sums, count, gamma, beta, running_mean=None, running_var=None, momentum=0.1, eps=1e-5):
+    """``bn_finalize``'s second half: [2,C] float64 sums over ``count`` elements -> (scale, shift); running stats updated in
+    place when given.  The same bits as ``bn_finalize`` for the same sums."""
+    if sums.dim() != 2 or sums.shape[0] != 2:
+        raise ValueError(f"sums: expected a [2, C] tensor, got shape {tuple(sums.shape)}")
+    c = sums.shape[1]
+    _dev_f64(sums, "sums", (2, c))
+    for t, n in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _dev_f32(t, n, shape=(c,))
+    if gamma is None or beta is None or (running_mean is None) != (running_var is None):
+        raise ValueError("bn_finalize_sums: gamma and beta are required; running_mean and running_var go together")
+    if not count > 0:
+        raise ValueError(f"bn_finalize_sums: count must be positive, got {count}")
+    scale, shift = _empty((c,), gamma), _empty((c,), gamma)
+    check(_lib.load().cer_bn_finalize_sums(ptr(sums), c, float(count), ptr(gamma), ptr(beta), ptr(running_mean),
+                                           ptr(running_var), momentum, eps, ptr(scale), ptr(shift), current_stream()),
+          "cer_bn_finalize_sums")
+    return scale, shift
+
+
 def bn_apply_nhwc(y, scale, shift, alpha=None, res=None, res_stride=1, res_scale=None, res_shift=None, mask=None,
                   want_stats=False):
     """out = mask*prelu(y*scale+shift) + (res*res_scale+res_shift) on NHWC; optionally the partial
@@ -996,6 +1039,89 @@ def bn_rows_bwd(dy, x, save_mean, save_invstd, w, train=True, split_out=False, a
                                       ptr(dx), ptr(dw), ptr(db), r, c, 1 if train else 0, ptr(ws), nbytes,
                                       current_stream()), "cer_bn_rows_bwd")
     return dx, dw, db
+
+
+# ------------------------------------------------------------------ row BatchNorm split at its statistics (synchronised BN)
+def bn_rows_moments(x):
+    """(count, mean, M2) per channel of the rows of x [R,C] (dense or a column slice) as [3,C] float64 -- what a rank
+    contributes to synchronised statistics (see cer_bn_rows_merge for why these and not raw sums)."""
+    r, c, x_ld = _rows(x, "x")
+    if r == 0 or c == 0:
+        raise ValueError(f"x: expected a non-empty [R, C] tensor, got shape {tuple(x.shape)}")
+    moments = torch.empty((3, c), device=x.device, dtype=torch.float64)
+    check(_lib.load().cer_bn_rows_moments(ptr(x), x_ld, r, c, ptr(moments), current_stream()), "cer_bn_rows_moments")
+    return moments
+
+
+def bn_rows_merge(moments, running_mean=None, running_var=None, eps=1e-5, momentum=0.1):
+    """[K,3,C] moment blocks (K ranks, in rank order) -> (save_mean, save_invstd) of their union; the running buffers, when
+    given, take the union's mean and unbiased variance in place."""
+    if moments.dim() != 3 or moments.shape[1] != 3 or moments.shape[0] == 0 or moments.shape[2] == 0:
+        raise ValueError(f"moments: expected a [K, 3, C] tensor, got shape {tuple(moments.shape)}")
+    k, _, c = moments.shape
+    _dev_f64(moments, "moments", (k, 3, c))
+    _dev_f32(running_mean, "running_mean", shape=(c,))
+    _dev_f32(running_var, "running_var", shape=(c,))
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("bn_rows_merge: running_mean and running_var go together")
+    sm = torch.empty((c,), device=moments.device, dtype=torch.float32)
+    si = torch.empty((c,), device=moments.device, dtype=torch.float32)
+    check(_lib.load().cer_bn_rows_merge(ptr(moments), k, c, eps, momentum, ptr(sm), ptr(si), ptr(running_mean),
+                                        ptr(running_var), current_stream()), "cer_bn_rows_merge")
+    return sm, si
+
+
+def bn_rows_apply(x, mean, invstd, w, b, out=None):
+    """y = (x - mean) * invstd * w + b over the rows of x [R,C]; ``out`` may be a column slice of a wider buffer."""
+    r, c, x_ld = _rows(x, "x")
+    for t, n in ((mean, "mean"), (invstd, "invstd"), (w, "w"), (b, "b")):
+        if t is None:
+            raise ValueError(f"bn_rows_apply: {n} is required")
+        _dev_f32(t, n, shape=(c,))
+    if out is None:
+        out = _empty((r, c), x)
+    _, _, y_ld = _rows(out, "out")
+    _dev_f32(out, "out", contiguous=False, shape=(r, c))
+    check(_lib.load().cer_bn_rows_apply(ptr(x), x_ld, ptr(mean), ptr(invstd), ptr(w), ptr(b), ptr(out), y_ld, r, c,
+                                        current_stream()), "cer_bn_rows_apply")
+    return out
+
+
+def bn_rows_bwd_sums(dy, x, save_mean, save_invstd):
+    """[2,C] float32 = (sum dy, sum dy * x_hat) over the local rows: this rank's db and dw (the reductions of
+    ``bn_rows_bwd``), and its contribution to the global sums of a synchronised backward."""
+    r, c, dy_ld = _rows(dy, "dy")
+    _, _, x_ld = _rows(x, "x")
+    _dev_f32(x, "x", contiguous=False, shape=(r, c))
+    for t, n in ((save_mean, "save_mean"), (save_invstd, "save_invstd")):
+        if t is None:
+            raise ValueError(f"bn_rows_bwd_sums: {n} is required")
+        _dev_f32(t, n, shape=(c,))
+    sums = _empty((2, c), x)
+    ws, nbytes = _col_ws(r, c, x)
+    check(_lib.load().cer_bn_rows_bwd_sums(ptr(dy), dy_ld, ptr(x), x_ld, ptr(save_mean), ptr(save_invstd), ptr(sums), r, c,
+                                           ptr(ws), nbytes, current_stream()), "cer_bn_rows_bwd_sums")
+    return sums
+
+
+def bn_rows_bwd_apply(dy, x, save_mean, save_invstd, w, sums, count):
+    """dx of the train-mode row BatchNorm over the local rows, from the GLOBAL [2,C] sums (sum dy | sum dy * x_hat) over
+    ``count`` rows."""
+    r, c, dy_ld = _rows(dy, "dy")
+    _, _, x_ld = _rows(x, "x")
+    _dev_f32(x, "x", contiguous=False, shape=(r, c))
+    for t, n in ((save_mean, "save_mean"), (save_invstd, "save_invstd"), (w, "w"), (sums, "sums")):
+        if t is None:
+            raise ValueError(f"bn_rows_bwd_apply: {n} is required")
+    for t, n in ((save_mean, "save_mean"), (save_invstd, "save_invstd"), (w, "w")):
+        _dev_f32(t, n, shape=(c,))
+    _dev_f32(sums, "sums", shape=(2, c))
+    if not count > 0:
+        raise ValueError(f"bn_rows_bwd_apply: count must be positive, got {count}")
+    dx = _empty((r, c), x)
+    check(_lib.load().cer_bn_rows_bwd_apply(ptr(dy), dy_ld, ptr(x), x_ld, ptr(save_mean), ptr(save_invstd), ptr(w), ptr(sums),
+                                            float(count), ptr(dx), r, c, current_stream()), "cer_bn_rows_bwd_apply")
+    return dx
 
 
 def _ptr_array(tensors):

@@ -379,6 +379,10 @@ class _ReleasedHead(torch.autograd.Function):
 class IR50(nn.Module):
     """``Backbone(num_layers=50, mode='ir')`` with an h x w output head."""
 
+    # data_parallel.BatchNormSync attached by ClipDataParallel(sync_bn=...): the batch-statistics forwards then normalise
+    # with the statistics of all ranks' frames (BatchNorm2d and the head BatchNorm1d)
+    bn_sync = None
+
     def __init__(self, input_channels=3, drop_ratio=0.4, head_hw=5, embedding_dim=512):
         super().__init__()
         self.head_hw = head_hw
@@ -726,11 +730,10 @@ class IR50(nn.Module):
         s0, t0 = self._finalize(xst, y.numel() // c, self.output_layer[0])
         hfeat = ops.bn_apply_nhwc_n16(y, s0, t0, dtype=dtype, mask=head_mask)["n16"]
         k = h * w * c
-        fc, bn1 = self.output_layer[3], self.output_layer[4]
+        fc = self.output_layer[3]
         e = ops.conv2d_n16(hfeat.view(n, 1, 1, k), P["head_w"], 1, 1, bias=fc.bias.detach(),
                            split_k=self._head_split_k(n, k), out_f32=True, out_n16=False)["y"].view(n, -1)
-        e, _, _ = ops.bn_rows_fwd(e, bn1.weight.detach(), bn1.bias.detach(), bn1.running_mean, bn1.running_var, True,
-                                  bn1.eps, bn1.momentum)
+        e = self._head_bn(e)
         torch._foreach_add_([m.num_batches_tracked for m in self.modules()
                              if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d))], 1)
         return ops.l2norm_rows(e)
@@ -845,11 +848,10 @@ class IR50(nn.Module):
         s0, t0 = self._finalize(xst, y.numel() // c, self.output_layer[0])
         hfeat = ops.bn_apply_nhwc_b3(y, s0, t0, mask=head_mask)["split"]
         k = h * w * c
-        fc, bn1 = self.output_layer[3], self.output_layer[4]
+        fc = self.output_layer[3]
         e = ops.conv2d_b3(hfeat.view(n, 1, 1, k), P["head_w"], 1, 1, bias=fc.bias.detach(),
                           split_k=self._head_split_k(n, k), out_f32=True, out_split=False)["y"].view(n, -1)
-        e, _, _ = ops.bn_rows_fwd(e, bn1.weight.detach(), bn1.bias.detach(), bn1.running_mean, bn1.running_var, True,
-                                  bn1.eps, bn1.momentum)
+        e = self._head_bn(e)
         torch._foreach_add_([m.num_batches_tracked for m in self.modules()
                              if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d))], 1)
         return ops.l2norm_rows(e)
@@ -927,8 +929,26 @@ class IR50(nn.Module):
         return max(1, min(k // 32, (768 + tiles - 1) // tiles))
 
     def _finalize(self, stats, count, bn):
+        if self.bn_sync is not None:
+            return self.bn_sync.encoder_finalize(stats, count, bn)
         return ops.bn_finalize(stats, count, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
                                momentum=bn.momentum, eps=bn.eps)
+
+    def _head_bn(self, e):
+        """The head BatchNorm1d of the batch-statistics forwards (no autograd: the frozen encoder's head)."""
+        bn1 = self.output_layer[4]
+        if self.bn_sync is not None:
+            return self.bn_sync.rows_fwd(e, bn1.weight.detach(), bn1.bias.detach(), bn1.running_mean, bn1.running_var,
+                                         bn1.eps, bn1.momentum)[0]
+        return ops.bn_rows_fwd(e, bn1.weight.detach(), bn1.bias.detach(), bn1.running_mean, bn1.running_var, True,
+                               bn1.eps, bn1.momentum)[0]
+
+    def check_sync_release(self):
+        """Synchronised statistics cover the frozen encoder only: refuse released units / head before anything runs."""
+        if self.bn_sync is not None and self.training and self.bn_mode == "reference" and torch.is_grad_enabled() and \
+                any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError("sync_bn with released encoder parameters is not implemented yet (follow-up: "
+                                      "synchronised statistics in _ReleasedUnit / _ReleasedStem / _ReleasedHead)")
 
     def _forward_batch_stats(self, x, head_mask=None):
         """Reference train() semantics: every BatchNorm uses batch statistics over the N frames and
@@ -980,10 +1000,9 @@ class IR50(nn.Module):
         s0, t0 = self._finalize(xst, y.numel() // c, self.output_layer[0])
         hfeat = ops.bn_apply_nhwc(y, s0, t0, mask=head_mask)
         k = h * w * c
-        fc, bn1 = self.output_layer[3], self.output_layer[4]
+        fc = self.output_layer[3]
         e = ops.linear(hfeat.view(n, k), P["head_w"], bias=fc.bias.detach(), split_k=self._head_split_k(n, k))
-        e, _, _ = ops.bn_rows_fwd(e, bn1.weight.detach(), bn1.bias.detach(), bn1.running_mean, bn1.running_var, True,
-                                  bn1.eps, bn1.momentum)
+        e = self._head_bn(e)
         torch._foreach_add_([m.num_batches_tracked for m in self.modules()
                              if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d))], 1)
         return ops.l2norm_rows(e)
@@ -1005,6 +1024,7 @@ class IR50(nn.Module):
 
     def _forward_impl(self, x, head_mask, narrow):
         if self.training and self.bn_mode == "reference":
+            self.check_sync_release()
             if narrow is not None:
                 return self._forward_batch_stats_n16(x, narrow, head_mask)
             if self.precision == "bf16x3":

@@ -326,6 +326,29 @@ int cer_bn_rows_bwd(const float *dy, int dy_ld, const float *x, int x_ld, const 
                     const float *save_invstd, const float *w, float *dx, float *dw, float *db,
                     int R, int C, int train, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The train-mode row BatchNorm split at its statistics, so that a cross-rank exchange can sit between the local reduction
+ * and its use (synchronised BatchNorm over data-parallel ranks).  Forward:
+ *   cer_bn_rows_moments  moments [3][C] float64 = (count, mean, M2 = sum (x - mean)^2) of the rows of x (pitch x_ld);
+ *   cer_bn_rows_merge    K gathered moment blocks [K][3][C] merged in block order (Chan's pairwise update) -> save_mean,
+ *                        save_invstd (1 / sqrt(var + eps), biased var) and, when non-NULL, the running update with the
+ *                        unbiased variance of the union; every caller with the same blocks gets the same bits;
+ *   cer_bn_rows_apply    y = (x - mean) * invstd * w + b, y with pitch y_ld (a column slice of a wider buffer).
+ * Backward:
+ *   cer_bn_rows_bwd_sums   sums [2][C] float32 = (sum dy, sum dy * x_hat) over the local rows -- db and dw of this rank, the
+ *                          same reductions as cer_bn_rows_bwd; workspace as cer_col_sum;
+ *   cer_bn_rows_bwd_apply  dx = w * invstd * (dy - (sum_dy + x_hat * sum_dy_xhat) / count) with sums and count of the
+ *                          global batch, over the local rows. */
+int cer_bn_rows_moments(const float *x, int x_ld, int R, int C, double *moments, void *stream);
+int cer_bn_rows_merge(const double *moments, int K, int C, float eps, float momentum, float *save_mean, float *save_invstd,
+                      float *running_mean, float *running_var, void *stream);
+int cer_bn_rows_apply(const float *x, int x_ld, const float *mean, const float *invstd, const float *w, const float *b,
+                      float *y, int y_ld, int R, int C, void *stream);
+int cer_bn_rows_bwd_sums(const float *dy, int dy_ld, const float *x, int x_ld, const float *save_mean, const float *save_invstd,
+                         float *sums, int R, int C, void *workspace, size_t workspace_bytes, void *stream);
+int cer_bn_rows_bwd_apply(const float *dy, int dy_ld, const float *x, int x_ld, const float *save_mean,
+                          const float *save_invstd, const float *w, const float *sums, double count, float *dx, int R, int C,
+                          void *stream);
+
 /* LFAN cross-modal attention core (reference models/transformer.py:11-19,133-159): for each
  * (row, head) an M x M softmax over MODALITIES, vals = softmax(q k^T/sqrt(hd)) v + v.
  * qkv[m] [R, H*3*hd] rows laid out [head][q|k|v]; vals [R, H*M*hd]; probs [R,H,M,M] saved. */
@@ -361,6 +384,14 @@ size_t cer_bn_finalize_workspace_bytes(int tiles, int C);
 int cer_bn_finalize(const float *partials, int tiles, int C, double count, const float *gamma, const float *beta,
                     float *running_mean, float *running_var, float momentum, float eps,
                     float *scale, float *shift, void *workspace, size_t workspace_bytes, void *stream);
+/* cer_bn_finalize in two steps, for statistics synchronised across data-parallel ranks (the all-reduce of `sums` goes
+ * between them): cer_bn_partial_sums reduces the partials exactly as cer_bn_finalize does into sums [2][C] float64
+ * (sum | sum of squares; workspace as cer_bn_finalize), cer_bn_finalize_sums applies cer_bn_finalize's formula to sums over
+ * `count` elements.  With one rank the pair gives cer_bn_finalize's bits. */
+int cer_bn_partial_sums(const float *partials, int tiles, int C, double *sums, void *workspace, size_t workspace_bytes,
+                        void *stream);
+int cer_bn_finalize_sums(const double *sums, int C, double count, const float *gamma, const float *beta, float *running_mean,
+                         float *running_var, float momentum, float eps, float *scale, float *shift, void *stream);
 int cer_bn_apply_stats_tiles(int P);
 int cer_bn_apply_nhwc(const float *y, const float *scale, const float *shift, const float *alpha,
                       const float *res, const float *res_scale, const float *res_shift, const float *mask,
