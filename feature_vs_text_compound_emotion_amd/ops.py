@@ -27,6 +27,13 @@ def _dev_f32(t, name, contiguous=True, shape=None):
         raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
 
 
+def _dev_mask(mask, y):
+    """An optional elementwise mask of the encoder passes: float32 on the GPU, contiguous, one value per element of ``y``."""
+    _dev_f32(mask, "mask")
+    if mask is not None and mask.numel() != y.numel():
+        raise ValueError(f"mask: expected {y.numel()} elements (the shape {tuple(y.shape)}), got {tuple(mask.shape)}")
+
+
 def _dense2d(t, name):
     """A contiguous [R,C] float32 GPU tensor (the kernel hard-codes pitch C).  Returns (rows, cols)."""
     _dev_f32(t, name)
@@ -184,8 +191,8 @@ def split_bf16(x, scale=None, shift=None):
     """fp32 tensor -> Split (round-to-nearest-even on both parts), optionally after the per-channel
     affine x*scale[c]+shift[c] over the last (channel) axis."""
     _dev_f32(x, "x")
-    _dev_f32(scale, "scale")
-    _dev_f32(shift, "shift")
+    _dev_f32(scale, "scale", shape=x.shape[-1:])
+    _dev_f32(shift, "shift", shape=x.shape[-1:])
     out = Split.empty(x.shape, x.device)
     c = x.shape[-1] if scale is not None else 0
     check(_lib.load().cer_split_bf16(ptr(x), ptr(scale), ptr(shift), c, ptr(out.hi), ptr(out.lo), x.numel(),
@@ -392,8 +399,8 @@ def _dev_n16(t, name, dtype=None):
 def to_n16(x, dtype, scale=None, shift=None):
     """fp32 tensor -> narrow tensor (round-to-nearest-even), optionally after x*scale[c]+shift[c] over the last axis."""
     _dev_f32(x, "x")
-    _dev_f32(scale, "scale")
-    _dev_f32(shift, "shift")
+    _dev_f32(scale, "scale", shape=x.shape[-1:])
+    _dev_f32(shift, "shift", shape=x.shape[-1:])
     out = torch.empty(x.shape, device=x.device, dtype=dtype)
     c = x.shape[-1] if scale is not None else 0
     check(_lib.load().cer_to_n16(ptr(x), ptr(scale), ptr(shift), c, ptr(out), x.numel(), storage_of(dtype), current_stream()),
@@ -490,10 +497,10 @@ def bn_apply_nhwc_n16(y, scale, shift, dtype=None, alpha=None, res=None, res_str
                       want_stats=False, out_f32=False, out_n16=True):
     """``bn_apply_nhwc`` for the narrow encoder: ``y`` (the conv result) and ``res`` are fp32 or narrow tensors; the result
     comes back narrow ('n16', what the next conv reads) and/or fp32 ('y'); 'stats' as requested."""
-    for t, nme in ((scale, "scale"), (shift, "shift"), (alpha, "alpha"), (res_scale, "res_scale"), (res_shift, "res_shift"),
-                   (mask, "mask")):
-        _dev_f32(t, nme)
     n, ho, wo, c = y.shape
+    for t, nme in ((scale, "scale"), (shift, "shift"), (alpha, "alpha"), (res_scale, "res_scale"), (res_shift, "res_shift")):
+        _dev_f32(t, nme, shape=(c,))
+    _dev_mask(mask, y)
     lib = _lib.load()
     if dtype is None:
         dtype = y.dtype if y.dtype != torch.float32 else (res.dtype if res is not None else None)
@@ -624,7 +631,7 @@ def conv2d_wgrad(dz, x, kh, kw, stride=1, pad=(0, 0), b3=False):
 
 def prelu_fwd(x, alpha):
     _dev_f32(x, "x")
-    _dev_f32(alpha, "alpha")
+    _dev_f32(alpha, "alpha", shape=x.shape[-1:])
     y = torch.empty_like(x)
     check(_lib.load().cer_prelu_fwd(ptr(x), ptr(alpha), ptr(y), x.numel() // x.shape[-1], x.shape[-1], current_stream()),
           "cer_prelu_fwd")
@@ -634,7 +641,7 @@ def prelu_fwd(x, alpha):
 def prelu_split(x, alpha):
     """prelu(x) as a Split tensor in one pass (the conv input a released unit rebuilds from its raw conv result)."""
     _dev_f32(x, "x")
-    _dev_f32(alpha, "alpha")
+    _dev_f32(alpha, "alpha", shape=x.shape[-1:])
     out = Split.empty(x.shape, x.device)
     c = x.shape[-1]
     check(_lib.load().cer_prelu_split(ptr(x), ptr(alpha), ptr(out.hi), ptr(out.lo), x.numel() // c, c, current_stream()),
@@ -645,8 +652,9 @@ def prelu_split(x, alpha):
 def prelu_bwd(dy, x, alpha, out=None, split_out=False):
     """-> (dx, dalpha): torch's PReLU backward for channels-last tensors.  ``split_out``: dx comes back as a Split tensor (no fp32
     copy is written); ``out``: write dx into this fp32 tensor / Split (a slice of a larger one: chunked calls)."""
-    for t, nme in ((dy, "dy"), (x, "x"), (alpha, "alpha")):
-        _dev_f32(t, nme)
+    _dev_f32(x, "x")
+    _dev_f32(dy, "dy", shape=x.shape)
+    _dev_f32(alpha, "alpha", shape=x.shape[-1:])
     terms = torch.empty_like(x)
     c = x.shape[-1]
     if split_out:
@@ -744,10 +752,12 @@ def bn_apply_nhwc(y, scale, shift, alpha=None, res=None, res_stride=1, res_scale
                   want_stats=False):
     """out = mask*prelu(y*scale+shift) + (res*res_scale+res_shift) on NHWC; optionally the partial
     statistics of ``out`` for the next BatchNorm."""
-    for t, nme in ((y, "y"), (scale, "scale"), (shift, "shift"), (alpha, "alpha"), (res, "res"),
-                   (res_scale, "res_scale"), (res_shift, "res_shift"), (mask, "mask")):
+    for t, nme in ((y, "y"), (res, "res")):
         _dev_f32(t, nme)
     n, ho, wo, c = y.shape
+    for t, nme in ((scale, "scale"), (shift, "shift"), (alpha, "alpha"), (res_scale, "res_scale"), (res_shift, "res_shift")):
+        _dev_f32(t, nme, shape=(c,))
+    _dev_mask(mask, y)
     lib = _lib.load()
     out = torch.empty_like(y)
     stats = _empty((lib.cer_bn_apply_stats_tiles(n * ho * wo), 2, c), y) if want_stats else None
@@ -762,10 +772,11 @@ def bn_apply_nhwc_b3(y, scale, shift, alpha=None, res=None, res_stride=1, res_sc
                      want_stats=False, out_f32=False, out_split=True):
     """``bn_apply_nhwc`` for the bf16x3 encoder: ``res`` may be a Split tensor, the result comes back as a Split
     (what the next conv reads) and/or fp32.  Returns a dict with 'split', 'y', 'stats' as requested."""
-    for t, nme in ((y, "y"), (scale, "scale"), (shift, "shift"), (alpha, "alpha"), (res_scale, "res_scale"),
-                   (res_shift, "res_shift"), (mask, "mask")):
-        _dev_f32(t, nme)
+    _dev_f32(y, "y")
     n, ho, wo, c = y.shape
+    for t, nme in ((scale, "scale"), (shift, "shift"), (alpha, "alpha"), (res_scale, "res_scale"), (res_shift, "res_shift")):
+        _dev_f32(t, nme, shape=(c,))
+    _dev_mask(mask, y)
     lib = _lib.load()
     r_f32 = r_hi = r_lo = None
     hr = wr = 0

@@ -655,3 +655,43 @@ def test_wrapper_refuses_before_launch(case):
     with pytest.raises(ValueError):
         REFUSALS[case](_ops(), t)
     torch.cuda.synchronize()
+
+
+# The encoder-side wrappers read their per-channel vectors (PReLU slopes, BatchNorm scale / shift, the residual's affine)
+# at channel index c of the tensor's last axis: a vector shorter than C would be read past its end.
+class _E:
+    def __init__(self):
+        cu = dict(device="cuda")
+        self.c = c = 64
+        self.x = torch.randn(2, 4, 4, c, **cu)
+        self.vec, self.short = torch.ones(c, **cu), torch.ones(c // 2, **cu)
+
+
+ENCODER_REFUSALS = {
+    "prelu_fwd alpha short": lambda o, t: o.prelu_fwd(t.x, t.short),
+    "prelu_split alpha short": lambda o, t: o.prelu_split(t.x, t.short),
+    "prelu_bwd alpha short": lambda o, t: o.prelu_bwd(t.x, t.x, t.short),
+    "prelu_bwd dy fewer rows": lambda o, t: o.prelu_bwd(t.x[:1], t.x, t.vec),
+    "split_bf16 scale short": lambda o, t: o.split_bf16(t.x, t.short, t.vec),
+    "split_bf16 shift short": lambda o, t: o.split_bf16(t.x, t.vec, t.short),
+    "to_n16 scale short": lambda o, t: o.to_n16(t.x, torch.float16, t.short, t.vec),
+    "bn_apply_nhwc scale short": lambda o, t: o.bn_apply_nhwc(t.x, t.short, t.vec),
+    "bn_apply_nhwc alpha short": lambda o, t: o.bn_apply_nhwc(t.x, t.vec, t.vec, alpha=t.short),
+    "bn_apply_nhwc res_shift short": lambda o, t: o.bn_apply_nhwc(t.x, t.vec, t.vec, res=t.x, res_scale=t.vec,
+                                                                  res_shift=t.short),
+    "bn_apply_nhwc mask short": lambda o, t: o.bn_apply_nhwc(t.x, t.vec, t.vec, mask=t.x[:1].contiguous()),
+    "bn_apply_nhwc_b3 shift short": lambda o, t: o.bn_apply_nhwc_b3(t.x, t.vec, t.short),
+    "bn_apply_nhwc_b3 res_scale short": lambda o, t: o.bn_apply_nhwc_b3(t.x, t.vec, t.vec, res=t.x, res_scale=t.short,
+                                                                        res_shift=t.vec),
+    "bn_apply_nhwc_n16 scale short": lambda o, t: o.bn_apply_nhwc_n16(t.x, t.short, t.vec, dtype=torch.float16),
+    "bn_apply_nhwc_n16 alpha short": lambda o, t: o.bn_apply_nhwc_n16(t.x, t.vec, t.vec, dtype=torch.float16, alpha=t.short),
+}
+
+
+@pytest.mark.parametrize("case", list(ENCODER_REFUSALS))
+def test_encoder_wrapper_refuses_before_launch(case):
+    t = _E()
+    torch.cuda.synchronize()
+    with pytest.raises(ValueError):
+        ENCODER_REFUSALS[case](_ops(), t)
+    torch.cuda.synchronize()
