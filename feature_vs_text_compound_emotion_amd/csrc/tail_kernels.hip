@@ -5,6 +5,7 @@
 // These ops move a few MB per step; the design goal is one pass over the data
 // per kernel, 64-wide wave reductions (no 32-lane idioms) and deterministic
 // results (no float atomics: column sums use a fixed two-level tree).
+#include <limits.h>
 #include <math.h>
 
 #include "cer_internal.h"
@@ -354,6 +355,97 @@ __global__ void bn_rows_moments_kernel(const float *__restrict__ x, int x_ld, in
         moments[c] = (double)R;
         moments[C + c] = mu;
         moments[2 * C + c] = t;
+    }
+}
+
+// Large-R moments (the released encoder units: 0.8 M .. 51 M rows of 64 .. 512 channels), ONE read of x, many blocks.
+// Slab stage: grid.x = channel chunks of 4 * CQ, grid.y = row slabs; block = CQ channel quads x (256 / CQ) row lanes, four
+// rows in flight per lane (16-byte loads).  Each slab sums d = x - k and d^2 about its OWN shift row k = x[first row of the
+// slab] in fp32 -- a sample of the column, a few sigma from its mean whatever the offset, so neither sum cancels -- and
+// writes the two partial rows to p1 / p2 [slab][C].  CQ = 16 for C <= 64 keeps every lane busy on the 64-channel tensors.
+template <int CQ>
+__global__ __launch_bounds__(256) void bn_rows_moments_slab_kernel(const float *__restrict__ x, float *__restrict__ p1,
+                                                                    float *__restrict__ p2, int R, int C, int rows_per_slab) {
+    constexpr int RL = 256 / CQ;
+    __shared__ float red[RL][CQ][8];
+    const int cx = threadIdx.x % CQ, ry = threadIdx.x / CQ;
+    const int c = (blockIdx.x * CQ + cx) * 4;
+    const int r0 = blockIdx.y * rows_per_slab, r1 = min(R, r0 + rows_per_slab);
+    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c < C) {
+        const float4 k = *reinterpret_cast<const float4 *>(x + (size_t)r0 * C + c);
+        for (int r = r0 + ry; r < r1; r += 4 * RL) {
+            float4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int rr = r + RL * u;
+                v[u] = rr < r1 ? *reinterpret_cast<const float4 *>(x + (size_t)rr * C + c) : k;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float d[4] = {v[u].x - k.x, v[u].y - k.y, v[u].z - k.z, v[u].w - k.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    s1[e] += d[e];
+                    s2[e] += d[e] * d[e];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        red[ry][cx][e] = s1[e];
+        red[ry][cx][4 + e] = s2[e];
+    }
+    __syncthreads();
+    if (ry == 0 && c < C) {
+        float t[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < RL; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) t[e] += red[i][cx][e];
+        *reinterpret_cast<float4 *>(p1 + (size_t)blockIdx.y * C + c) = make_float4(t[0], t[1], t[2], t[3]);
+        *reinterpret_cast<float4 *>(p2 + (size_t)blockIdx.y * C + c) = make_float4(t[4], t[5], t[6], t[7]);
+    }
+}
+
+// Finishing stage: the slab partials -> moments [3][C] in float64.  A slab j of n_j rows with shift k_j contributes, about the
+// common reference k_0 (slab 0's shift) and with d_j = k_j - k_0,
+//   sum (x - k_0) = s1_j + n_j d_j,      sum (x - k_0)^2 = s2_j + 2 d_j s1_j + n_j d_j^2,
+// all in float64; then mean = k_0 + S1 / R and M2 = S2 - S1^2 / R (k_0 is a sample of the column: S1 / R is a few sigma at
+// most, and the subtraction costs float64 a digit or two, not fp32 all of its).  Block = 32 channels x 8 lanes, lane ry takes
+// slabs ry, ry + 8, ..., then the 8 lane sums are added in lane order: a fixed order, no atomics, deterministic.
+__global__ void bn_rows_moments_finish_kernel(const float *__restrict__ x, const float *__restrict__ p1, const float *__restrict__ p2,
+                                              int R, int C, int rows_per_slab, int slabs, double *__restrict__ moments) {
+    __shared__ double red[2][8][33];
+    const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + cx;
+    double a1 = 0.0, a2 = 0.0, k0 = 0.0;
+    if (c < C) {
+        k0 = (double)x[c];
+        for (int j = ry; j < slabs; j += 8) {
+            const size_t r0 = (size_t)j * rows_per_slab;
+            const size_t left = (size_t)R - r0;
+            const double n = (double)(left < (size_t)rows_per_slab ? left : (size_t)rows_per_slab);
+            const double d = (double)x[r0 * C + c] - k0;
+            const double s1 = (double)p1[(size_t)j * C + c], s2 = (double)p2[(size_t)j * C + c];
+            a1 += s1 + n * d;
+            a2 += s2 + 2.0 * d * s1 + n * d * d;
+        }
+    }
+    red[0][ry][cx] = a1;
+    red[1][ry][cx] = a2;
+    __syncthreads();
+    if (ry == 0 && c < C) {
+        double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            t1 += red[0][i][cx];
+            t2 += red[1][i][cx];
+        }
+        const double m2 = t2 - t1 * (t1 / (double)R);
+        moments[c] = (double)R;
+        moments[C + c] = k0 + t1 / (double)R;
+        moments[2 * C + c] = m2 > 0.0 ? m2 : 0.0;
     }
 }
 
@@ -922,6 +1014,35 @@ extern "C" int cer_bn_rows_bwd(const float *dy, int dy_ld, const float *x, int x
 extern "C" int cer_bn_rows_moments(const float *x, int x_ld, int R, int C, double *moments, void *stream) {
     if (!x || !moments || R <= 0 || C <= 0 || x_ld < C) return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_moments: bad argument");
     CER_LAUNCH(bn_rows_moments_kernel, dim3((C + 31) / 32), dim3(256), 0, ST, x, x_ld, R, C, moments);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+// slabs of at least 256 rows, at most 1024 of them (the slab count the column sums use; the finishing kernel walks them)
+static int moments_large_rows_per_slab(int R) {
+    return (R + 255) / 256 <= 1024 ? 256 : ((R + 1023) / 1024 + 63) / 64 * 64;
+}
+
+extern "C" size_t cer_bn_rows_moments_large_workspace_bytes(int R, int C) {
+    if (R <= 0 || C <= 0) return 0;
+    const int rps = moments_large_rows_per_slab(R);
+    return (size_t)2 * ((R + rps - 1) / rps) * C * sizeof(float);
+}
+
+extern "C" int cer_bn_rows_moments_large(const float *x, int R, int C, double *moments, void *workspace, size_t workspace_bytes,
+                                         void *stream) {
+    if (!x || !moments || R <= 0 || R > INT_MAX - 1024 || C <= 0 || (C & 3) || !aligned16(x) || !aligned16(workspace))
+        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_moments_large: bad argument (dense rows, C % 4 == 0, 16-byte aligned)");
+    const int rps = moments_large_rows_per_slab(R), slabs = (R + rps - 1) / rps;
+    if (!workspace || workspace_bytes < cer_bn_rows_moments_large_workspace_bytes(R, C))
+        return cer_set_error(CER_ERR_WORKSPACE, "bn_rows_moments_large: workspace too small");
+    float *p1 = (float *)workspace, *p2 = p1 + (size_t)slabs * C;
+    if (C <= 64)
+        CER_LAUNCH(bn_rows_moments_slab_kernel<16>, dim3((C + 63) / 64, slabs), dim3(256), 0, ST, x, p1, p2, R, C, rps);
+    else
+        CER_LAUNCH(bn_rows_moments_slab_kernel<32>, dim3((C + 127) / 128, slabs), dim3(256), 0, ST, x, p1, p2, R, C, rps);
+    CER_LAUNCH(bn_rows_moments_finish_kernel, dim3((C + 31) / 32), dim3(256), 0, ST, x, (const float *)p1, (const float *)p2, R, C,
+               rps, slabs, moments);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }

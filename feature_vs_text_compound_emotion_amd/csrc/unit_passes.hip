@@ -143,3 +143,33 @@ extern "C" int cer_bn_rows_bwd_add(const float *dy, const float *x, const float 
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }
+
+// The apply passes of cer_bn_rows_bwd_split / cer_bn_rows_bwd_add from GIVEN sums [2][C] (sum dy | sum dy * x_hat) over
+// ``count`` rows -- a synchronised BatchNorm's backward, where the sums are all-reduced over the ranks and count is the global
+// batch's rows.  The same kernels with the same 1.0f / (float)count: with the local sums and count == R they write the bits of
+// the unsynchronised entry points.
+extern "C" int cer_bn_rows_bwd_apply_split(const float *dy, const float *x, const float *save_mean, const float *save_invstd,
+                                           const float *w, const float *sums, double count, uint16_t *dx_hi, uint16_t *dx_lo, int R,
+                                           int C, void *stream) {
+    if (!dy || !x || !save_mean || !save_invstd || !w || !sums || !dx_hi || !dx_lo || R <= 0 || C <= 0 || (C & 3) || !(count > 0))
+        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd_apply_split: bad argument (dense rows, C % 4 == 0, count > 0)");
+    const size_t n4 = (size_t)R * (C / 4);
+    CER_LAUNCH(bn_rows_bwd_split_kernel, dim3(cer_blocks(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4 *)dy,
+               (const float4 *)x, save_mean, save_invstd, w, sums, sums + C, (ushort4 *)dx_hi, (ushort4 *)dx_lo, n4, C / 4,
+               1.0f / (float)count);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_bn_rows_bwd_apply_add(const float *dy, const float *x, const float *save_mean, const float *save_invstd,
+                                         const float *w, const float *sums, double count, const float *add, float *dx, int R, int C,
+                                         void *stream) {
+    if (!dy || !x || !save_mean || !save_invstd || !w || !sums || !dx || R <= 0 || C <= 0 || (C & 3) || !(count > 0))
+        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd_apply_add: bad argument (dense rows, C % 4 == 0, count > 0)");
+    const size_t n4 = (size_t)R * (C / 4);
+    CER_LAUNCH(bn_rows_bwd_add_kernel, dim3(cer_blocks(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4 *)dy,
+               (const float4 *)x, save_mean, save_invstd, w, sums, sums + C, (const float4 *)add, (float4 *)dx, n4, C / 4,
+               1.0f / (float)count);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}

@@ -55,7 +55,9 @@ class BatchNormSync:
     * row BatchNorm1d forward: float64 (count, mean, M2) per rank, all-gathered and merged in rank order (identical bits on
       every rank; see cer_bn_rows_merge);
     * row BatchNorm1d backward: the float32 (sum dy, sum dy * x_hat) all-reduced, dx from the global sums over
-      ``world x`` the local rows; dw and db stay the rank's own (the gradient all-reduce averages them).
+      ``world x`` the local rows; dw and db stay the rank's own (the gradient all-reduce averages them);
+    * released encoder units / stem / head (``sync_released``): the same exchanges over 0.8 M .. 51 M rows -- the moments of
+      ``bn_rows_moments_large`` (one read of x), and the backward's fused split / addend apply passes from the global sums.
 
     The element counts assume equal shards (what ``ClipDataParallel.shard`` gives when the global batch divides by the
     world size) -- the same assumption under which the mean of the ranks' gradients is the full-batch gradient."""
@@ -86,13 +88,41 @@ class BatchNormSync:
         sm, si = ops.bn_rows_merge(gathered.view(self.world, 3, -1), running_mean, running_var, eps, momentum)
         return ops.bn_rows_apply(x, sm, si, w, b, out=out), sm, si
 
-    def rows_bwd(self, dy, x, save_mean, save_invstd, w):
-        """``ops.bn_rows_bwd(train=True)`` over the global batch: (dx, dw, db), dw / db of the local rows."""
+    def rows_bwd(self, dy, x, save_mean, save_invstd, w, split_out=False, add=None):
+        """``ops.bn_rows_bwd(train=True)`` over the global batch: (dx, dw, db), dw / db of the local rows.  ``split_out`` / ``add``
+        (the released encoder units' fused passes, dense rows, C % 4 == 0): dx as a Split tensor, or with ``add`` summed in,
+        like ``ops.bn_rows_bwd(split_out=..., add=...)``."""
         from . import ops
         local = ops.bn_rows_bwd_sums(dy, x, save_mean, save_invstd)
         total = self._all_reduce(local.clone())
-        dx = ops.bn_rows_bwd_apply(dy, x, save_mean, save_invstd, w, total, dy.shape[0] * self.world)
+        count = dy.shape[0] * self.world
+        if split_out or add is not None:
+            dx = ops.bn_rows_bwd_apply_fused(dy, x, save_mean, save_invstd, w, total, count, split_out=split_out, add=add)
+        else:
+            dx = ops.bn_rows_bwd_apply(dy, x, save_mean, save_invstd, w, total, count)
         return dx, local[1], local[0]
+
+    # ---- released encoder units (IR50 with ``sync_released``): row counts of frames x pixels, 0.8 M .. 51 M rows
+    def rows_stats_large(self, x, running_mean, running_var, eps, momentum):
+        """``ops.bn_rows_stats`` over the global batch for dense rows x [R,C] of any size: (save_mean, save_invstd), the same
+        bits on every rank, running buffers updated with the global statistics."""
+        from . import ops
+        local = ops.bn_rows_moments_large(x)
+        gathered = torch.empty((self.world * 3, local.shape[1]), device=local.device, dtype=local.dtype)
+        dist.all_gather_into_tensor(gathered, local, group=self.group)
+        return ops.bn_rows_merge(gathered.view(self.world, 3, -1), running_mean, running_var, eps, momentum)
+
+    def rows_fwd_large(self, x, w, b, running_mean, running_var, eps, momentum):
+        """``ops.bn_rows_fwd(train=True)`` over the global batch for large dense rows: (y, save_mean, save_invstd)."""
+        from . import ops
+        sm, si = self.rows_stats_large(x, running_mean, running_var, eps, momentum)
+        return ops.bn_rows_apply(x, sm, si, w, b), sm, si
+
+    def agree_min(self, flag, device):
+        """The minimum of an integer flag over the ranks (e.g. "this rank's memory fits the plan"), on the sync group."""
+        t = torch.tensor([int(flag)], device=device, dtype=torch.int32)
+        dist.all_reduce(t, op=dist.ReduceOp.MIN, group=self.group)
+        return int(t.item())
 
 
 def _bn_sync_owners(model):
@@ -103,16 +133,23 @@ def _bn_sync_owners(model):
 class ClipDataParallel:
     """Gradient bucket + collectives for a model whose trainable part is small."""
 
-    def __init__(self, model, world_size=None, broadcast=True, overlap=False, bucket_mb=25.0, sync_bn=False):
+    def __init__(self, model, world_size=None, broadcast=True, overlap=False, bucket_mb=25.0, sync_bn=False,
+                 sync_released=False):
         """``sync_bn``: train-mode BatchNorms of the encoder and the tail normalise with the statistics of the global batch
         (``BatchNormSync``; needs an initialised process group).  ``"force"`` runs the collectives with one rank too, like
         ``overlap="force"``.  Off by default: each rank's BatchNorms see its own shard.
+
+        ``sync_released`` (needs ``sync_bn``): the RELEASED parts of the IR-50 encoder (the reference's gradual release:
+        output layer, stage 4, half of stage 3 -- or the whole encoder) normalise with the global statistics too, forward and
+        backward.  Off by default: with ``sync_bn`` alone a released encoder parameter is refused (NotImplementedError).
 
         ``overlap``: cut the flat bucket into slices of ``bucket_mb`` (in parameter order) and start the all-reduce of a
         slice from an autograd hook as soon as the last gradient of the slice has been accumulated -- backward produces
         the gradients from the top of the model down, so with released encoder units (28-43 M parameters, 112-172 MB) the
         exchange of the tail's and the upper units' gradients runs under the backward of the units below.  Needs ONE
         ``backward()`` per ``zero_grad()`` (the reference's training loop); off by default."""
+        if sync_released and not sync_bn:
+            raise ValueError("sync_released=True needs sync_bn (synchronised statistics of the released encoder units)")
         self.model = model
         self.world = world_size if world_size is not None else (dist.get_world_size() if dist.is_initialized() else 1)
         self.params = [p for p in model.parameters() if p.requires_grad]
@@ -145,6 +182,8 @@ class ClipDataParallel:
             self.bn_sync = BatchNormSync(dist.new_group(), dist.get_world_size(), dist.get_rank())
             for m in _bn_sync_owners(model):
                 m.bn_sync = self.bn_sync
+                if hasattr(type(m), "sync_released"):    # (IR50) a plain flag: deep copies of the model keep it
+                    m.sync_released = bool(sync_released)
 
     # ------------------------------------------------------------------ bucketed, overlapped exchange
     def _build_buckets(self, bucket_mb):

@@ -1135,6 +1135,60 @@ def bn_rows_bwd_apply(dy, x, save_mean, save_invstd, w, sums, count):
     return dx
 
 
+def _dense_rows4(t, name):
+    """A contiguous [R,C] float32 GPU tensor with C % 4 == 0 and a 16-byte-aligned base (the float4 row passes).  Returns (R, C)."""
+    r, c = _dense2d(t, name)
+    if r == 0 or c == 0 or c % 4 or t.data_ptr() % 16:
+        raise ValueError(f"{name}: expected non-empty dense rows with C % 4 == 0 and a 16-byte-aligned base, got shape "
+                         f"{tuple(t.shape)}")
+    return r, c
+
+
+def bn_rows_moments_large(x):
+    """``bn_rows_moments`` for the released encoder units' large row counts: [3,C] float64 (count, mean, M2) of the dense rows
+    of x [R,C] (C % 4 == 0) from one read of x by many row slabs, merged in float64 in a fixed order."""
+    r, c = _dense_rows4(x, "x")
+    lib = _lib.load()
+    nbytes = lib.cer_bn_rows_moments_large_workspace_bytes(r, c)
+    ws = _empty((nbytes // 4,), x)
+    moments = torch.empty((3, c), device=x.device, dtype=torch.float64)
+    check(lib.cer_bn_rows_moments_large(ptr(x), r, c, ptr(moments), ptr(ws), nbytes, current_stream()),
+          "cer_bn_rows_moments_large")
+    return moments
+
+
+def bn_rows_bwd_apply_fused(dy, x, save_mean, save_invstd, w, sums, count, split_out=False, add=None):
+    """The apply pass of ``bn_rows_bwd(split_out=True)`` / ``bn_rows_bwd(add=...)`` from GIVEN [2,C] sums (sum dy | sum dy *
+    x_hat) over ``count`` rows: dx as a Split tensor, or fp32 with ``add`` (optional) summed in.  Dense rows, C % 4 == 0.
+    With ``bn_rows_bwd_sums`` of the same rows and ``count == R`` it returns ``bn_rows_bwd``'s dx bit for bit."""
+    r, c = _dense_rows4(dy, "dy")
+    _dense_rows4(x, "x")
+    _dev_f32(x, "x", shape=(r, c))
+    for t, n in ((save_mean, "save_mean"), (save_invstd, "save_invstd"), (w, "w"), (sums, "sums")):
+        if t is None:
+            raise ValueError(f"bn_rows_bwd_apply_fused: {n} is required")
+    for t, n in ((save_mean, "save_mean"), (save_invstd, "save_invstd"), (w, "w")):
+        _dev_f32(t, n, shape=(c,))
+    _dev_f32(sums, "sums", shape=(2, c))
+    if add is not None:
+        if split_out:
+            raise ValueError("bn_rows_bwd_apply_fused: add needs the fp32 result (split_out=False)")
+        _dense_rows4(add, "add")
+        _dev_f32(add, "add", shape=(r, c))
+    if not count > 0:
+        raise ValueError(f"bn_rows_bwd_apply_fused: count must be positive, got {count}")
+    lib = _lib.load()
+    if split_out:
+        dx = Split.empty((r, c), x.device)
+        check(lib.cer_bn_rows_bwd_apply_split(ptr(dy), ptr(x), ptr(save_mean), ptr(save_invstd), ptr(w), ptr(sums), float(count),
+                                              ptr(dx.hi), ptr(dx.lo), r, c, current_stream()), "cer_bn_rows_bwd_apply_split")
+        return dx
+    dx = _empty((r, c), x)
+    check(lib.cer_bn_rows_bwd_apply_add(ptr(dy), ptr(x), ptr(save_mean), ptr(save_invstd), ptr(w), ptr(sums), float(count), ptr(add),
+                                        ptr(dx), r, c, current_stream()), "cer_bn_rows_bwd_apply_add")
+    return dx
+
+
 def _ptr_array(tensors):
     arr = (ctypes.c_void_p * len(tensors))()
     for i, t in enumerate(tensors):

@@ -136,6 +136,28 @@ def _bn_affine_from_saved(save_mean, save_invstd, gamma, beta):
     return scale.contiguous(), (beta - save_mean * scale).contiguous()
 
 
+# The released parts' row BatchNorms.  ``sync``: the model's BatchNormSync when ``IR50.sync_released`` is on (statistics and
+# backward sums of the global batch, data_parallel.py), else None (the rank's own rows).
+def _rows_stats(sync, x, bn):
+    if sync is not None:
+        return sync.rows_stats_large(x, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
+    return ops.bn_rows_stats(x, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
+
+
+def _rows_fwd(sync, x, w, b, bn, large=True):
+    if sync is None:
+        return ops.bn_rows_fwd(x, w, b, bn.running_mean, bn.running_var, True, bn.eps, bn.momentum)
+    if large:
+        return sync.rows_fwd_large(x, w, b, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
+    return sync.rows_fwd(x, w, b, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
+
+
+def _rows_bwd(sync, dy, x, save_mean, save_invstd, w, split_out=False, add=None):
+    if sync is not None:
+        return sync.rows_bwd(dy, x, save_mean, save_invstd, w, split_out=split_out, add=add)
+    return ops.bn_rows_bwd(dy, x, save_mean, save_invstd, w, split_out=split_out, add=add)
+
+
 class _ReleasedUnit(torch.autograd.Function):
     """One bottleneck_IR unit (arcface_model.py:44-60) in train mode WITH its backward, for the body groups of the
     reference's gradual release (base/parameter_control.py:55-103: stage 4, then half of stage 3) and, as an extension, the
@@ -159,13 +181,13 @@ class _ReleasedUnit(torch.autograd.Function):
     -- an explicit trade, held to its own bar in tests/test_head_release_gpu.py."""
 
     @staticmethod
-    def forward(ctx, x, u, prec, memory, g1, b1, w1, a1, w2, g2, b2, ws, gs, bs):
+    def forward(ctx, x, u, prec, memory, g1, b1, w1, a1, w2, g2, b2, ws, gs, bs, sync=None):
         n, h, w, cin = x.shape
         bn1, bn2, s = u.res_layer[0], u.res_layer[4], u.stride
         b3 = prec == "bf16x3"
         # BatchNorm 1: statistics pass only; the normalisation is ONE affine (+ split) pass from them -- the same arithmetic the
         # backward uses to rebuild it, so the "recompute" memory plan reproduces z1 / z2 bit for bit
-        sm1, si1 = ops.bn_rows_stats(x.view(-1, cin), bn1.running_mean, bn1.running_var, bn1.eps, bn1.momentum)
+        sm1, si1 = _rows_stats(sync, x.view(-1, cin), bn1)
         sc1, sh1 = _bn_affine_from_saved(sm1, si1, g1.detach(), b1.detach())
         xb_k = ops.split_bf16(x, sc1, sh1) if b3 else torch.addcmul(sh1, x, sc1)
         if b3 and memory != "raw":   # z1 is not kept: PReLU and the split happen in the conv's epilogue (no z1 / t1 round trips)
@@ -185,13 +207,13 @@ class _ReleasedUnit(torch.autograd.Function):
         del t1_k
         _, ho, wo, depth = z2.shape
         # BatchNorm 2 (+ the shortcut's BatchNorm) and the residual add in ONE pass over z2: statistics, then scale / shift
-        sm2, si2 = ops.bn_rows_stats(z2.view(-1, depth), bn2.running_mean, bn2.running_var, bn2.eps, bn2.momentum)
+        sm2, si2 = _rows_stats(sync, z2.view(-1, depth), bn2)
         sc2, sh2 = _bn_affine_from_saved(sm2, si2, g2.detach(), b2.detach())
         zs = sms = sis = None
         if ws is not None:
             bns = u.shortcut_layer[1]
             zs = _conv_prec(x, ops.pack_conv_weight(ws.detach().contiguous()), 1, 1, s, (0, 0), prec)
-            sms, sis = ops.bn_rows_stats(zs.view(-1, depth), bns.running_mean, bns.running_var, bns.eps, bns.momentum)
+            sms, sis = _rows_stats(sync, zs.view(-1, depth), bns)
             scs, shs = _bn_affine_from_saved(sms, sis, gs.detach(), bs.detach())
             out = ops.bn_apply_nhwc(z2, sc2, sh2, res=zs, res_scale=scs, res_shift=shs)
         else:
@@ -212,13 +234,14 @@ class _ReleasedUnit(torch.autograd.Function):
                               gs.detach() if gs is not None else None)
         ctx.stride = s
         ctx.prec = prec
+        ctx.sync = sync
         ctx.out_shape = tuple(out.shape)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, z1, z2, sm1, si1, sm2, si2, zs, sms, sis, g1, b1, w1, a1, w2, g2, ws, gs = ctx.saved_tensors
-        s, prec = ctx.stride, ctx.prec
+        s, prec, sync = ctx.stride, ctx.prec, ctx.sync
         # fp16 storage has no range for UN-scaled gradients: a mean cross-entropy gradient divided over B*L rows and H*W
         # pixels sits at or below fp16's smallest subnormal (6e-8) and would flush to zero when the output gradient is
         # rounded to the storage type.  The reference always pairs fp16 with GradScaler (trainer.py:341,389); this package's
@@ -248,7 +271,7 @@ class _ReleasedUnit(torch.autograd.Function):
             z2 = _conv_prec(t1, ops.pack_conv_weight(w2.contiguous()), 3, 3, s, (1, 1), prec)
             if ws is not None:
                 zs = _conv_prec(x, ops.pack_conv_weight(ws.contiguous()), 1, 1, s, (0, 0), prec)
-        dz2, dg2, db2 = ops.bn_rows_bwd(dout.view(-1, depth), z2.view(-1, depth), sm2, si2, g2, split_out=split)
+        dz2, dg2, db2 = _rows_bwd(sync, dout.view(-1, depth), z2.view(-1, depth), sm2, si2, g2, split_out=split)
         del z2
         dz2 = dz2.view(n, ho, wo, depth)
         dw2 = ops.conv2d_wgrad(dz2, t1, 3, 3, stride=s, pad=(1, 1), b3=b3)
@@ -267,7 +290,7 @@ class _ReleasedUnit(torch.autograd.Function):
         dws = dgs = dbs = None
         addend = even = None
         if ws is not None:
-            dzs, dgs, dbs = ops.bn_rows_bwd(dout.view(-1, depth), zs.view(-1, depth), sms, sis, gs)
+            dzs, dgs, dbs = _rows_bwd(sync, dout.view(-1, depth), zs.view(-1, depth), sms, sis, gs)
             dzs = dzs.view(n, ho, wo, depth)
             if split and s == 1:
                 dzs = ops.split_bf16(dzs)
@@ -284,12 +307,13 @@ class _ReleasedUnit(torch.autograd.Function):
             addend = dout
         rows_ok = need_dx and addend is not None and cin % 4 == 0
         if xh is not None:   # x_hat is what was saved: mean 0, invstd 1, and the outer gamma * invstd factor as the "weight"
-            dx, dg1, db1 = ops.bn_rows_bwd(dxb.view(-1, cin), xh.view(-1, cin), torch.zeros_like(sm1), torch.ones_like(si1),
-                                           (g1 * si1).contiguous(), add=addend.view(-1, cin) if rows_ok else None)
+            # (synchronised: the sums of THIS form -- sum dy, sum dy * x_hat of the global statistics -- are the ones exchanged)
+            dx, dg1, db1 = _rows_bwd(sync, dxb.view(-1, cin), xh.view(-1, cin), torch.zeros_like(sm1), torch.ones_like(si1),
+                                     (g1 * si1).contiguous(), add=addend.view(-1, cin) if rows_ok else None)
             del xh
         else:
-            dx, dg1, db1 = ops.bn_rows_bwd(dxb.view(-1, cin), x.view(-1, cin), sm1, si1, g1,
-                                           add=addend.view(-1, cin) if rows_ok else None)
+            dx, dg1, db1 = _rows_bwd(sync, dxb.view(-1, cin), x.view(-1, cin), sm1, si1, g1,
+                                     add=addend.view(-1, cin) if rows_ok else None)
         del dxb
         dx = dx.view(n, h, w, cin)
         if need_dx and not rows_ok:
@@ -299,7 +323,7 @@ class _ReleasedUnit(torch.autograd.Function):
                 dx[:, ::2, ::2] += even
             elif ws is None and s > 1:
                 dx[:, ::s, ::s] += dout
-        return (dx if need_dx else None), None, None, None, dg1, db1, dw1, da1, dw2, dg2, db2, dws, dgs, dbs
+        return (dx if need_dx else None), None, None, None, dg1, db1, dw1, da1, dw2, dg2, db2, dws, dgs, dbs, None
 
 
 class _ReleasedStem(torch.autograd.Function):
@@ -310,13 +334,13 @@ class _ReleasedStem(torch.autograd.Function):
     result is kept for the backward; the BatchNorm output the PReLU saw is recomputed from the saved statistics."""
 
     @staticmethod
-    def forward(ctx, x, bn, w, g, b, a):
+    def forward(ctx, x, bn, w, g, b, a, sync=None):
         n, _, h, wd = x.shape
         z = ops.conv2d(x.contiguous(), ops.pack_conv_weight(w.detach().contiguous()), 3, 3, pad=(1, 1), x_nchw=True)
-        zb, sm, si = ops.bn_rows_fwd(z.view(-1, 64), g.detach(), b.detach(), bn.running_mean, bn.running_var, True, bn.eps,
-                                     bn.momentum)
+        zb, sm, si = _rows_fwd(sync, z.view(-1, 64), g.detach(), b.detach(), bn)
         y = ops.prelu_fwd(zb.view(n, h, wd, 64), a.detach().contiguous())
         ctx.save_for_backward(x, z, sm, si, g.detach(), b.detach(), a.detach())
+        ctx.sync = sync
         return y
 
     @staticmethod
@@ -327,12 +351,12 @@ class _ReleasedStem(torch.autograd.Function):
         zb = torch.addcmul(sh, z, sc)
         dzb, da = ops.prelu_bwd(dy.contiguous(), zb, a.contiguous())
         del zb
-        dz, dg, db = ops.bn_rows_bwd(dzb.view(-1, 64), z.view(-1, 64), sm, si, g)
+        dz, dg, db = _rows_bwd(ctx.sync, dzb.view(-1, 64), z.view(-1, 64), sm, si, g)
         del dzb
         x4 = torch.zeros((n, h, wd, 4), device=x.device, dtype=torch.float32)
         x4[..., :3] = x.permute(0, 2, 3, 1)
         dw = ops.conv2d_wgrad(dz.view(n, h, wd, 64), x4, 3, 3, stride=1, pad=(1, 1), b3=True)[:, :3].contiguous()
-        return None, None, dw, dg, db, da
+        return None, None, dw, dg, db, da, None
 
 
 class _ReleasedHead(torch.autograd.Function):
@@ -343,19 +367,18 @@ class _ReleasedHead(torch.autograd.Function):
     Everything runs on the exact-fp32 kernels (row BatchNorm fwd/bwd, igemm GEMMs, TN weight-gradient GEMM)."""
 
     @staticmethod
-    def forward(ctx, y, mask, bn2, fc, bn1, w2, b2, wfc, bfc, w1, b1):
+    def forward(ctx, y, mask, bn2, fc, bn1, w2, b2, wfc, bfc, w1, b1, sync=None):
         n, h, w, c = y.shape
         rows = y.view(n * h * w, c)
-        o2, sm2, si2 = ops.bn_rows_fwd(rows, w2.detach(), b2.detach(), bn2.running_mean, bn2.running_var, True, bn2.eps,
-                                       bn2.momentum)
+        o2, sm2, si2 = _rows_fwd(sync, rows, w2.detach(), b2.detach(), bn2)
         hfeat = ops.act_mask_bwd(o2, o2, mask.view(n * h * w, c), slope=1.0) if mask is not None else o2  # o2 * mask
         k = h * w * c
         whwc = wfc.detach().view(wfc.shape[0], c, h * w).permute(0, 2, 1).contiguous().view(wfc.shape[0], k)  # (c,h,w)->(h,w,c)
         e = ops.linear(hfeat.view(n, k), whwc, bias=bfc.detach(), split_k=max(1, min(k // 32, 192 // ((n + 127) // 128))))
-        e2, sm1, si1 = ops.bn_rows_fwd(e, w1.detach(), b1.detach(), bn1.running_mean, bn1.running_var, True, bn1.eps,
-                                       bn1.momentum)
+        e2, sm1, si1 = _rows_fwd(sync, e, w1.detach(), b1.detach(), bn1, large=False)   # (one row per frame)
         ctx.save_for_backward(rows, mask, hfeat, e, e2, sm2, si2, sm1, si1, whwc, w2.detach(), w1.detach())
         ctx.dims = (n, h, w, c)
+        ctx.sync = sync
         return ops.l2norm_rows(e2)
 
     @staticmethod
@@ -364,16 +387,16 @@ class _ReleasedHead(torch.autograd.Function):
         n, h, w, c = ctx.dims
         k = h * w * c
         de2 = ops.l2norm_rows_bwd(demb.contiguous(), e2)
-        de, dw1, db1 = ops.bn_rows_bwd(de2, e, sm1, si1, w1)
+        de, dw1, db1 = _rows_bwd(ctx.sync, de2, e, sm1, si1, w1)
         dwhwc = ops.conv1d_wgrad(de, hfeat.view(n, k), n, 1, 1).view(-1, h * w, c)      # dW[o][(h,w,c)] = de^T hfeat
         dwfc = dwhwc.permute(0, 2, 1).reshape(-1, k)                                     # back to the (c,h,w) flatten order
         dbfc = ops.col_sum(de)
         dh = ops.linear(de, whwc.t().contiguous())                                       # [n, k] = de @ W
         do2 = ops.act_mask_bwd(dh.view(n * h * w, c), dh.view(n * h * w, c), mask.view(n * h * w, c), slope=1.0) \
             if mask is not None else dh.view(n * h * w, c)
-        dy, dw2, db2 = ops.bn_rows_bwd(do2, rows, sm2, si2, w2)
+        dy, dw2, db2 = _rows_bwd(ctx.sync, do2, rows, sm2, si2, w2)
         dy = dy.view(n, h, w, c) if ctx.needs_input_grad[0] else None  # only when body units below are released too
-        return dy, None, None, None, None, dw2, db2, dwfc, dbfc, dw1, db1
+        return dy, None, None, None, None, dw2, db2, dwfc, dbfc, dw1, db1, None
 
 
 class IR50(nn.Module):
@@ -382,6 +405,9 @@ class IR50(nn.Module):
     # data_parallel.BatchNormSync attached by ClipDataParallel(sync_bn=...): the batch-statistics forwards then normalise
     # with the statistics of all ranks' frames (BatchNorm2d and the head BatchNorm1d)
     bn_sync = None
+    # ClipDataParallel(sync_released=True): the released head / units / stem (_ReleasedHead, _ReleasedUnit, _ReleasedStem) take
+    # their statistics and backward sums from ``bn_sync`` too; without it a released parameter is refused under ``bn_sync``
+    sync_released = False
 
     def __init__(self, input_channels=3, drop_ratio=0.4, head_hw=5, embedding_dim=512):
         super().__init__()
@@ -680,7 +706,7 @@ class IR50(nn.Module):
         plan = self._release_plan()
         first_released = len(P["units"]) if plan is None else plan
         if plan is not None:
-            self._resolve_activation_memory(x.shape[0], x.shape[2])
+            self._resolve_activation_memory(x.shape[0], x.shape[2], x.device)
         y = ys = xst = None
         if plan is not None and self._stem_released():
             y = self._released_stem(x)
@@ -797,7 +823,7 @@ class IR50(nn.Module):
         plan = self._release_plan()
         first_released = len(P["units"]) if plan is None else plan
         if plan is not None:
-            self._resolve_activation_memory(x.shape[0], x.shape[2])
+            self._resolve_activation_memory(x.shape[0], x.shape[2], x.device)
         y = ys = xst = None
         if plan is not None and self._stem_released():
             y = self._released_stem(x)
@@ -893,19 +919,32 @@ class IR50(nn.Module):
 
     def _released_stem(self, x):
         il = self.input_layer
-        return _ReleasedStem.apply(x, il[1], il[0].weight, il[1].weight, il[1].bias, il[2].weight)
+        return _ReleasedStem.apply(x, il[1], il[0].weight, il[1].weight, il[1].bias, il[2].weight, self._release_sync())
 
-    def _resolve_activation_memory(self, frames, hw):
-        """What the released units of THIS forward keep (see ``activation_memory``); called once per forward."""
+    def _release_sync(self):
+        """The BatchNormSync of the released parts, or None (their statistics stay the rank's own)."""
+        return self.bn_sync if self.sync_released else None
+
+    def _resolve_activation_memory(self, frames, hw, device=None):
+        """What the released units of THIS forward keep (see ``activation_memory``); called once per forward.  Under
+        ``sync_released`` the ranks agree on "auto" (raw only where it fits on every rank: an all-reduce MIN on the sync
+        group), so that no rank runs the slower plan alone and straggles at the exchanges; the gradients are the same bits
+        either way."""
         mode = self.activation_memory
         if mode not in ("auto", "raw", "recompute", "recompute16"):
             raise ValueError(f"unknown activation_memory {mode!r}")
         if mode == "auto":
             released = sum(1 for u in self.body if all(p.requires_grad for p in u.parameters()))
             raw = 410e6 * (hw / 224.0) ** 2 * frames * released / len(self.body)      # fp32 raw tensors of the released units
-            free, _ = torch.cuda.mem_get_info()
-            free += torch.cuda.memory_reserved() - torch.cuda.memory_allocated()      # the allocator's cached blocks are reusable
-            mode = "raw" if 1.6 * raw < free else "recompute"
+            sync = self._release_sync()
+            if sync is not None:
+                free, _ = torch.cuda.mem_get_info(device)
+                free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+                mode = "raw" if sync.agree_min(1.6 * raw < free, device) else "recompute"
+            else:
+                free, _ = torch.cuda.mem_get_info()
+                free += torch.cuda.memory_reserved() - torch.cuda.memory_allocated()  # the allocator's cached blocks are reusable
+                mode = "raw" if 1.6 * raw < free else "recompute"
         self._act_mem = mode
         return mode
 
@@ -914,11 +953,13 @@ class IR50(nn.Module):
         sc = u.shortcut_layer if u.cin != u.depth else None
         return _ReleasedUnit.apply(y, u, prec, self._act_mem, pr[0].weight, pr[0].bias, pr[1].weight, pr[2].weight, pr[3].weight, pr[4].weight,
                                    pr[4].bias, sc[0].weight if sc is not None else None,
-                                   sc[1].weight if sc is not None else None, sc[1].bias if sc is not None else None)
+                                   sc[1].weight if sc is not None else None, sc[1].bias if sc is not None else None,
+                                   self._release_sync())
 
     def _released_head(self, y, head_mask):
         bn2, fc, bn1 = self.output_layer[0], self.output_layer[3], self.output_layer[4]
-        out = _ReleasedHead.apply(y, head_mask, bn2, fc, bn1, bn2.weight, bn2.bias, fc.weight, fc.bias, bn1.weight, bn1.bias)
+        out = _ReleasedHead.apply(y, head_mask, bn2, fc, bn1, bn2.weight, bn2.bias, fc.weight, fc.bias, bn1.weight, bn1.bias,
+                                  self._release_sync())
         torch._foreach_add_([m.num_batches_tracked for m in self.modules()
                              if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d))], 1)
         return out
@@ -944,11 +985,13 @@ class IR50(nn.Module):
                                bn1.eps, bn1.momentum)[0]
 
     def check_sync_release(self):
-        """Synchronised statistics cover the frozen encoder only: refuse released units / head before anything runs."""
-        if self.bn_sync is not None and self.training and self.bn_mode == "reference" and torch.is_grad_enabled() and \
+        """Synchronised statistics cover the released units / head / stem only under ``sync_released``: otherwise refuse them
+        before anything runs."""
+        if self.bn_sync is not None and not self.sync_released and self.training and self.bn_mode == "reference" and torch.is_grad_enabled() and \
                 any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("sync_bn with released encoder parameters is not implemented yet (follow-up: "
-                                      "synchronised statistics in _ReleasedUnit / _ReleasedStem / _ReleasedHead)")
+            raise NotImplementedError("sync_bn with released encoder parameters is not implemented on the default path "
+                                      "(synchronised statistics in _ReleasedUnit / _ReleasedStem / _ReleasedHead are opt-in: "
+                                      "ClipDataParallel(model, sync_bn=True, sync_released=True))")
 
     def _forward_batch_stats(self, x, head_mask=None):
         """Reference train() semantics: every BatchNorm uses batch statistics over the N frames and
@@ -960,7 +1003,7 @@ class IR50(nn.Module):
         plan = self._release_plan()
         first_released = len(P["units"]) if plan is None else plan
         if plan is not None:
-            self._resolve_activation_memory(x.shape[0], x.shape[2])
+            self._resolve_activation_memory(x.shape[0], x.shape[2], x.device)
         xst = None
         if plan is not None and self._stem_released():
             y = self._released_stem(x)

@@ -348,6 +348,21 @@ int cer_bn_rows_bwd_sums(const float *dy, int dy_ld, const float *x, int x_ld, c
 int cer_bn_rows_bwd_apply(const float *dy, int dy_ld, const float *x, int x_ld, const float *save_mean,
                           const float *save_invstd, const float *w, const float *sums, double count, float *dx, int R, int C,
                           void *stream);
+/* The same split for the released encoder units' row BatchNorms (dense rows, C % 4 == 0, 16-byte aligned):
+ *   cer_bn_rows_moments_large  moments [3][C] float64 like cer_bn_rows_moments, for any R (up to 51 M rows and R * C > 2^31):
+ *                              ONE read of x by many row slabs, each summing about its own first row in fp32, then the slab
+ *                              partials merged in float64 in a fixed order (deterministic); workspace of
+ *                              cer_bn_rows_moments_large_workspace_bytes(R, C) bytes;
+ *   cer_bn_rows_bwd_apply_split  the apply pass of cer_bn_rows_bwd_split (dx as hi / lo bf16 planes) from given sums [2][C]
+ *                              (sum dy | sum dy * x_hat) over count rows;
+ *   cer_bn_rows_bwd_apply_add  the apply pass of cer_bn_rows_bwd_add (fp32 dx, optional addend) from given sums over count rows.
+ * With the local sums of cer_bn_rows_bwd_sums and count == R the two apply passes write the unsynchronised entry points' bits. */
+size_t cer_bn_rows_moments_large_workspace_bytes(int R, int C);
+int cer_bn_rows_moments_large(const float *x, int R, int C, double *moments, void *workspace, size_t workspace_bytes, void *stream);
+int cer_bn_rows_bwd_apply_split(const float *dy, const float *x, const float *save_mean, const float *save_invstd, const float *w,
+                                const float *sums, double count, uint16_t *dx_hi, uint16_t *dx_lo, int R, int C, void *stream);
+int cer_bn_rows_bwd_apply_add(const float *dy, const float *x, const float *save_mean, const float *save_invstd, const float *w,
+                              const float *sums, double count, const float *add, float *dx, int R, int C, void *stream);
 
 /* LFAN cross-modal attention core (reference models/transformer.py:11-19,133-159): for each
  * (row, head) an M x M softmax over MODALITIES, vals = softmax(q k^T/sqrt(hd)) v + v.
