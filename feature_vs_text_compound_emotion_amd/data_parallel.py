@@ -355,12 +355,55 @@ class _FlatOptimizer(torch.optim.Optimizer):
     buffers of a ``ClipDataParallel``.  Being an ``Optimizer`` is what lets torch's schedulers (and the reference's
     ``MyStepLR`` / ``MyCosineLR``, base/scheduler.py:167-256) drive it: they type-check for it and read / write
     ``param_groups[*]['lr']`` and ``initial_lr``.  The state lives in flat buffers, not in ``self.state``, so ``state_dict``
-    / ``load_state_dict`` are the subclasses' own."""
+    / ``load_state_dict`` are the subclasses' own.
+
+    Loss scaling: ``_step_supports_amp_scaling`` makes ``torch.amp.GradScaler.step`` hand the update ``grad_scale`` and
+    ``found_inf`` as device tensors (attributes set around ``step()``) instead of reading ``found_inf`` on the host; the update
+    then unscales and skips on the device (``ops.*_flat_amp``).  The applied-step count those launches need lives on the
+    device (``_applied``, int64) from the first such step on; ``steps`` reads it (one host read) and a plain step folds it
+    back into the host count."""
+
+    _step_supports_amp_scaling = True
 
     def __init__(self, ddp, defaults):
         super().__init__(ddp.params, defaults)
         self.ddp = ddp
         self.flat_param = ddp.flatten_parameters()
+        self._steps, self._applied, self._amp_bound = 0, None, 0
+
+    @property
+    def steps(self):
+        """Applied steps (skipped loss-scaled steps do not count).  A host read once a loss-scaled step has run."""
+        return self._steps if self._applied is None else int(self._applied.item())
+
+    @steps.setter
+    def steps(self, value):
+        self._steps, self._applied = int(value), None
+
+    def _amp_state(self):
+        """(grad_scale, found_inf) when a GradScaler drives this step, else None.  GradScaler sets ``found_inf`` always and
+        ``grad_scale`` unless the gradients were unscaled already (an explicit ``scaler.unscale_(opt)``)."""
+        found_inf = getattr(self, "found_inf", None)
+        if found_inf is None:
+            return None
+        grad_scale = getattr(self, "grad_scale", None)
+        if grad_scale is not None:
+            grad_scale = grad_scale.reshape(1).to(torch.float32)
+        return grad_scale, found_inf.reshape(1).to(torch.float32)
+
+    def _device_applied(self):
+        """The device-resident applied-step counter, started from the host count (a fill launch, no host read); advances
+        ``_amp_bound``, the host's upper bound of the count after this step."""
+        if self._applied is None:
+            self._applied = torch.full((1,), self._steps, dtype=torch.int64, device=self.flat_param.device)
+            self._amp_bound = self._steps
+        self._amp_bound += 1
+        return self._applied
+
+    def _fold_applied(self):
+        """Before a plain step: bring a device-resident count back to the host (no-op unless a loss-scaled step ran)."""
+        if self._applied is not None:
+            self.steps = self.steps
 
     def zero_grad(self, set_to_none=False):
         self.ddp.zero_grad()
@@ -390,12 +433,19 @@ class FlatNesterovSGD(_FlatOptimizer):
         super().__init__(ddp, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                                    nesterov=nesterov))
         self.buf = torch.zeros_like(self.flat_param)
-        self.steps = 0
 
     def step(self):
         from . import ops
         self.ddp.gather_gradients()
         g = self.param_groups[0]
+        amp = self._amp_state()
+        if amp is not None:
+            ops.sgd_nesterov_flat_amp(self.flat_param, self.ddp.flat, self.buf, g["lr"], *amp, self._device_applied(),
+                                      momentum=g["momentum"], dampening=g["dampening"], weight_decay=g["weight_decay"],
+                                      nesterov=g["nesterov"])
+            self._bump_versions()
+            return
+        self._fold_applied()
         ops.sgd_nesterov_flat(self.flat_param, self.ddp.flat, self.buf, g["lr"], g["momentum"], g["dampening"],
                               g["weight_decay"], g["nesterov"], first_step=self.steps == 0)
         self.steps += 1
@@ -423,12 +473,41 @@ class FlatAdam(_FlatOptimizer):
         self.exp_avg = torch.zeros_like(self.flat_param)
         self.exp_avg_sq = torch.zeros_like(self.flat_param)
         self.max_exp_avg_sq = torch.zeros_like(self.flat_param) if amsgrad else None
-        self.steps = 0
+        self._bias, self._bias_betas, self._bias_saturated = None, None, False
+
+    def _bias_table(self, betas, need):
+        """[T, 2] float64 on the device: (1 - b1^k, sqrt(1 - b2^k)) for k = 1..T, computed with the Python-float arithmetic
+        torch.optim.Adam uses (and cer_adam_flat's std::pow), T >= ``need`` -- or shorter once both columns have reached 1.0,
+        after which every later k has the same entry (the kernel clamps k to T).  Grown by doubling; the copy goes from
+        pinned memory without a host synchronisation."""
+        b1, b2 = float(betas[0]), float(betas[1])
+        if self._bias is not None and self._bias_betas == (b1, b2) and (self._bias.shape[0] >= need or self._bias_saturated):
+            return self._bias
+        cap = max(need, 1024, 2 * (self._bias.shape[0] if self._bias is not None and self._bias_betas == (b1, b2) else 0))
+        rows = []
+        for k in range(1, cap + 1):
+            rows.append((1 - b1 ** k, (1 - b2 ** k) ** 0.5))
+            if rows[-1] == (1.0, 1.0):
+                break
+        self._bias_saturated = rows[-1] == (1.0, 1.0)
+        host = torch.tensor(rows, dtype=torch.float64).pin_memory()
+        self._bias = host.to(self.flat_param.device, non_blocking=True)
+        self._bias_betas = (b1, b2)
+        return self._bias
 
     def step(self):
         from . import ops
         self.ddp.gather_gradients()
         g = self.param_groups[0]
+        amp = self._amp_state()
+        if amp is not None:
+            applied = self._device_applied()       # _amp_bound: the largest step number this launch can use
+            ops.adam_flat_amp(self.flat_param, self.ddp.flat, self.exp_avg, self.exp_avg_sq, self.max_exp_avg_sq, g["lr"],
+                              self._bias_table(g["betas"], self._amp_bound), *amp, applied, betas=g["betas"], eps=g["eps"],
+                              weight_decay=g["weight_decay"], amsgrad=g["amsgrad"])
+            self._bump_versions()
+            return
+        self._fold_applied()
         ops.adam_flat(self.flat_param, self.ddp.flat, self.exp_avg, self.exp_avg_sq, self.max_exp_avg_sq, g["lr"],
                       self.steps + 1, betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], amsgrad=g["amsgrad"])
         self.steps += 1
@@ -448,3 +527,38 @@ class FlatAdam(_FlatOptimizer):
             self.max_exp_avg_sq.copy_(sd["max_exp_avg_sq"])
         self.steps = int(sd["steps"])
         self._load_groups(sd)
+
+
+class FlatGradScaler(torch.amp.GradScaler):
+    """``torch.amp.GradScaler`` whose gradient check / unscale is ONE launch over the flat bucket of a ``_FlatOptimizer``
+    (``ops.amp_check_unscale_flat``) instead of torch's foreach chain over the per-parameter views; any other optimiser goes
+    through torch's own route.  With the flat optimisers' ``_step_supports_amp_scaling``, ``step`` then hands ``grad_scale``
+    and ``found_inf`` to the fused update as device tensors, so ``scale -> backward -> step -> update`` reads nothing back to
+    the host.  ``update`` is torch's (``_amp_update_scale_``): the scale trajectory is torch's by construction.
+
+    Data parallel: call ``ddp.all_reduce_gradients()`` between ``backward`` and ``step``.  The check then runs on the
+    all-reduced bucket, and since the all-reduce SUMS the ranks' buckets, a non-finite gradient on any rank is non-finite on
+    every rank: all ranks find the same ``found_inf``, skip the same steps and move their scales in lockstep, without a
+    collective of their own."""
+
+    def _unscale_grads_(self, optimizer, inv_scale, found_inf, allow_fp16):
+        """``unscale_()`` (explicit, e.g. before clipping): check and unscale the bucket; the following ``step`` gets
+        ``grad_scale=None`` and only skips."""
+        if not isinstance(optimizer, _FlatOptimizer):
+            return super()._unscale_grads_(optimizer, inv_scale, found_inf, allow_fp16)
+        from . import ops
+        optimizer.ddp.gather_gradients()
+        ops.amp_check_unscale_flat(optimizer.ddp.flat, found_inf.reshape(1), inv_scale.reshape(1))
+        return {found_inf.device: found_inf}
+
+    def _check_inf_per_device(self, optimizer):
+        """``step()`` without a preceding ``unscale_()``: check only (the bucket is not written; the fused update unscales)."""
+        if not isinstance(optimizer, _FlatOptimizer):
+            return super()._check_inf_per_device(optimizer)
+        from . import ops
+        scale, _ = self._check_scale_growth_tracker("_check_inf_per_device")
+        found_inf = torch.full((), 0.0, dtype=torch.float32, device=scale.device)
+        optimizer.ddp.gather_gradients()
+        ops.amp_check_unscale_flat(optimizer.ddp.flat, found_inf.reshape(1))
+        self._per_optimizer_states[id(optimizer)]["found_inf_per_device"] = {found_inf.device: found_inf}
+        return self._per_optimizer_states[id(optimizer)]["found_inf_per_device"]

@@ -877,6 +877,71 @@ def adam_flat(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, step, betas=
                                     current_stream()), "cer_adam_flat")
 
 
+def _dev_scalar(t, name, dtype, device):
+    """A one-element tensor of ``dtype`` on ``device`` (GradScaler's scale / found_inf, the applied-step counter)."""
+    if not (t.is_cuda and t.dtype == dtype and t.numel() == 1 and t.device == device and t.is_contiguous()):
+        raise ValueError(f"{name}: expected a one-element {dtype} tensor on {device}, got {t.dtype} {t.device} numel={t.numel()}")
+
+
+def amp_check_unscale_flat(grad, found_inf, inv_scale=None):
+    """``torch._amp_foreach_non_finite_check_and_unscale_`` over the flat fp32 gradient bucket in one launch: ``found_inf``
+    (fp32 device scalar) becomes 1 if any element is Inf / NaN; with ``inv_scale`` (fp32 device scalar) the bucket is unscaled
+    in place, without it only checked."""
+    _dev_f32(grad, "grad")
+    _dev_scalar(found_inf, "found_inf", torch.float32, grad.device)
+    if inv_scale is not None:
+        _dev_scalar(inv_scale, "inv_scale", torch.float32, grad.device)
+    check(_lib.load().cer_amp_check_unscale_flat(ptr(grad), grad.numel(), ptr(inv_scale), ptr(found_inf), current_stream()),
+          "cer_amp_check_unscale_flat")
+
+
+def _amp_scalars(grad, grad_scale, found_inf, applied):
+    if grad_scale is not None:
+        _dev_scalar(grad_scale, "grad_scale", torch.float32, grad.device)
+    _dev_scalar(found_inf, "found_inf", torch.float32, grad.device)
+    _dev_scalar(applied, "applied", torch.int64, grad.device)
+
+
+def sgd_nesterov_flat_amp(param, grad, buf, lr, grad_scale, found_inf, applied, momentum=0.9, dampening=0.0, weight_decay=0.0,
+                          nesterov=True):
+    """``sgd_nesterov_flat`` under a GradScaler: skipped on the device when ``found_inf`` != 0, gradients unscaled in place by
+    ``grad_scale`` (None: already unscaled), ``applied`` (int64 device scalar) counts the applied steps and decides the first
+    step."""
+    for t, nme in ((param, "param"), (grad, "grad"), (buf, "buf")):
+        _dev_f32(t, nme)
+        if t.numel() != param.numel():
+            raise ValueError(f"{nme}: expected {param.numel()} elements, got {t.numel()}")
+    _amp_scalars(grad, grad_scale, found_inf, applied)
+    check(_lib.load().cer_sgd_nesterov_flat_amp(ptr(param), ptr(grad), ptr(buf), param.numel(), lr, momentum, dampening,
+                                                weight_decay, int(nesterov), ptr(grad_scale), ptr(found_inf), ptr(applied),
+                                                current_stream()), "cer_sgd_nesterov_flat_amp")
+
+
+def adam_flat_amp(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq, lr, bias_correction, grad_scale, found_inf, applied,
+                  betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False):
+    """``adam_flat`` under a GradScaler: as ``sgd_nesterov_flat_amp``; the step is ``applied + 1`` on the device and its bias
+    corrections come from ``bias_correction`` [T, 2] float64 (1 - b1^k, sqrt(1 - b2^k) for k = 1..T)."""
+    bufs = [(param, "param"), (grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")]
+    if amsgrad:
+        if max_exp_avg_sq is None:
+            raise ValueError("max_exp_avg_sq: required with amsgrad")
+        bufs.append((max_exp_avg_sq, "max_exp_avg_sq"))
+    for t, nme in bufs:
+        _dev_f32(t, nme)
+        if t.numel() != param.numel():
+            raise ValueError(f"{nme}: expected {param.numel()} elements, got {t.numel()}")
+    if not (bias_correction.is_cuda and bias_correction.dtype == torch.float64 and bias_correction.is_contiguous()
+            and bias_correction.dim() == 2 and bias_correction.shape[1] == 2 and bias_correction.shape[0] >= 1
+            and bias_correction.device == param.device):
+        raise ValueError("bias_correction: expected a contiguous [T >= 1, 2] float64 tensor on the parameters' device")
+    _amp_scalars(grad, grad_scale, found_inf, applied)
+    check(_lib.load().cer_adam_flat_amp(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq),
+                                        ptr(max_exp_avg_sq) if amsgrad else None, param.numel(), float(lr), float(betas[0]),
+                                        float(betas[1]), float(eps), float(weight_decay), int(amsgrad), ptr(bias_correction),
+                                        bias_correction.shape[0], ptr(grad_scale), ptr(found_inf), ptr(applied),
+                                        current_stream()), "cer_adam_flat_amp")
+
+
 # ------------------------------------------------------------------ trainable tail
 def weight_norm_fwd(v, g):
     """v [Cout,Cin,k], g [Cout,1,1] -> (w [Cout,Cin,k], norm [Cout])."""

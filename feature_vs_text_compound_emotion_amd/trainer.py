@@ -19,6 +19,7 @@ Two ways in:
 Logging (dllogger), pickled outputs, PerfTracker reports and best-model files stay with the reference's trainer: they are
 its control plane, not this path.
 """
+import contextlib
 import math
 from collections import Counter
 from types import SimpleNamespace
@@ -400,6 +401,7 @@ class Trainer(DeviceEvalMixin):
         self.device = device
         self.model = model.to(device) if hasattr(model, "to") else model     # base/trainer.py:25
         self.optimizer, self.scheduler = optimizer, None
+        self.scaler = None                               # the --amp GradScaler (trainer.py:341), one per train_one_epoch
         self.criterion = criterion if criterion is not None else cross_entropy_loss
         self.model_name, self.train_batch_size = model_name, train_batch_size
         self.number_classes = number_classes if number_classes is not None else 7
@@ -483,8 +485,23 @@ class Trainer(DeviceEvalMixin):
             labels = inputs.pop(EXPR, None)
         return inputs, labels
 
+    def _train_amp(self):
+        """``--amp`` on a GPU: the step runs the forward and the loss under fp16 autocast, as ``inference`` does, with loss
+        scaling (trainer.py:341,365-391)."""
+        return bool(self._arg("amp", False)) and _is_gpu(self.device)
+
+    def _new_scaler(self):
+        """``FlatGradScaler`` with ``data_parallel`` (one launch over the flat bucket, no host read in the step), torch's
+        ``GradScaler`` otherwise."""
+        if self.ddp is not None:
+            from .data_parallel import FlatGradScaler
+            return FlatGradScaler("cuda")
+        return torch.amp.GradScaler("cuda")
+
     def train_step(self, X, indices=None):
-        """One iteration of trainer.py:345-391.  Returns the (detached) loss tensor."""
+        """One iteration of trainer.py:345-391.  Returns the (detached) loss tensor.  With ``args.amp`` (GPU): autocast
+        forward and loss, then ``scaler.scale(loss).backward()``, the gradient all-reduce, ``scaler.step``, ``scaler.update``
+        -- a step with a non-finite gradient is skipped and halves the scale, as the reference's GradScaler does."""
         inputs, labels = self._split(X)
         if labels.numel() == self.train_batch_size:  # the reference's "todo : fix this." label hack (:360-363)
             n = len(indices[0]) if indices is not None else labels.shape[1]
@@ -493,22 +510,35 @@ class Trainer(DeviceEvalMixin):
             self.ddp.zero_grad()
         else:
             self.optimizer.zero_grad(set_to_none=True)
-        outputs = self.model(inputs)
-        bsz, nfms, d = labels.shape
-        assert d == 1, d
-        assert outputs.ndim == 3 and tuple(outputs.shape) == (bsz, nfms, self.number_classes), tuple(outputs.shape)
-        loss = self.criterion(outputs.contiguous().view(bsz * nfms, -1), labels.contiguous().view(bsz * nfms).long())  # trainer.py:380-383
-        loss.backward()
+        amp = self._train_amp()
+        with torch.autocast("cuda", dtype=torch.float16) if amp else contextlib.nullcontext():
+            outputs = self.model(inputs)
+            bsz, nfms, d = labels.shape
+            assert d == 1, d
+            assert outputs.ndim == 3 and tuple(outputs.shape) == (bsz, nfms, self.number_classes), tuple(outputs.shape)
+            loss = self.criterion(outputs.contiguous().view(bsz * nfms, -1), labels.contiguous().view(bsz * nfms).long())  # trainer.py:380-383
+        if not amp:
+            loss.backward()
+            if self.ddp is not None:
+                self.ddp.all_reduce_gradients()
+            self.optimizer.step()
+            return loss.detach()
+        if self.scaler is None:
+            self.scaler = self._new_scaler()
+        self.scaler.scale(loss).backward()
         if self.ddp is not None:
-            self.ddp.all_reduce_gradients()
-        self.optimizer.step()
+            self.ddp.all_reduce_gradients()   # found_inf is taken after it: every rank sees the summed bucket
+        self.scaler.step(self.optimizer)
+        self.scaler.update()
         return loss.detach()
 
     def train_one_epoch(self, dataloader=None):
-        """trainer.py:315-434 (the reference reads ``self.dataloaders[TRAINSET]``; a loader may also be passed)."""
+        """trainer.py:315-434 (the reference reads ``self.dataloaders[TRAINSET]``; a loader may also be passed).  Like the
+        reference, ``--amp`` starts every epoch with a fresh GradScaler (trainer.py:341)."""
         if dataloader is None:
             dataloader = self.dataloaders[TRAINSET]
         self.model.train()
+        self.scaler = self._new_scaler() if self._train_amp() else None
         running, count = 0.0, 0
         for X, trials, lengths, indices in dataloader:
             running = running + self.train_step(X, indices)

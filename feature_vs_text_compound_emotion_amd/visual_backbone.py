@@ -244,9 +244,10 @@ class _ReleasedUnit(torch.autograd.Function):
         s, prec, sync = ctx.stride, ctx.prec, ctx.sync
         # fp16 storage has no range for UN-scaled gradients: a mean cross-entropy gradient divided over B*L rows and H*W
         # pixels sits at or below fp16's smallest subnormal (6e-8) and would flush to zero when the output gradient is
-        # rounded to the storage type.  The reference always pairs fp16 with GradScaler (trainer.py:341,389); this package's
-        # own Trainer has no scaler, so the data-gradient convs of an fp16 encoder run on the bf16x3 kernels (fp32 range,
-        # 2^-15 per product) -- scaled or not, nothing underflows.
+        # rounded to the storage type.  The reference always pairs fp16 with GradScaler (trainer.py:341,389), and so does this
+        # package's Trainer under --amp (FlatGradScaler with data_parallel), but fp16 may also run without a scaler (precision
+        # = "fp16" set directly, or autocast alone), so the data-gradient convs of an fp16 encoder run on the bf16x3 kernels
+        # (fp32 range, 2^-15 per product) -- scaled or not, nothing underflows.
         dprec = "bf16x3" if prec == "fp16" else prec
         n, h, w, cin = x.shape              # (the saved tensor: x, or its normalised fp16 plane -- same shape)
         _, ho, wo, depth = ctx.out_shape

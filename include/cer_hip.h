@@ -452,6 +452,28 @@ int cer_adam_flat(float *param, const float *grad, float *exp_avg, float *exp_av
                   double lr, double beta1, double beta2, double eps, double weight_decay, int amsgrad, int64_t step,
                   void *stream);
 
+/* Loss scaling over the flat buffers (torch.amp.GradScaler's contract for an optimiser with _step_supports_amp_scaling), no host
+ * read of device state.  cer_amp_check_unscale_flat: torch._amp_foreach_non_finite_check_and_unscale_ over the whole bucket in
+ * one launch -- *found_inf = 1.0f if any input element is Inf / NaN (never reset), and, when inv_scale (a device scalar) is
+ * given, every element becomes *inv_scale == 1 ? g : g * *inv_scale; inv_scale NULL: check only, grad is not written.
+ * n % 4 == 0, grad 16-byte aligned. */
+int cer_amp_check_unscale_flat(float *grad, size_t n, const float *inv_scale, float *found_inf, void *stream);
+
+/* cer_sgd_nesterov_flat / cer_adam_flat with a device-side skip: if *found_inf != 0 nothing changes (parameters, moments,
+ * *applied); otherwise, when grad_scale is given, each gradient is first unscaled by (float)(1 / (double)*grad_scale) and
+ * written back into grad, then the update runs with the per-element arithmetic of the plain entry points, and *applied (the
+ * device-resident count of applied steps, int64) is incremented by a second one-thread launch on the same stream.  SGD: the
+ * momentum buffer is initialised on the first applied step (*applied == 0).  Adam: step k = *applied + 1 reads
+ * bias_correction[2(k-1)] = 1 - beta1^k and bias_correction[2(k-1)+1] = sqrt(1 - beta2^k) (double, host-computed; k is
+ * clamped to table_len, whose last entry must then hold for every later k) and forms -lr / (1 - beta1^k) in double. */
+int cer_sgd_nesterov_flat_amp(float *param, float *grad, float *momentum_buf, size_t n, float lr, float momentum,
+                              float dampening, float weight_decay, int nesterov, const float *grad_scale, const float *found_inf,
+                              int64_t *applied, void *stream);
+int cer_adam_flat_amp(float *param, float *grad, float *exp_avg, float *exp_avg_sq, float *max_exp_avg_sq, size_t n,
+                      double lr, double beta1, double beta2, double eps, double weight_decay, int amsgrad,
+                      const double *bias_correction, int64_t table_len, const float *grad_scale, const float *found_inf,
+                      int64_t *applied, void *stream);
+
 /* out[i][:] = src[index[i]][:], zeros where index[i] < 0 or >= n_src: the token -> frame spreading of the BERT rows
  * (abaw5_pre_processing/base/speech.py:690-738) and the edge-padded frame indexing of VGGish rows
  * (base/preprocessing.py:992-1018); the index plan is host logic.  cols % 4 == 0. */
