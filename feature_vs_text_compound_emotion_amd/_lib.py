@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_PKG_DIR, "libcer_hip.so")
 
 ACT_NONE, ACT_PRELU, ACT_LEAKY, ACT_RELU, ACT_GELU = 0, 1, 2, 3, 4
 STORE_NONE, STORE_BF16, STORE_F16 = 0, 1, 2
+FC_ACT_NONE, FC_ACT_F32, FC_ACT_SPLIT, FC_ACT_BF16, FC_ACT_F16 = 0, 1, 2, 3, 4   # cer_fc_act_kind
 
 
 class ConvDesc(Structure):
@@ -85,6 +86,8 @@ _SIGNATURES = {
     "cer_col_sum": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
     "cer_bn_bwd_sums": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
     "cer_act_mask_bwd": (c_int, [_P, _P, _P, _P, c_size_t, c_float, _P]),
+    "cer_fc_bwd_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "cer_fc_bwd_elem": (c_int, [_P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
     "cer_tblock_tail_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, c_float, _P]),
     "cer_bn_rows_fwd_workspace_bytes": (c_size_t, [c_int, c_int]),
     "cer_bn_rows_fwd": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float,

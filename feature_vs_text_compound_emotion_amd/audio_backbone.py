@@ -53,6 +53,74 @@ def example_starts(num_frames, window_frames, hop_frames):
     return [round(hop_frames * i) for i in range(max(n, 0))]
 
 
+def _fc_split_k(n):
+    return max(1, min(8, 512 // max(1, (n + 127) // 128 * 32)))
+
+
+def _rows2d(t):
+    """[n, 1, 1, C] (or [n, C]) fp32 tensor / 16-bit plane / Split -> the [n, C] view."""
+    n, c = t.shape[0], t.shape[-1]
+    return t.view(n, c)
+
+
+class _ReleasedEmbeddings(torch.autograd.Function):
+    """VGGish's embedding stack (Linear 12288->4096, ReLU, Linear 4096->4096, ReLU, Linear 4096->128; backbone.py:16-31)
+    WITH its backward, for the audio groups of the reference's gradual release (base/parameter_control.py:58,85-103:
+    parameters 16-17, then 14-15, then 12-13 -- always a suffix of the stack, top first).
+
+    Forward: exactly the kernels of the frozen forward (``VGGish._embed``), so the output is the same bits.  It keeps the
+    input of every released layer as the planes the forward already made (fp32, ``Split`` or one 16-bit plane); the input
+    of the layer above a ReLU is that ReLU's output, i.e. the mask of the layer below.
+
+    Backward, top layer down: ``ops.fc_bwd`` (ReLU mask + split + bias gradient in one pass), the weight gradient as a 1x1
+    conv weight gradient over the rows (the bf16x3 kernel on split operands; the fp32 kernel in "fp32"), and -- only while a
+    lower layer is released -- the data gradient as a 1x1 conv on the transposed weight in the encoder's arithmetic.  An fp16
+    encoder runs its data gradients on the bf16x3 kernels (fp32 range: un-scaled gradients cannot underflow), like the
+    released IR-50 units.  No gradient reaches the convolutions (never released)."""
+
+    @staticmethod
+    def forward(ctx, e, vgg, depth, w0, b0, w2, b2, w4, b4):
+        out, acts = vgg._embed(e)
+        ctx.acts = [None] * (3 - depth) + acts[3 - depth:]      # the inputs of the released layers only
+        ctx.weights = (w2.detach() if depth >= 3 else None, w4.detach() if depth >= 2 else None)   # data gradients
+        ctx.prec, ctx.depth = vgg.precision, depth
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        prec, depth, acts = ctx.prec, ctx.depth, ctx.acts
+        w_of = {2: ctx.weights[0], 4: ctx.weights[1]}
+        dprec = "bf16x3" if prec == "fp16" else prec
+        grads = {}
+        da = dout.contiguous()
+        n = da.shape[0]
+        for j, (layer, k) in enumerate(((4, 2), (2, 1), (0, 0))[:depth]):
+            x_in = acts[k]
+            mask = _rows2d(acts[k + 1]) if layer != 4 else None
+            r = ops.fc_bwd(da, mask, out_split=prec != "fp32", out_f32=prec == "fp32")
+            cout, cin = da.shape[1], x_in.shape[-1]
+            if prec == "fp32":
+                dw = ops.conv2d_wgrad(r["f32"].view(n, 1, 1, cout), x_in.view(n, 1, 1, cin), 1, 1)
+            else:
+                xs = x_in if isinstance(x_in, ops.Split) else ops.split_bf16(ops.from_n16(x_in))   # exact for bf16 / fp16
+                dw = ops.conv2d_wgrad(r["split"].view(n, 1, 1, cout), xs.view(n, 1, 1, cin), 1, 1)
+            grads[layer] = (dw.view(cout, cin), r["db"])
+            if j + 1 < depth:   # the data gradient feeds the next released layer down
+                wt = ops.pack_conv_weight(w_of[layer].view(cout, cin, 1, 1).contiguous(), transpose=True)   # [cin, cout]
+                split = max(1, min(8, cout // 512))
+                if dprec == "fp32":
+                    da = ops.linear(r["f32"], wt, split_k=split)
+                elif dprec == "bf16x3":
+                    da = ops.conv2d_b3(r["split"].view(n, 1, 1, cout), ops.split_bf16(wt), 1, 1, split_k=split, out_f32=True,
+                                       out_split=False)["y"].view(n, cin)
+                else:   # bf16 storage: the hi plane IS bf16(dz) (round-to-nearest-even, like ops.to_n16)
+                    da = ops.conv2d_n16(r["split"].hi.view(n, 1, 1, cout), ops.to_n16(wt, torch.bfloat16), 1, 1, split_k=split,
+                                        out_f32=True, out_n16=False)["y"].view(n, cin)
+            del r
+        g0, g2, g4 = grads.get(0, (None, None)), grads.get(2, (None, None)), grads.get(4, (None, None))
+        return None, None, None, g0[0], g0[1], g2[0], g2[1], g4[0], g4[1]
+
+
 class VGGish(nn.Module):
     def __init__(self):
         super().__init__()
@@ -96,18 +164,53 @@ class VGGish(nn.Module):
             self._packed = packed
         return new
 
+    def _release_depth(self):
+        """How many embedding layers train (base/parameter_control.py:57-58,85-103 releases parameters 16-17 =
+        ``embeddings.4``, then 14-15 = ``embeddings.2``, then 12-13 = ``embeddings.0``): 0 (frozen, or no autograd), 1, 2 or 3.
+        Anything the reference cannot produce fails loudly here, before any launch."""
+        if not torch.is_grad_enabled():
+            return 0
+        if any(p.requires_grad for p in self.features.parameters()):
+            raise NotImplementedError("the VGGish convolutions have no backward on the HIP path (the reference releases "
+                                      "only the embedding layers, parameters 12..17 of the audio encoder)")
+        flags = []
+        for i in (0, 2, 4):
+            f = [p.requires_grad for p in self.embeddings[i].parameters()]
+            if any(f) and not all(f):
+                raise NotImplementedError("release whole embedding layers (weight and bias) or nothing")
+            flags.append(all(f))
+        first = len(flags)
+        while first > 0 and flags[first - 1]:
+            first -= 1
+        if any(flags[:first]):
+            raise NotImplementedError("released embedding layers must form a suffix of the stack (the reference releases "
+                                      "from the top: embeddings.4, then embeddings.2, then embeddings.0)")
+        return len(flags) - first
+
     def forward(self, x, fs=None):
         """x: [n,96,64] log-mel examples (tensor or numpy, like the reference) -> [n,128]."""
+        depth = self._release_depth()
+        if self.precision not in ("bf16x3", "bf16", "fp16", "fp32"):
+            raise ValueError(f"unknown precision {self.precision!r}")
         dev = self.features[0].weight.device
         x = torch.as_tensor(x).to(dev).float().contiguous()
+        with torch.no_grad():   # the conv trunk is never released
+            e = self._trunk(x)
+        if depth == 0:
+            return self._embed(e)[0]
+        fc = self.embeddings
+        return _ReleasedEmbeddings.apply(e, self, depth, fc[0].weight, fc[0].bias, fc[2].weight, fc[2].bias, fc[4].weight,
+                                         fc[4].bias)
+
+    def _trunk(self, x):
+        """The six convs and four max-pools: the flattened (H, W, C) feature [n, 12288] as the precision mode carries it
+        into the embedding stack (fp32, ``Split`` or one 16-bit plane)."""
         packed = self._pack()
         n = x.shape[0]
         if self.precision == "bf16x3":
-            return self._forward_b3(x, packed, n)
+            return self._trunk_b3(x, packed, n)
         if self.precision in ("bf16", "fp16"):
-            return self._forward_n16(x, n, torch.bfloat16 if self.precision == "bf16" else torch.float16)
-        if self.precision != "fp32":
-            raise ValueError(f"unknown precision {self.precision!r}")
+            return self._trunk_n16(x, n, torch.bfloat16 if self.precision == "bf16" else torch.float16)
         packed = packed["convs"]
         y = x.view(n, 1, x.shape[1], x.shape[2])  # NCHW with C = 1
         for j, i in enumerate(CONV_IDX):
@@ -115,17 +218,40 @@ class VGGish(nn.Module):
                            x_nchw=(j == 0))
             if i in POOL_AFTER:
                 y = ops.maxpool2x2_nhwc(y)
-        e = y.view(n, -1)  # (H, W, C) flatten == the reference's transposes + view
-        fc = self.embeddings
-        split = max(1, min(8, 512 // max(1, (n + 127) // 128 * 32)))
-        e = ops.linear(e, fc[0].weight.detach(), bias=fc[0].bias.detach(), act=ops.ACT_RELU, split_k=split)
-        e = ops.linear(e, fc[2].weight.detach(), bias=fc[2].bias.detach(), act=ops.ACT_RELU, split_k=split)
-        return ops.linear(e, fc[4].weight.detach(), bias=fc[4].bias.detach(), split_k=split)
+        return y.view(n, -1)  # (H, W, C) flatten == the reference's transposes + view
 
-    def _forward_b3(self, x, packed, n):
+    def _embed(self, e):
+        """The three embedding layers on the trunk's output.  Returns (output [n, 128], [e0, e1, e2]): the inputs of
+        ``embeddings.0`` / ``.2`` / ``.4`` as the forward made them (e1 / e2 are also the post-ReLU outputs of .0 / .2)."""
+        fc = self.embeddings
+        if self.precision == "fp32":
+            n = e.shape[0]
+            split = _fc_split_k(n)
+            e1 = ops.linear(e, fc[0].weight.detach(), bias=fc[0].bias.detach(), act=ops.ACT_RELU, split_k=split)
+            e2 = ops.linear(e1, fc[2].weight.detach(), bias=fc[2].bias.detach(), act=ops.ACT_RELU, split_k=split)
+            return ops.linear(e2, fc[4].weight.detach(), bias=fc[4].bias.detach(), split_k=split), [e, e1, e2]
+        if self.precision == "bf16x3":
+            packed = self._pack()
+            n = e.shape[0]
+            split = _fc_split_k(n)
+            e1 = ops.conv2d_b3(e, packed["fc_b3"][0], 1, 1, bias=fc[0].bias.detach(), act1=ops.ACT_RELU, split_k=split)["split"]
+            e2 = ops.conv2d_b3(e1, packed["fc_b3"][1], 1, 1, bias=fc[2].bias.detach(), act1=ops.ACT_RELU, split_k=split)["split"]
+            out = ops.conv2d_b3(e2, packed["fc_b3"][2], 1, 1, bias=fc[4].bias.detach(), split_k=split, out_f32=True,
+                                out_split=False)["y"].view(n, -1)
+            return out, [e, e1, e2]
+        packed = self._pack_n16(e.dtype)
+        n = e.shape[0]
+        split = _fc_split_k(n)
+        e1 = ops.conv2d_n16(e, packed["fc_n16"][0], 1, 1, bias=fc[0].bias.detach(), act1=ops.ACT_RELU, split_k=split)["n16"]
+        e2 = ops.conv2d_n16(e1, packed["fc_n16"][1], 1, 1, bias=fc[2].bias.detach(), act1=ops.ACT_RELU, split_k=split)["n16"]
+        out = ops.conv2d_n16(e2, packed["fc_n16"][2], 1, 1, bias=fc[4].bias.detach(), split_k=split, out_f32=True,
+                             out_n16=False)["y"].view(n, -1)
+        return out, [e, e1, e2]
+
+    def _trunk_b3(self, x, packed, n):
         """Layer 1 (Cin = 1) on the fp32 small-Cin kernel, everything else on the bf16x3 kernels.  Max-pooling
         needs the fp32 value, so a conv that feeds a pool writes fp32 and the pooled map is re-split."""
-        feats, fc = self.features, self.embeddings
+        feats = self.features
         y = ops.conv2d(x.view(n, 1, x.shape[1], x.shape[2]), packed["convs"][0], 3, 3, pad=(1, 1),
                        bias=feats[0].bias.detach(), act1=ops.ACT_RELU, x_nchw=True)
         cur = ops.split_bf16(ops.maxpool2x2_nhwc(y))
@@ -135,18 +261,13 @@ class VGGish(nn.Module):
                               out_f32=pooled, out_split=not pooled)
             cur = ops.split_bf16(ops.maxpool2x2_nhwc(r["y"])) if pooled else r["split"]
         k = cur.hi.numel() // n
-        e = cur.view(n, 1, 1, k)  # (H, W, C) flatten == the reference's transposes + view
-        split = max(1, min(8, 512 // max(1, (n + 127) // 128 * 32)))
-        e = ops.conv2d_b3(e, packed["fc_b3"][0], 1, 1, bias=fc[0].bias.detach(), act1=ops.ACT_RELU, split_k=split)["split"]
-        e = ops.conv2d_b3(e, packed["fc_b3"][1], 1, 1, bias=fc[2].bias.detach(), act1=ops.ACT_RELU, split_k=split)["split"]
-        return ops.conv2d_b3(e, packed["fc_b3"][2], 1, 1, bias=fc[4].bias.detach(), split_k=split, out_f32=True,
-                             out_split=False)["y"].view(n, -1)
+        return cur.view(n, 1, 1, k)  # (H, W, C) flatten == the reference's transposes + view
 
-    def _forward_n16(self, x, n, dtype):
+    def _trunk_n16(self, x, n, dtype):
         """Narrow storage: layer 1 (Cin = 1) on the fp32 small-Cin kernel, convs 2-6 and the FCs on the narrow kernels.  A
         conv that feeds a max-pool writes fp32 (pooling wants the un-rounded value) and the pooled map is rounded once."""
         packed = self._pack_n16(dtype)
-        feats, fc = self.features, self.embeddings
+        feats = self.features
         y = ops.conv2d(x.view(n, 1, x.shape[1], x.shape[2]), packed["convs"][0], 3, 3, pad=(1, 1),
                        bias=feats[0].bias.detach(), act1=ops.ACT_RELU, x_nchw=True)
         cur = ops.to_n16(ops.maxpool2x2_nhwc(y), dtype)
@@ -156,12 +277,7 @@ class VGGish(nn.Module):
                                out_f32=pooled, out_n16=not pooled)
             cur = ops.to_n16(ops.maxpool2x2_nhwc(r["y"]), dtype) if pooled else r["n16"]
         k = cur.numel() // n
-        e = cur.view(n, 1, 1, k)
-        split = max(1, min(8, 512 // max(1, (n + 127) // 128 * 32)))
-        e = ops.conv2d_n16(e, packed["fc_n16"][0], 1, 1, bias=fc[0].bias.detach(), act1=ops.ACT_RELU, split_k=split)["n16"]
-        e = ops.conv2d_n16(e, packed["fc_n16"][1], 1, 1, bias=fc[2].bias.detach(), act1=ops.ACT_RELU, split_k=split)["n16"]
-        return ops.conv2d_n16(e, packed["fc_n16"][2], 1, 1, bias=fc[4].bias.detach(), split_k=split, out_f32=True,
-                              out_n16=False)["y"].view(n, -1)
+        return cur.view(n, 1, 1, k)
 
     # ---------------------------------------------------------------- front end
     def wav_int16_to_examples(self, pcm_int16, sample_rate, window_sec=0.96, hop_sec=0.96):

@@ -352,9 +352,11 @@ class _TailModel(nn.Module):
                 X[m] = rows.detach().view(bsz, length, -1).unsqueeze(1)
             elif m == "logmel":
                 bsz, height, length, width = x.shape
-                with torch.no_grad():
+                # frozen VGGish: no autograd graph; after an audio release (embedding layers) the graph reaches them
+                released = any(p.requires_grad for p in self.spatial["audio"].parameters())
+                with torch.set_grad_enabled(released and torch.is_grad_enabled()):
                     rows = self.spatial["audio"](x.permute(0, 2, 3, 1).contiguous().view(-1, width, height))
-                X[m] = rows.view(bsz, length, -1).unsqueeze(1)
+                X[m] = rows.detach().view(bsz, length, -1).unsqueeze(1)
             else:
                 bsz, length = x.shape[0], x.shape[2]
                 rows = x.reshape(bsz * length, x.shape[-1])

@@ -279,7 +279,9 @@ class LFAN(nn.Module):
             elif m == "logmel":
                 # model.py:500-508: [B, 64 mel bins, L, 96 frames] -> one 96 x 64 example per clip frame -> VGGish
                 bsz, height, length, width = x.shape
-                with torch.no_grad():
+                # frozen VGGish: no autograd graph; after an audio release (embedding layers) the graph reaches them
+                released = any(p.requires_grad for p in self.spatial["audio"].parameters())
+                with torch.set_grad_enabled(released and torch.is_grad_enabled()):
                     rows_in[m] = self.spatial["audio"](x.permute(0, 2, 3, 1).contiguous().view(-1, width, height))
             else:
                 bsz, length = x.shape[0], x.shape[2]

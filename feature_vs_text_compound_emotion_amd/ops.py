@@ -1035,6 +1035,50 @@ def act_mask_bwd(dy, y, mask=None, slope=LEAKY_SLOPE):
     return dz
 
 
+def fc_bwd(da, act=None, out_split=True, out_f32=False):
+    """The elementwise part of a fully-connected layer's backward in ONE pass: dz = da * (act > 0) (``act`` = the layer's
+    saved post-ReLU output [R, C] -- fp32, ``Split`` or one bf16 / fp16 plane; None: no mask, the output layer), stored as a
+    ``Split`` ('split') and / or fp32 ('f32'), and the bias gradient 'db' = column sums of dz (fixed order, bit-identical
+    from run to run).  ``da`` may be a column slice of a wider row-major buffer.  Returns a dict."""
+    if not (da.is_cuda and da.dtype == torch.float32 and da.dim() == 2 and da.stride(1) == 1):
+        raise ValueError("da: expected a 2-D float32 GPU tensor with unit column stride")
+    r, c = da.shape
+    ld = da.stride(0) if r > 1 else c
+    if c % 4:
+        raise ValueError(f"fc_bwd: C = {c} is not a multiple of 4")
+    if not (out_split or out_f32):
+        raise ValueError("fc_bwd: ask for the split planes, the fp32 dz, or both")
+    a = a_lo = None
+    kind = _lib.FC_ACT_NONE
+    if isinstance(act, Split):
+        _dev_bf16(act.hi, "act.hi")
+        _dev_bf16(act.lo, "act.lo")
+        a, a_lo, kind = act.hi, act.lo, _lib.FC_ACT_SPLIT
+    elif act is not None:
+        if act.dtype == torch.float32:
+            _dev_f32(act, "act")
+            kind = _lib.FC_ACT_F32
+        else:
+            _dev_n16(act, "act")
+            kind = _lib.FC_ACT_BF16 if act.dtype == torch.bfloat16 else _lib.FC_ACT_F16
+        a = act
+    if a is not None and a.numel() != r * c:
+        raise ValueError(f"act: expected {r * c} elements (the shape of da), got {tuple(a.shape)}")
+    res = {"db": torch.empty((c,), device=da.device, dtype=torch.float32)}
+    if out_split:
+        res["split"] = Split.empty((r, c), da.device)
+    if out_f32:
+        res["f32"] = torch.empty((r, c), device=da.device, dtype=torch.float32)
+    lib = _lib.load()
+    nbytes = lib.cer_fc_bwd_workspace_bytes(r, c)
+    ws = torch.empty((nbytes // 4,), device=da.device, dtype=torch.float32) if nbytes else None
+    sp = res.get("split")
+    check(lib.cer_fc_bwd_elem(ptr(da), ld, ptr(a), ptr(a_lo), kind, ptr(sp.hi) if sp is not None else None,
+                              ptr(sp.lo) if sp is not None else None, ptr(res.get("f32")), ptr(res["db"]), r, c, ptr(ws), nbytes,
+                              current_stream()), "cer_fc_bwd_elem")
+    return res
+
+
 def tblock_tail_bwd(dout, out, a2, mask2=None, slope=LEAKY_SLOPE):
     _dev_f32(dout, "dout")
     for t, n in ((out, "out"), (a2, "a2"), (mask2, "mask2")):

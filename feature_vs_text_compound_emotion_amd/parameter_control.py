@@ -4,8 +4,12 @@ The reference keeps two stacks of PARAMETER-INDEX groups per encoder and, each t
 ``requires_grad`` of ``list(model[modal].parameters())[i]`` for every index of the group, and rebuilds the optimiser
 (``trainer.init_optimizer_and_scheduler``).  For the visual encoder the groups are (4..9) = the output layer, (163..186) =
 stage 4 and (142..162) = the second half of stage 3 -- always "output layer + a suffix of whole units", which is what
-``visual_backbone.IR50`` can train (``_ReleasedHead`` / ``_ReleasedUnit``).  The audio stack of the reference indexes
-VGGish parameters 12..17 (its three FC layers); the VGGish mirror has no backward, so releasing it raises.
+``visual_backbone.IR50`` can train (``_ReleasedHead`` / ``_ReleasedUnit``).  The audio stack indexes VGGish parameters
+(16, 17) = ``embeddings.4``, then (14, 15) = ``embeddings.2``, then (12, 13) = ``embeddings.0`` -- its three embedding layers,
+top first, which ``audio_backbone._ReleasedEmbeddings`` trains.
+
+The reference's ``release_param`` defaults to BOTH encoders (``modalities=['visual', 'audio']``); here the default stays
+``("visual",)`` so that existing callers keep their behaviour -- pass ``modalities=("visual", "audio")`` to reproduce it.
 """
 from operator import itemgetter
 
@@ -43,7 +47,9 @@ class ResnetParamControl:
         return self.trainer.optimizer.param_groups[0]["lr"]
 
     def release_param(self, model, epoch=0, modalities=("visual",)):
-        """``model`` is ``LFAN.spatial`` (a mapping with key 'visual').  Returns the parameters that were released."""
+        """``model`` is ``LFAN.spatial`` (a mapping with keys 'visual' and / or 'audio').  Pops one group per listed encoder
+        that the model has and releases it; returns the parameters that were released.  The reference's default is
+        ``modalities=['visual', 'audio']`` (parameter_control.py:85); pass both to reproduce it."""
         released = []
         if not self.gradual_release:
             return released
@@ -54,8 +60,6 @@ class ResnetParamControl:
         for modal in modalities:
             if modal not in model:
                 continue
-            if modal != "visual":
-                raise NotImplementedError("only the visual encoder has a backward on the HIP path (VGGish is frozen)")
             if not self.module_stack[modal]:
                 continue
             indices = self.get_param_group(modal)

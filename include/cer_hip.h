@@ -562,6 +562,18 @@ int cer_softmax_gate_fwd(const float *z, const float *c, float *out, float *prob
 int cer_softmax_gate_bwd(const float *dout, const float *prob, const float *c, float *dz, float *dc, int R, int C,
                          void *stream);
 
+/* Elementwise part of a fully-connected layer's backward, one pass over dense-or-pitched rows (the released VGGish
+ * embedding layers): dz = da * (a > 0) with a the SAVED post-ReLU output of the layer ([R, C], dense) given as
+ * a_kind = CER_FC_ACT_F32 (float), _SPLIT (a = hi plane, a_lo = lo plane), _BF16 / _F16 (one plane); CER_FC_ACT_NONE with
+ * a = a_lo = NULL applies no mask (the output layer).  dz goes to the split planes dz_hi / dz_lo (bf16x3 operand; both or
+ * neither) and / or to fp32 dz (dense [R, C]); db[c] = sum_r dz[r][c], per-slab partials folded in slab order (no atomics:
+ * bit-identical from run to run).  C % 4 == 0, da_ld >= C, a / outputs / workspace 16-byte aligned;
+ * workspace: cer_fc_bwd_workspace_bytes(R, C). */
+enum cer_fc_act_kind { CER_FC_ACT_NONE = 0, CER_FC_ACT_F32 = 1, CER_FC_ACT_SPLIT = 2, CER_FC_ACT_BF16 = 3, CER_FC_ACT_F16 = 4 };
+size_t cer_fc_bwd_workspace_bytes(int R, int C);
+int cer_fc_bwd_elem(const float *da, int da_ld, const void *a, const uint16_t *a_lo, int a_kind, uint16_t *dz_hi,
+                    uint16_t *dz_lo, float *dz, float *db, int R, int C, void *workspace, size_t workspace_bytes, void *stream);
+
 /* y[r, 0:C] (pitch y_ld) = x[r, 0:C] (pitch x_ld). */
 int cer_copy_cols(const float *x, int x_ld, float *y, int y_ld, int R, int C, void *stream);
 
