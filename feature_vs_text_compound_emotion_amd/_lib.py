@@ -80,11 +80,8 @@ _SIGNATURES = {
     "cer_prelu_bwd": (c_int, [_P, _P, _P, _P, _P, c_size_t, c_int, _P]),
     "cer_prelu_split": (c_int, [_P, _P, _P, _P, c_size_t, c_int, _P]),
     "cer_prelu_bwd_split": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_size_t, c_int, _P]),
-    "cer_bn_rows_bwd_split": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
-    "cer_bn_rows_bwd_add": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
     "cer_col_sum_workspace_bytes": (c_size_t, [c_int, c_int]),
     "cer_col_sum": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
-    "cer_bn_bwd_sums": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
     "cer_act_mask_bwd": (c_int, [_P, _P, _P, _P, c_size_t, c_float, _P]),
     "cer_fc_bwd_workspace_bytes": (c_size_t, [c_int, c_int]),
     "cer_fc_bwd_elem": (c_int, [_P, c_int, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
@@ -92,17 +89,14 @@ _SIGNATURES = {
     "cer_bn_rows_fwd_workspace_bytes": (c_size_t, [c_int, c_int]),
     "cer_bn_rows_fwd": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float,
                                 c_float, _P, c_size_t, _P]),
-    "cer_bn_rows_bwd": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t,
-                                _P]),
     "cer_bn_rows_moments": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "cer_bn_rows_merge": (c_int, [_P, c_int, c_int, c_float, c_float, _P, _P, _P, _P, _P]),
     "cer_bn_rows_apply": (c_int, [_P, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "cer_bn_rows_bwd_sums": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, c_int, c_int, _P, c_size_t, _P]),
-    "cer_bn_rows_bwd_apply": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_double, _P, c_int, c_int, _P]),
+    "cer_bn_rows_bwd_apply": (c_int, [_P, c_int, _P, c_int, _P, _P, _P, _P, c_double, c_int, _P, _P, _P, _P, c_int, c_int,
+                                      _P]),
     "cer_bn_rows_moments_large_workspace_bytes": (c_size_t, [c_int, c_int]),
     "cer_bn_rows_moments_large": (c_int, [_P, c_int, c_int, _P, _P, c_size_t, _P]),
-    "cer_bn_rows_bwd_apply_split": (c_int, [_P, _P, _P, _P, _P, _P, c_double, _P, _P, c_int, c_int, _P]),
-    "cer_bn_rows_bwd_apply_add": (c_int, [_P, _P, _P, _P, _P, _P, c_double, _P, _P, c_int, c_int, _P]),
     "cer_lfan_attn_fwd": (c_int, [POINTER(_P), _P, _P, c_int, c_int, c_int, c_int, _P]),
     "cer_lfan_attn_bwd": (c_int, [POINTER(_P), _P, _P, POINTER(_P), c_int, c_int, c_int, c_int, _P]),
     "cer_layernorm_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, c_float, _P]),

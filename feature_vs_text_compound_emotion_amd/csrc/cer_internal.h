@@ -27,3 +27,9 @@ static inline unsigned cer_blocks(size_t n, unsigned per_block) {
         (void)hipGetLastError();        \
         hipLaunchKernelGGL(__VA_ARGS__); \
     } while (0)
+
+// The float4 apply passes of cer_bn_rows_bwd_apply (unit_passes.hip): dx as a split tensor (dx_hi != NULL), or fp32 with an
+// optional addend; dense rows, C % 4 == 0, arguments checked by the caller.
+int bn_rows_bwd_apply4(const float *dy, const float *x, const float *save_mean, const float *save_invstd, const float *w,
+                       const float *sums, float inv_count, const float *add, float *dx, uint16_t *dx_hi, uint16_t *dx_lo, int R,
+                       int C, hipStream_t stream);

@@ -994,23 +994,6 @@ extern "C" int cer_bn_rows_fwd(const float *x, int x_ld, const float *w, const f
     return CER_OK;
 }
 
-extern "C" int cer_bn_rows_bwd(const float *dy, int dy_ld, const float *x, int x_ld, const float *save_mean,
-                               const float *save_invstd, const float *w, float *dx, float *dw, float *db, int R,
-                               int C, int train, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!dy || !x || !save_mean || !save_invstd || !w || !dx || !dw || !db || R <= 0 || C <= 0)
-        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd: bad argument");
-    if (!(dy_ld == C && x_ld == C && col_sum_pair(dy, x, save_mean, save_invstd, db, dw, R, C, workspace, workspace_bytes, stream))) {
-        int rc = cer_col_sum(dy, dy_ld, nullptr, 0, nullptr, nullptr, db, R, C, workspace, workspace_bytes, stream);
-        if (rc) return rc;
-        rc = cer_col_sum(dy, dy_ld, x, x_ld, save_mean, save_invstd, dw, R, C, workspace, workspace_bytes, stream);
-        if (rc) return rc;
-    }
-    CER_LAUNCH(bn_rows_bwd_kernel, dim3(cer_blocks((size_t)R * C, 256)), dim3(256), 0, ST, dy, dy_ld, x, x_ld,
-                       save_mean, save_invstd, w, (const float *)db, (const float *)dw, dx, R, C, train, (float)R);
-    CER_HIP_CHECK(hipGetLastError());
-    return CER_OK;
-}
-
 extern "C" int cer_bn_rows_moments(const float *x, int x_ld, int R, int C, double *moments, void *stream) {
     if (!x || !moments || R <= 0 || C <= 0 || x_ld < C) return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_moments: bad argument");
     CER_LAUNCH(bn_rows_moments_kernel, dim3((C + 31) / 32), dim3(256), 0, ST, x, x_ld, R, C, moments);
@@ -1072,7 +1055,7 @@ extern "C" int cer_bn_rows_bwd_sums(const float *dy, int dy_ld, const float *x, 
                                     void *stream) {
     if (!dy || !x || !save_mean || !save_invstd || !sums || R <= 0 || C <= 0 || dy_ld < C || x_ld < C)
         return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd_sums: bad argument");
-    float *db = sums, *dw = sums + C;   // the same reductions, in the same order, as cer_bn_rows_bwd
+    float *db = sums, *dw = sums + C;
     if (!(dy_ld == C && x_ld == C && col_sum_pair(dy, x, save_mean, save_invstd, db, dw, R, C, workspace, workspace_bytes, stream))) {
         int rc = cer_col_sum(dy, dy_ld, nullptr, 0, nullptr, nullptr, db, R, C, workspace, workspace_bytes, stream);
         if (rc) return rc;
@@ -1084,13 +1067,20 @@ extern "C" int cer_bn_rows_bwd_sums(const float *dy, int dy_ld, const float *x, 
 }
 
 extern "C" int cer_bn_rows_bwd_apply(const float *dy, int dy_ld, const float *x, int x_ld, const float *save_mean,
-                                     const float *save_invstd, const float *w, const float *sums, double count, float *dx, int R,
-                                     int C, void *stream) {
-    if (!dy || !x || !save_mean || !save_invstd || !w || !sums || !dx || R <= 0 || C <= 0 || dy_ld < C || x_ld < C ||
-        !(count > 0))
+                                     const float *save_invstd, const float *w, const float *sums, double count, int train,
+                                     const float *add, float *dx, uint16_t *dx_hi, uint16_t *dx_lo, int R, int C, void *stream) {
+    const bool split = dx_hi != nullptr;
+    if (!dy || !x || !save_mean || !save_invstd || !w || !sums || (split ? !dx_lo || add : !dx) || R <= 0 || C <= 0 ||
+        dy_ld < C || x_ld < C || !(count > 0))
         return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd_apply: bad argument");
+    if (split || add) {   // the released encoder units' float4 passes: dx as a split tensor, or fp32 with the addend summed in
+        if (!train || dy_ld != C || x_ld != C || (C & 3) || !aligned16(dy) || !aligned16(x) || !aligned16(add))
+            return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd_apply: the split / addend forms need train mode and dense "
+                                                      "rows, C %% 4 == 0, 16-byte aligned");
+        return bn_rows_bwd_apply4(dy, x, save_mean, save_invstd, w, sums, 1.0f / (float)count, add, dx, dx_hi, dx_lo, R, C, ST);
+    }
     CER_LAUNCH(bn_rows_bwd_kernel, dim3(cer_blocks((size_t)R * C, 256)), dim3(256), 0, ST, dy, dy_ld, x, x_ld, save_mean,
-               save_invstd, w, sums, sums + C, dx, R, C, 1, (float)count);
+               save_invstd, w, sums, sums + C, dx, R, C, train, (float)count);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }
@@ -1183,16 +1173,3 @@ extern "C" int cer_copy_cols(const float *x, int x_ld, float *y, int y_ld, int R
     return CER_OK;
 }
 
-
-// (used by cer_bn_rows_bwd_split in conv_b3.hip) db = sum dy, dw = sum dy * x_hat in one pass when the shape allows, else two
-extern "C" int cer_bn_bwd_sums(const float *dy, const float *x, const float *save_mean, const float *save_invstd, float *db, float *dw,
-                               int R, int C, void *workspace, size_t workspace_bytes, void *stream) {
-    if (!dy || !x || !save_mean || !save_invstd || !db || !dw || R <= 0 || C <= 0) return cer_set_error(CER_ERR_INVALID_ARG, "bn_bwd_sums: bad argument");
-    if (col_sum_pair(dy, x, save_mean, save_invstd, db, dw, R, C, workspace, workspace_bytes, stream)) {
-        CER_HIP_CHECK(hipGetLastError());
-        return CER_OK;
-    }
-    int rc = cer_col_sum(dy, C, nullptr, 0, nullptr, nullptr, db, R, C, workspace, workspace_bytes, stream);
-    if (rc) return rc;
-    return cer_col_sum(dy, C, x, C, save_mean, save_invstd, dw, R, C, workspace, workspace_bytes, stream);
-}

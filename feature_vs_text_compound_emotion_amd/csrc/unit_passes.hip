@@ -114,62 +114,19 @@ extern "C" int cer_prelu_bwd_split(const float *dy, const float *x, const float 
     return CER_OK;
 }
 
-extern "C" int cer_bn_rows_bwd_split(const float *dy, const float *x, const float *save_mean, const float *save_invstd,
-                                     const float *w, uint16_t *dx_hi, uint16_t *dx_lo, float *dw, float *db, int R, int C,
-                                     void *workspace, size_t workspace_bytes, void *stream) {
-    if (!dy || !x || !save_mean || !save_invstd || !w || !dx_hi || !dx_lo || !dw || !db || R <= 0 || C <= 0 || (C & 3))
-        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd_split: bad argument (dense rows, C % 4 == 0)");
-    const int rc = cer_bn_bwd_sums(dy, x, save_mean, save_invstd, db, dw, R, C, workspace, workspace_bytes, stream);
-    if (rc) return rc;
+// cer_bn_rows_bwd_apply (tail_kernels.hip) has checked the arguments
+int bn_rows_bwd_apply4(const float *dy, const float *x, const float *save_mean, const float *save_invstd, const float *w,
+                       const float *sums, float inv_count, const float *add, float *dx, uint16_t *dx_hi, uint16_t *dx_lo, int R,
+                       int C, hipStream_t stream) {
     const size_t n4 = (size_t)R * (C / 4);
-    CER_LAUNCH(bn_rows_bwd_split_kernel, dim3(cer_blocks(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4 *)dy,
-               (const float4 *)x, save_mean, save_invstd, w, (const float *)db, (const float *)dw, (ushort4 *)dx_hi, (ushort4 *)dx_lo, n4,
-               C / 4, 1.0f / (float)R);
-    CER_HIP_CHECK(hipGetLastError());
-    return CER_OK;
-}
-
-extern "C" int cer_bn_rows_bwd_add(const float *dy, const float *x, const float *save_mean, const float *save_invstd, const float *w,
-                                   const float *add, float *dx, float *dw, float *db, int R, int C, void *workspace,
-                                   size_t workspace_bytes, void *stream) {
-    if (!dy || !x || !save_mean || !save_invstd || !w || !dx || !dw || !db || R <= 0 || C <= 0 || (C & 3))
-        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd_add: bad argument (dense rows, C % 4 == 0)");
-    const int rc = cer_bn_bwd_sums(dy, x, save_mean, save_invstd, db, dw, R, C, workspace, workspace_bytes, stream);
-    if (rc) return rc;
-    const size_t n4 = (size_t)R * (C / 4);
-    CER_LAUNCH(bn_rows_bwd_add_kernel, dim3(cer_blocks(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4 *)dy,
-               (const float4 *)x, save_mean, save_invstd, w, (const float *)db, (const float *)dw, (const float4 *)add, (float4 *)dx, n4,
-               C / 4, 1.0f / (float)R);
-    CER_HIP_CHECK(hipGetLastError());
-    return CER_OK;
-}
-
-// The apply passes of cer_bn_rows_bwd_split / cer_bn_rows_bwd_add from GIVEN sums [2][C] (sum dy | sum dy * x_hat) over
-// ``count`` rows -- a synchronised BatchNorm's backward, where the sums are all-reduced over the ranks and count is the global
-// batch's rows.  The same kernels with the same 1.0f / (float)count: with the local sums and count == R they write the bits of
-// the unsynchronised entry points.
-extern "C" int cer_bn_rows_bwd_apply_split(const float *dy, const float *x, const float *save_mean, const float *save_invstd,
-                                           const float *w, const float *sums, double count, uint16_t *dx_hi, uint16_t *dx_lo, int R,
-                                           int C, void *stream) {
-    if (!dy || !x || !save_mean || !save_invstd || !w || !sums || !dx_hi || !dx_lo || R <= 0 || C <= 0 || (C & 3) || !(count > 0))
-        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd_apply_split: bad argument (dense rows, C % 4 == 0, count > 0)");
-    const size_t n4 = (size_t)R * (C / 4);
-    CER_LAUNCH(bn_rows_bwd_split_kernel, dim3(cer_blocks(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4 *)dy,
-               (const float4 *)x, save_mean, save_invstd, w, sums, sums + C, (ushort4 *)dx_hi, (ushort4 *)dx_lo, n4, C / 4,
-               1.0f / (float)count);
-    CER_HIP_CHECK(hipGetLastError());
-    return CER_OK;
-}
-
-extern "C" int cer_bn_rows_bwd_apply_add(const float *dy, const float *x, const float *save_mean, const float *save_invstd,
-                                         const float *w, const float *sums, double count, const float *add, float *dx, int R, int C,
-                                         void *stream) {
-    if (!dy || !x || !save_mean || !save_invstd || !w || !sums || !dx || R <= 0 || C <= 0 || (C & 3) || !(count > 0))
-        return cer_set_error(CER_ERR_INVALID_ARG, "bn_rows_bwd_apply_add: bad argument (dense rows, C % 4 == 0, count > 0)");
-    const size_t n4 = (size_t)R * (C / 4);
-    CER_LAUNCH(bn_rows_bwd_add_kernel, dim3(cer_blocks(n4, 256)), dim3(256), 0, (hipStream_t)stream, (const float4 *)dy,
-               (const float4 *)x, save_mean, save_invstd, w, sums, sums + C, (const float4 *)add, (float4 *)dx, n4, C / 4,
-               1.0f / (float)count);
+    if (dx_hi)
+        CER_LAUNCH(bn_rows_bwd_split_kernel, dim3(cer_blocks(n4, 256)), dim3(256), 0, stream, (const float4 *)dy,
+                   (const float4 *)x, save_mean, save_invstd, w, sums, sums + C, (ushort4 *)dx_hi, (ushort4 *)dx_lo, n4, C / 4,
+                   inv_count);
+    else
+        CER_LAUNCH(bn_rows_bwd_add_kernel, dim3(cer_blocks(n4, 256)), dim3(256), 0, stream, (const float4 *)dy,
+                   (const float4 *)x, save_mean, save_invstd, w, sums, sums + C, (const float4 *)add, (float4 *)dx, n4, C / 4,
+                   inv_count);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }

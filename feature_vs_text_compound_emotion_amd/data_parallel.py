@@ -24,6 +24,9 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import ops
+from .batchnorm import BatchNormLocal
+
 
 def init_process_group_from_env(backend=None, single_rank_group=False):
     """RANK / WORLD_SIZE / LOCAL_RANK / MASTER_* come from the launcher (torch.distributed.run).  ``single_rank_group``:
@@ -43,12 +46,12 @@ def init_process_group_from_env(backend=None, single_rank_group=False):
     return rank, world, local
 
 
-class BatchNormSync:
+class BatchNormSync(BatchNormLocal):
     """Synchronised batch statistics for the train-mode BatchNorms of the HIP modules (``IR50``, ``LFAN``, ``CAN`` / ``JMT``),
-    which call the methods below in place of their one-call BatchNorm ops while one of these is attached to them as
-    ``bn_sync``.  The collectives run on a process group of their own, so they never interleave with the gradient slices
-    that the overlapped exchange issues from autograd hooks on the default group; with RCCL they are stream-ordered (no
-    host synchronisation).
+    which call it in place of ``batchnorm.LOCAL`` while it is attached to them as ``bn_sync``: it overrides the statistics, the
+    encoder finalize, the backward's sums (``global_sums``) and ``agree_min``.  The collectives run on a process group of
+    their own, so they never interleave with the gradient slices that the overlapped exchange issues from autograd hooks on
+    the default group; with RCCL they are stream-ordered (no host synchronisation).
 
     * encoder BatchNorm2d: float64 (sum, sum of squares) per channel, all-reduced, finalized over ``world x`` the local
       element count;
@@ -74,49 +77,28 @@ class BatchNormSync:
 
     def encoder_finalize(self, partials, count, bn):
         """``ops.bn_finalize`` over the global batch: (scale, shift), running buffers updated with the global statistics."""
-        from . import ops
         sums = self._all_reduce(ops.bn_partial_sums(partials))
         return ops.bn_finalize_sums(sums, count * self.world, bn.weight.detach(), bn.bias.detach(), bn.running_mean,
                                     bn.running_var, momentum=bn.momentum, eps=bn.eps)
 
-    def rows_fwd(self, x, w, b, running_mean, running_var, eps, momentum, out=None):
-        """``ops.bn_rows_fwd(train=True)`` over the global batch: (y, save_mean, save_invstd)."""
-        from . import ops
-        local = ops.bn_rows_moments(x)
-        gathered = torch.empty((self.world * 3, local.shape[1]), device=local.device, dtype=local.dtype)
-        dist.all_gather_into_tensor(gathered, local, group=self.group)
-        sm, si = ops.bn_rows_merge(gathered.view(self.world, 3, -1), running_mean, running_var, eps, momentum)
-        return ops.bn_rows_apply(x, sm, si, w, b, out=out), sm, si
-
-    def rows_bwd(self, dy, x, save_mean, save_invstd, w, split_out=False, add=None):
-        """``ops.bn_rows_bwd(train=True)`` over the global batch: (dx, dw, db), dw / db of the local rows.  ``split_out`` / ``add``
-        (the released encoder units' fused passes, dense rows, C % 4 == 0): dx as a Split tensor, or with ``add`` summed in,
-        like ``ops.bn_rows_bwd(split_out=..., add=...)``."""
-        from . import ops
-        local = ops.bn_rows_bwd_sums(dy, x, save_mean, save_invstd)
-        total = self._all_reduce(local.clone())
-        count = dy.shape[0] * self.world
-        if split_out or add is not None:
-            dx = ops.bn_rows_bwd_apply_fused(dy, x, save_mean, save_invstd, w, total, count, split_out=split_out, add=add)
-        else:
-            dx = ops.bn_rows_bwd_apply(dy, x, save_mean, save_invstd, w, total, count)
-        return dx, local[1], local[0]
-
-    # ---- released encoder units (IR50 with ``sync_released``): row counts of frames x pixels, 0.8 M .. 51 M rows
-    def rows_stats_large(self, x, running_mean, running_var, eps, momentum):
-        """``ops.bn_rows_stats`` over the global batch for dense rows x [R,C] of any size: (save_mean, save_invstd), the same
-        bits on every rank, running buffers updated with the global statistics."""
-        from . import ops
-        local = ops.bn_rows_moments_large(x)
+    def rows_stats(self, x, running_mean, running_var, eps, momentum, large=False):
+        """``ops.bn_rows_stats`` over the global batch: (save_mean, save_invstd), the same bits on every rank, running buffers
+        updated with the global statistics.  ``large``: dense rows of any size, read once (``bn_rows_moments_large``)."""
+        local = ops.bn_rows_moments_large(x) if large else ops.bn_rows_moments(x)
         gathered = torch.empty((self.world * 3, local.shape[1]), device=local.device, dtype=local.dtype)
         dist.all_gather_into_tensor(gathered, local, group=self.group)
         return ops.bn_rows_merge(gathered.view(self.world, 3, -1), running_mean, running_var, eps, momentum)
 
-    def rows_fwd_large(self, x, w, b, running_mean, running_var, eps, momentum):
-        """``ops.bn_rows_fwd(train=True)`` over the global batch for large dense rows: (y, save_mean, save_invstd)."""
-        from . import ops
-        sm, si = self.rows_stats_large(x, running_mean, running_var, eps, momentum)
-        return ops.bn_rows_apply(x, sm, si, w, b), sm, si
+    def rows_fwd(self, x, w, b, running_mean, running_var, eps, momentum, train=True, out=None, large=False):
+        """``ops.bn_rows_fwd`` over the global batch in train mode: (y, save_mean, save_invstd)."""
+        if not train:
+            return super().rows_fwd(x, w, b, running_mean, running_var, eps, momentum, train=False, out=out)
+        sm, si = self.rows_stats(x, running_mean, running_var, eps, momentum, large)
+        return ops.bn_rows_apply(x, sm, si, w, b, out=out), sm, si
+
+    def global_sums(self, sums, rows):
+        """The ranks' backward sums all-reduced, over ``world x`` the local rows."""
+        return self._all_reduce(sums.clone()), rows * self.world
 
     def agree_min(self, flag, device):
         """The minimum of an integer flag over the ranks (e.g. "this rank's memory fits the plan"), on the sync group."""

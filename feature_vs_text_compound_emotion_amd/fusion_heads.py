@@ -21,6 +21,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .batchnorm import LOCAL
 from .lfan import CLASSIFICATION, REGRESSION, TASKS, _linear_T, _packed  # noqa: F401
 from .temporal_convnet import TemporalConvNet
 from .visual_backbone import VisualBackbone
@@ -72,34 +73,25 @@ class LayerNormFn(torch.autograd.Function):
 
 
 class BNRowsFn(torch.autograd.Function):
-    """``sync``: None or a data_parallel.BatchNormSync -- in train mode the statistics (and the backward's sums) of all ranks'
-    rows."""
+    """``norm``: where the BatchNorm takes its statistics (batchnorm.LOCAL, or a data_parallel.BatchNormSync: in train mode
+    the statistics and the backward's sums of all ranks' rows)."""
 
     @staticmethod
-    def forward(ctx, x, w, b, running_mean, running_var, train, sync=None):
+    def forward(ctx, x, w, b, running_mean, running_var, train, norm=LOCAL):
         x = x.contiguous()
-        sync = sync if train else None
-        if sync is not None:
-            y, sm, si = sync.rows_fwd(x, w, b, running_mean, running_var, BN_EPS, BN_MOMENTUM)
-        else:
-            y, sm, si = ops.bn_rows_fwd(x, w, b, running_mean, running_var, train, BN_EPS, BN_MOMENTUM)
-        if not train:
-            sm, si = running_mean, torch.rsqrt(running_var + BN_EPS)
-        ctx.saved, ctx.train, ctx.sync = (x, w, sm, si), train, sync
+        y, sm, si = norm.rows_fwd(x, w, b, running_mean, running_var, BN_EPS, BN_MOMENTUM, train=train)
+        ctx.saved, ctx.train, ctx.norm = (x, w, sm, si), train, norm
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w, sm, si = ctx.saved
-        if ctx.sync is not None:
-            dx, dw, db = ctx.sync.rows_bwd(dy.contiguous(), x, sm, si, w)
-        else:
-            dx, dw, db = ops.bn_rows_bwd(dy.contiguous(), x, sm, si, w, ctx.train)
+        dx, dw, db = ctx.norm.rows_bwd(dy.contiguous(), x, sm, si, w, ctx.train)
         return dx, dw, db, None, None, None, None
 
 
-def batchnorm_rows(x, bn, train, sync=None):
-    y = BNRowsFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, train, sync)
+def batchnorm_rows(x, bn, train, norm=LOCAL):
+    y = BNRowsFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, train, norm)
     if train:
         bn.num_batches_tracked += 1
     return y
@@ -361,12 +353,12 @@ class _TailModel(nn.Module):
                 bsz, length = x.shape[0], x.shape[2]
                 rows = x.reshape(bsz * length, x.shape[-1])
             t = self.temporal[m].forward_rows(rows, bsz, length, seed=self.dropout_seed * 16 + i)
-            feats[m] = batchnorm_rows(t, self.bn[m], self.training, self.bn_sync)
+            feats[m] = batchnorm_rows(t, self.bn[m], self.training, self.bn_sync or LOCAL)
         return feats, bsz, length
 
     def _head(self, c, bsz, length):
         c = linear(c, self.fc1)
-        c = batchnorm_rows(c, self.bn1, self.training, self.bn_sync)
+        c = batchnorm_rows(c, self.bn1, self.training, self.bn_sync or LOCAL)
         c = linear(LeakyReLUFn.apply(c), self.fc2)
         c = c.view(bsz, length, -1)
         return torch.tanh(c) if self.task == REGRESSION else c

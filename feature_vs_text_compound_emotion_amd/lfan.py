@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .batchnorm import LOCAL
 from .temporal_convnet import TemporalConvNet
 from .audio_backbone import AudioBackbone
 from .visual_backbone import VisualBackbone
@@ -46,14 +47,14 @@ class LFANHeadFunction(torch.autograd.Function):
 
     args: (meta, buffers, fusion_mask, *tensors) where tensors =
       [t_m for each modality] + per modality [bn_w, bn_b, qkv_w, qkv_b] + [o_w, o_b, ln_w, ln_b, r_w, r_b]
-    meta = (M, H, hd, train, sink, sync); buffers = [(running_mean, running_var)] per modality (updated in place); ``sink``: None
-    or a list that receives the M BatchNorm outputs (detached views; what the reference leaves in the caller's dict); ``sync``:
-    None or a data_parallel.BatchNormSync -- the train-mode BatchNorms then use the statistics of all ranks' rows.
+    meta = (M, H, hd, train, sink, norm); buffers = [(running_mean, running_var)] per modality (updated in place); ``sink``: None
+    or a list that receives the M BatchNorm outputs (detached views; what the reference leaves in the caller's dict); ``norm``:
+    where the BatchNorms take their statistics (batchnorm.LOCAL, or a data_parallel.BatchNormSync: all ranks' rows).
     """
 
     @staticmethod
     def forward(ctx, meta, buffers, fmask, *ts):
-        M, H, hd, train, sink, sync = meta
+        M, H, hd, train, sink, norm = meta
         t = [x.contiguous() for x in ts[:M]]
         per = [ts[M + 4 * i:M + 4 * i + 4] for i in range(M)]
         o_w, o_b, ln_w, ln_b, r_w, r_b = ts[M + 4 * M:]
@@ -63,13 +64,7 @@ class LFANHeadFunction(torch.autograd.Function):
         for i in range(M):
             bn_w, bn_b, q_w, q_b = per[i]
             out = z[:, :enc0] if i == 0 else None
-            if train and sync is not None:
-                y, sm, si = sync.rows_fwd(t[i], bn_w, bn_b, buffers[i][0], buffers[i][1], BN_EPS, BN_MOMENTUM, out=out)
-            else:
-                y, sm, si = ops.bn_rows_fwd(t[i], bn_w, bn_b, buffers[i][0], buffers[i][1], train, BN_EPS, BN_MOMENTUM,
-                                            out=out)
-            if not train:  # eval-mode backward (rare) needs the statistics actually used
-                sm, si = buffers[i][0], torch.rsqrt(buffers[i][1] + BN_EPS)
+            y, sm, si = norm.rows_fwd(t[i], bn_w, bn_b, buffers[i][0], buffers[i][1], BN_EPS, BN_MOMENTUM, train=train, out=out)
             ys.append(y)
             stats.append((sm, si))
             qkvs.append(ops.linear(y, _packed(q_w), bias=q_b))
@@ -79,7 +74,7 @@ class LFANHeadFunction(torch.autograd.Function):
         logits = ops.linear(z, _packed(r_w), bias=r_b)
         if sink is not None:
             sink.extend(y.detach() for y in ys)
-        ctx.meta, ctx.sync, ctx.ts = meta[:4], sync, ts
+        ctx.meta, ctx.norm, ctx.ts = meta[:4], norm, ts
         ctx.saved = (t, ys, stats, qkvs, vals, probs, o, ln_mean, ln_rstd, z, fmask, enc0)
         return logits
 
@@ -110,10 +105,7 @@ class LFANHeadFunction(torch.autograd.Function):
             if i == 0:  # the leader also feeds the regressor directly
                 lead = ops.copy_cols(dz[:, :enc0], torch.empty((rows, enc0), device=z.device, dtype=torch.float32))
             dy = _linear_T(dqkv[i], q_w, residual=lead)
-            if train and ctx.sync is not None:
-                dt, g[M + 4 * i + 0], g[M + 4 * i + 1] = ctx.sync.rows_bwd(dy, t[i], stats[i][0], stats[i][1], bn_w)
-            else:
-                dt, g[M + 4 * i + 0], g[M + 4 * i + 1] = ops.bn_rows_bwd(dy, t[i], stats[i][0], stats[i][1], bn_w, train)
+            dt, g[M + 4 * i + 0], g[M + 4 * i + 1] = ctx.norm.rows_bwd(dy, t[i], stats[i][0], stats[i][1], bn_w, train)
             g[i] = dt if ctx.needs_input_grad[3 + i] else None
         return (None, None, None, *g)
 
@@ -309,7 +301,7 @@ class LFAN(nn.Module):
                self.regressor.weight, self.regressor.bias]
         buffers = [(self.bn[m].running_mean, self.bn[m].running_var) for m in mods]
         sink = []
-        logits = LFANHeadFunction.apply((M, H, hd, self.training, sink, self.bn_sync), buffers, fmask, *ts)
+        logits = LFANHeadFunction.apply((M, H, hd, self.training, sink, self.bn_sync or LOCAL), buffers, fmask, *ts)
         if self.training:
             for m in mods:
                 self.bn[m].num_batches_tracked += 1

@@ -1126,39 +1126,20 @@ def bn_rows_stats(x, running_mean, running_var, eps=1e-5, momentum=0.1):
 
 
 def bn_rows_bwd(dy, x, save_mean, save_invstd, w, train=True, split_out=False, add=None):
-    """``split_out`` (train mode, dense rows): dx as a Split tensor written by the apply pass itself.  ``add`` (train mode,
-    dense rows, C % 4 == 0): dx = BatchNorm-backward(dy) + add in the same pass."""
-    r, c, _ = _rows(dy, "dy")
-    for t, nme in ((save_mean, "save_mean"), (save_invstd, "save_invstd"), (w, "w")):
-        _dev_f32(t, nme, shape=(c,))
-    if add is not None:
-        for t, nme in ((dy, "dy"), (x, "x")):
-            _dev_f32(t, nme, shape=(r, c))
-        _dev_f32(add, "add")
-        if split_out or tuple(add.shape) != (r, c) or c % 4:
-            raise ValueError("bn_rows_bwd(add=...): fp32 result, add of the rows' shape, C % 4 == 0")
-        dx, dw, db = _empty((r, c), x), _empty((c,), x), _empty((c,), x)
-        ws, nbytes = _col_ws(r, c, x)
-        check(_lib.load().cer_bn_rows_bwd_add(ptr(dy), ptr(x), ptr(save_mean), ptr(save_invstd), ptr(w), ptr(add), ptr(dx), ptr(dw),
-                                              ptr(db), r, c, ptr(ws), nbytes, current_stream()), "cer_bn_rows_bwd_add")
-        return dx, dw, db
-    if split_out:
-        _dev_f32(dy, "dy")
-        _dev_f32(x, "x", shape=(r, c))
-        dx, dw, db = Split.empty((r, c), x.device), _empty((c,), x), _empty((c,), x)
-        ws, nbytes = _col_ws(r, c, x)
-        check(_lib.load().cer_bn_rows_bwd_split(ptr(dy), ptr(x), ptr(save_mean), ptr(save_invstd), ptr(w), ptr(dx.hi), ptr(dx.lo),
-                                                ptr(dw), ptr(db), r, c, ptr(ws), nbytes, current_stream()), "cer_bn_rows_bwd_split")
-        return dx, dw, db
-    r, c, dy_ld = _rows(dy, "dy")
-    _, _, x_ld = _rows(x, "x")
-    _dev_f32(x, "x", contiguous=False, shape=(r, c))
-    dx, dw, db = _empty((r, c), x), _empty((c,), x), _empty((c,), x)
-    ws, nbytes = _col_ws(r, c, x)
-    check(_lib.load().cer_bn_rows_bwd(ptr(dy), dy_ld, ptr(x), x_ld, ptr(save_mean), ptr(save_invstd), ptr(w),
-                                      ptr(dx), ptr(dw), ptr(db), r, c, 1 if train else 0, ptr(ws), nbytes,
-                                      current_stream()), "cer_bn_rows_bwd")
-    return dx, dw, db
+    """(dx, dw, db) of the row BatchNorm over x [R,C] (dense or a column slice): ``bn_rows_bwd_sums``, then
+    ``bn_rows_bwd_apply`` with those sums over R rows.  ``split_out`` (train mode, dense rows): dx as a Split tensor written by
+    the apply pass itself.  ``add`` (train mode, dense rows): dx = BatchNorm-backward(dy) + add in the same pass."""
+    return _bn_rows_bwd(dy, x, save_mean, save_invstd, w, train, split_out, add, None)
+
+
+def _bn_rows_bwd(dy, x, save_mean, save_invstd, w, train, split_out, add, global_sums):
+    """``bn_rows_bwd`` with the operands checked once; in train mode ``global_sums`` (None: the identity) maps the local
+    [2,C] sums and R to the sums and row count that dx is taken over (a synchronised BatchNorm's exchange)."""
+    r, c, dy_ld, x_ld = _bn_rows_bwd_check("bn_rows_bwd", dy, x, (save_mean, save_invstd, w), train, split_out, add)
+    sums = _bn_rows_bwd_sums(dy, dy_ld, x, x_ld, save_mean, save_invstd, r, c)
+    total, count = global_sums(sums, r) if train and global_sums is not None else (sums, r)
+    dx = _bn_rows_bwd_apply(dy, dy_ld, x, x_ld, save_mean, save_invstd, w, total, count, train, split_out, add, r, c)
+    return dx, sums[1], sums[0]
 
 
 # ------------------------------------------------------------------ row BatchNorm split at its statistics (synchronised BN)
@@ -1207,16 +1188,28 @@ def bn_rows_apply(x, mean, invstd, w, b, out=None):
     return out
 
 
-def bn_rows_bwd_sums(dy, x, save_mean, save_invstd):
-    """[2,C] float32 = (sum dy, sum dy * x_hat) over the local rows: this rank's db and dw (the reductions of
-    ``bn_rows_bwd``), and its contribution to the global sums of a synchronised backward."""
+def _bn_rows_bwd_check(fn, dy, x, vecs, train=True, split_out=False, add=None):
+    """The operands of the row BatchNorm backward, refused before any launch; ``vecs``: (save_mean, save_invstd[, w]), the
+    [C] vectors the call reads.  Returns (R, C, dy pitch, x pitch)."""
     r, c, dy_ld = _rows(dy, "dy")
     _, _, x_ld = _rows(x, "x")
     _dev_f32(x, "x", contiguous=False, shape=(r, c))
-    for t, n in ((save_mean, "save_mean"), (save_invstd, "save_invstd")):
+    for t, n in zip(vecs, ("save_mean", "save_invstd", "w")):
         if t is None:
-            raise ValueError(f"bn_rows_bwd_sums: {n} is required")
+            raise ValueError(f"{fn}: {n} is required")
         _dev_f32(t, n, shape=(c,))
+    if split_out or add is not None:   # the released encoder units' float4 passes
+        if not train or (split_out and add is not None):
+            raise ValueError(f"{fn}: split_out / add are train mode, and add needs the fp32 result (split_out=False)")
+        _dense_rows4(dy, "dy")
+        _dense_rows4(x, "x")
+        if add is not None:
+            _dense_rows4(add, "add")
+            _dev_f32(add, "add", shape=(r, c))
+    return r, c, dy_ld, x_ld
+
+
+def _bn_rows_bwd_sums(dy, dy_ld, x, x_ld, save_mean, save_invstd, r, c):
     sums = _empty((2, c), x)
     ws, nbytes = _col_ws(r, c, x)
     check(_lib.load().cer_bn_rows_bwd_sums(ptr(dy), dy_ld, ptr(x), x_ld, ptr(save_mean), ptr(save_invstd), ptr(sums), r, c,
@@ -1224,24 +1217,33 @@ def bn_rows_bwd_sums(dy, x, save_mean, save_invstd):
     return sums
 
 
-def bn_rows_bwd_apply(dy, x, save_mean, save_invstd, w, sums, count):
-    """dx of the train-mode row BatchNorm over the local rows, from the GLOBAL [2,C] sums (sum dy | sum dy * x_hat) over
-    ``count`` rows."""
-    r, c, dy_ld = _rows(dy, "dy")
-    _, _, x_ld = _rows(x, "x")
-    _dev_f32(x, "x", contiguous=False, shape=(r, c))
-    for t, n in ((save_mean, "save_mean"), (save_invstd, "save_invstd"), (w, "w"), (sums, "sums")):
-        if t is None:
-            raise ValueError(f"bn_rows_bwd_apply: {n} is required")
-    for t, n in ((save_mean, "save_mean"), (save_invstd, "save_invstd"), (w, "w")):
-        _dev_f32(t, n, shape=(c,))
+def _bn_rows_bwd_apply(dy, dy_ld, x, x_ld, save_mean, save_invstd, w, sums, count, train, split_out, add, r, c):
+    dx = Split.empty((r, c), x.device) if split_out else _empty((r, c), x)
+    f32, hi, lo = (None, dx.hi, dx.lo) if split_out else (dx, None, None)
+    check(_lib.load().cer_bn_rows_bwd_apply(ptr(dy), dy_ld, ptr(x), x_ld, ptr(save_mean), ptr(save_invstd), ptr(w), ptr(sums),
+                                            float(count), 1 if train else 0, ptr(add), ptr(f32), ptr(hi), ptr(lo), r, c,
+                                            current_stream()), "cer_bn_rows_bwd_apply")
+    return dx
+
+
+def bn_rows_bwd_sums(dy, x, save_mean, save_invstd):
+    """[2,C] float32 = (sum dy, sum dy * x_hat) over the local rows: this rank's db and dw, and its contribution to the
+    global sums of a synchronised backward."""
+    r, c, dy_ld, x_ld = _bn_rows_bwd_check("bn_rows_bwd_sums", dy, x, (save_mean, save_invstd))
+    return _bn_rows_bwd_sums(dy, dy_ld, x, x_ld, save_mean, save_invstd, r, c)
+
+
+def bn_rows_bwd_apply(dy, x, save_mean, save_invstd, w, sums, count, *, train=True, split_out=False, add=None):
+    """dx of the row BatchNorm over the local rows from GIVEN [2,C] sums (sum dy | sum dy * x_hat) over ``count`` rows (the
+    global batch's under synchronised BatchNorm; eval mode reads neither).  ``split_out`` / ``add`` as in ``bn_rows_bwd``."""
+    r, c, dy_ld, x_ld = _bn_rows_bwd_check("bn_rows_bwd_apply", dy, x, (save_mean, save_invstd, w), train, split_out,
+                                        add)
+    if sums is None:
+        raise ValueError("bn_rows_bwd_apply: sums is required")
     _dev_f32(sums, "sums", shape=(2, c))
     if not count > 0:
         raise ValueError(f"bn_rows_bwd_apply: count must be positive, got {count}")
-    dx = _empty((r, c), x)
-    check(_lib.load().cer_bn_rows_bwd_apply(ptr(dy), dy_ld, ptr(x), x_ld, ptr(save_mean), ptr(save_invstd), ptr(w), ptr(sums),
-                                            float(count), ptr(dx), r, c, current_stream()), "cer_bn_rows_bwd_apply")
-    return dx
+    return _bn_rows_bwd_apply(dy, dy_ld, x, x_ld, save_mean, save_invstd, w, sums, count, train, split_out, add, r, c)
 
 
 def _dense_rows4(t, name):
@@ -1264,38 +1266,6 @@ def bn_rows_moments_large(x):
     check(lib.cer_bn_rows_moments_large(ptr(x), r, c, ptr(moments), ptr(ws), nbytes, current_stream()),
           "cer_bn_rows_moments_large")
     return moments
-
-
-def bn_rows_bwd_apply_fused(dy, x, save_mean, save_invstd, w, sums, count, split_out=False, add=None):
-    """The apply pass of ``bn_rows_bwd(split_out=True)`` / ``bn_rows_bwd(add=...)`` from GIVEN [2,C] sums (sum dy | sum dy *
-    x_hat) over ``count`` rows: dx as a Split tensor, or fp32 with ``add`` (optional) summed in.  Dense rows, C % 4 == 0.
-    With ``bn_rows_bwd_sums`` of the same rows and ``count == R`` it returns ``bn_rows_bwd``'s dx bit for bit."""
-    r, c = _dense_rows4(dy, "dy")
-    _dense_rows4(x, "x")
-    _dev_f32(x, "x", shape=(r, c))
-    for t, n in ((save_mean, "save_mean"), (save_invstd, "save_invstd"), (w, "w"), (sums, "sums")):
-        if t is None:
-            raise ValueError(f"bn_rows_bwd_apply_fused: {n} is required")
-    for t, n in ((save_mean, "save_mean"), (save_invstd, "save_invstd"), (w, "w")):
-        _dev_f32(t, n, shape=(c,))
-    _dev_f32(sums, "sums", shape=(2, c))
-    if add is not None:
-        if split_out:
-            raise ValueError("bn_rows_bwd_apply_fused: add needs the fp32 result (split_out=False)")
-        _dense_rows4(add, "add")
-        _dev_f32(add, "add", shape=(r, c))
-    if not count > 0:
-        raise ValueError(f"bn_rows_bwd_apply_fused: count must be positive, got {count}")
-    lib = _lib.load()
-    if split_out:
-        dx = Split.empty((r, c), x.device)
-        check(lib.cer_bn_rows_bwd_apply_split(ptr(dy), ptr(x), ptr(save_mean), ptr(save_invstd), ptr(w), ptr(sums), float(count),
-                                              ptr(dx.hi), ptr(dx.lo), r, c, current_stream()), "cer_bn_rows_bwd_apply_split")
-        return dx
-    dx = _empty((r, c), x)
-    check(lib.cer_bn_rows_bwd_apply_add(ptr(dy), ptr(x), ptr(save_mean), ptr(save_invstd), ptr(w), ptr(sums), float(count), ptr(add),
-                                        ptr(dx), r, c, current_stream()), "cer_bn_rows_bwd_apply_add")
-    return dx
 
 
 def _ptr_array(tensors):

@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .batchnorm import LOCAL
 from .synth import ir50_units
 
 BN_EPS = 1e-5
@@ -136,26 +137,9 @@ def _bn_affine_from_saved(save_mean, save_invstd, gamma, beta):
     return scale.contiguous(), (beta - save_mean * scale).contiguous()
 
 
-# The released parts' row BatchNorms.  ``sync``: the model's BatchNormSync when ``IR50.sync_released`` is on (statistics and
-# backward sums of the global batch, data_parallel.py), else None (the rank's own rows).
-def _rows_stats(sync, x, bn):
-    if sync is not None:
-        return sync.rows_stats_large(x, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
-    return ops.bn_rows_stats(x, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
-
-
-def _rows_fwd(sync, x, w, b, bn, large=True):
-    if sync is None:
-        return ops.bn_rows_fwd(x, w, b, bn.running_mean, bn.running_var, True, bn.eps, bn.momentum)
-    if large:
-        return sync.rows_fwd_large(x, w, b, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
-    return sync.rows_fwd(x, w, b, bn.running_mean, bn.running_var, bn.eps, bn.momentum)
-
-
-def _rows_bwd(sync, dy, x, save_mean, save_invstd, w, split_out=False, add=None):
-    if sync is not None:
-        return sync.rows_bwd(dy, x, save_mean, save_invstd, w, split_out=split_out, add=add)
-    return ops.bn_rows_bwd(dy, x, save_mean, save_invstd, w, split_out=split_out, add=add)
+def _buffers(bn):
+    """The running buffers and constants of a row BatchNorm, as ``BatchNormLocal.rows_stats`` / ``rows_fwd`` take them."""
+    return bn.running_mean, bn.running_var, bn.eps, bn.momentum
 
 
 class _ReleasedUnit(torch.autograd.Function):
@@ -181,13 +165,13 @@ class _ReleasedUnit(torch.autograd.Function):
     -- an explicit trade, held to its own bar in tests/test_head_release_gpu.py."""
 
     @staticmethod
-    def forward(ctx, x, u, prec, memory, g1, b1, w1, a1, w2, g2, b2, ws, gs, bs, sync=None):
+    def forward(ctx, x, u, prec, memory, g1, b1, w1, a1, w2, g2, b2, ws, gs, bs, norm=LOCAL):
         n, h, w, cin = x.shape
         bn1, bn2, s = u.res_layer[0], u.res_layer[4], u.stride
         b3 = prec == "bf16x3"
         # BatchNorm 1: statistics pass only; the normalisation is ONE affine (+ split) pass from them -- the same arithmetic the
         # backward uses to rebuild it, so the "recompute" memory plan reproduces z1 / z2 bit for bit
-        sm1, si1 = _rows_stats(sync, x.view(-1, cin), bn1)
+        sm1, si1 = norm.rows_stats(x.view(-1, cin), *_buffers(bn1), large=True)
         sc1, sh1 = _bn_affine_from_saved(sm1, si1, g1.detach(), b1.detach())
         xb_k = ops.split_bf16(x, sc1, sh1) if b3 else torch.addcmul(sh1, x, sc1)
         if b3 and memory != "raw":   # z1 is not kept: PReLU and the split happen in the conv's epilogue (no z1 / t1 round trips)
@@ -207,13 +191,13 @@ class _ReleasedUnit(torch.autograd.Function):
         del t1_k
         _, ho, wo, depth = z2.shape
         # BatchNorm 2 (+ the shortcut's BatchNorm) and the residual add in ONE pass over z2: statistics, then scale / shift
-        sm2, si2 = _rows_stats(sync, z2.view(-1, depth), bn2)
+        sm2, si2 = norm.rows_stats(z2.view(-1, depth), *_buffers(bn2), large=True)
         sc2, sh2 = _bn_affine_from_saved(sm2, si2, g2.detach(), b2.detach())
         zs = sms = sis = None
         if ws is not None:
             bns = u.shortcut_layer[1]
             zs = _conv_prec(x, ops.pack_conv_weight(ws.detach().contiguous()), 1, 1, s, (0, 0), prec)
-            sms, sis = _rows_stats(sync, zs.view(-1, depth), bns)
+            sms, sis = norm.rows_stats(zs.view(-1, depth), *_buffers(bns), large=True)
             scs, shs = _bn_affine_from_saved(sms, sis, gs.detach(), bs.detach())
             out = ops.bn_apply_nhwc(z2, sc2, sh2, res=zs, res_scale=scs, res_shift=shs)
         else:
@@ -234,14 +218,14 @@ class _ReleasedUnit(torch.autograd.Function):
                               gs.detach() if gs is not None else None)
         ctx.stride = s
         ctx.prec = prec
-        ctx.sync = sync
+        ctx.norm = norm
         ctx.out_shape = tuple(out.shape)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, z1, z2, sm1, si1, sm2, si2, zs, sms, sis, g1, b1, w1, a1, w2, g2, ws, gs = ctx.saved_tensors
-        s, prec, sync = ctx.stride, ctx.prec, ctx.sync
+        s, prec, norm = ctx.stride, ctx.prec, ctx.norm
         # fp16 storage has no range for UN-scaled gradients: a mean cross-entropy gradient divided over B*L rows and H*W
         # pixels sits at or below fp16's smallest subnormal (6e-8) and would flush to zero when the output gradient is
         # rounded to the storage type.  The reference always pairs fp16 with GradScaler (trainer.py:341,389), and so does this
@@ -272,7 +256,7 @@ class _ReleasedUnit(torch.autograd.Function):
             z2 = _conv_prec(t1, ops.pack_conv_weight(w2.contiguous()), 3, 3, s, (1, 1), prec)
             if ws is not None:
                 zs = _conv_prec(x, ops.pack_conv_weight(ws.contiguous()), 1, 1, s, (0, 0), prec)
-        dz2, dg2, db2 = _rows_bwd(sync, dout.view(-1, depth), z2.view(-1, depth), sm2, si2, g2, split_out=split)
+        dz2, dg2, db2 = norm.rows_bwd(dout.view(-1, depth), z2.view(-1, depth), sm2, si2, g2, split_out=split)
         del z2
         dz2 = dz2.view(n, ho, wo, depth)
         dw2 = ops.conv2d_wgrad(dz2, t1, 3, 3, stride=s, pad=(1, 1), b3=b3)
@@ -291,7 +275,7 @@ class _ReleasedUnit(torch.autograd.Function):
         dws = dgs = dbs = None
         addend = even = None
         if ws is not None:
-            dzs, dgs, dbs = _rows_bwd(sync, dout.view(-1, depth), zs.view(-1, depth), sms, sis, gs)
+            dzs, dgs, dbs = norm.rows_bwd(dout.view(-1, depth), zs.view(-1, depth), sms, sis, gs)
             dzs = dzs.view(n, ho, wo, depth)
             if split and s == 1:
                 dzs = ops.split_bf16(dzs)
@@ -309,12 +293,12 @@ class _ReleasedUnit(torch.autograd.Function):
         rows_ok = need_dx and addend is not None and cin % 4 == 0
         if xh is not None:   # x_hat is what was saved: mean 0, invstd 1, and the outer gamma * invstd factor as the "weight"
             # (synchronised: the sums of THIS form -- sum dy, sum dy * x_hat of the global statistics -- are the ones exchanged)
-            dx, dg1, db1 = _rows_bwd(sync, dxb.view(-1, cin), xh.view(-1, cin), torch.zeros_like(sm1), torch.ones_like(si1),
-                                     (g1 * si1).contiguous(), add=addend.view(-1, cin) if rows_ok else None)
+            dx, dg1, db1 = norm.rows_bwd(dxb.view(-1, cin), xh.view(-1, cin), torch.zeros_like(sm1), torch.ones_like(si1),
+                                         (g1 * si1).contiguous(), add=addend.view(-1, cin) if rows_ok else None)
             del xh
         else:
-            dx, dg1, db1 = _rows_bwd(sync, dxb.view(-1, cin), x.view(-1, cin), sm1, si1, g1,
-                                     add=addend.view(-1, cin) if rows_ok else None)
+            dx, dg1, db1 = norm.rows_bwd(dxb.view(-1, cin), x.view(-1, cin), sm1, si1, g1,
+                                         add=addend.view(-1, cin) if rows_ok else None)
         del dxb
         dx = dx.view(n, h, w, cin)
         if need_dx and not rows_ok:
@@ -335,13 +319,13 @@ class _ReleasedStem(torch.autograd.Function):
     result is kept for the backward; the BatchNorm output the PReLU saw is recomputed from the saved statistics."""
 
     @staticmethod
-    def forward(ctx, x, bn, w, g, b, a, sync=None):
+    def forward(ctx, x, bn, w, g, b, a, norm=LOCAL):
         n, _, h, wd = x.shape
         z = ops.conv2d(x.contiguous(), ops.pack_conv_weight(w.detach().contiguous()), 3, 3, pad=(1, 1), x_nchw=True)
-        zb, sm, si = _rows_fwd(sync, z.view(-1, 64), g.detach(), b.detach(), bn)
+        zb, sm, si = norm.rows_fwd(z.view(-1, 64), g.detach(), b.detach(), *_buffers(bn), large=True)
         y = ops.prelu_fwd(zb.view(n, h, wd, 64), a.detach().contiguous())
         ctx.save_for_backward(x, z, sm, si, g.detach(), b.detach(), a.detach())
-        ctx.sync = sync
+        ctx.norm = norm
         return y
 
     @staticmethod
@@ -352,7 +336,7 @@ class _ReleasedStem(torch.autograd.Function):
         zb = torch.addcmul(sh, z, sc)
         dzb, da = ops.prelu_bwd(dy.contiguous(), zb, a.contiguous())
         del zb
-        dz, dg, db = _rows_bwd(ctx.sync, dzb.view(-1, 64), z.view(-1, 64), sm, si, g)
+        dz, dg, db = ctx.norm.rows_bwd(dzb.view(-1, 64), z.view(-1, 64), sm, si, g)
         del dzb
         x4 = torch.zeros((n, h, wd, 4), device=x.device, dtype=torch.float32)
         x4[..., :3] = x.permute(0, 2, 3, 1)
@@ -368,18 +352,18 @@ class _ReleasedHead(torch.autograd.Function):
     Everything runs on the exact-fp32 kernels (row BatchNorm fwd/bwd, igemm GEMMs, TN weight-gradient GEMM)."""
 
     @staticmethod
-    def forward(ctx, y, mask, bn2, fc, bn1, w2, b2, wfc, bfc, w1, b1, sync=None):
+    def forward(ctx, y, mask, bn2, fc, bn1, w2, b2, wfc, bfc, w1, b1, norm=LOCAL):
         n, h, w, c = y.shape
         rows = y.view(n * h * w, c)
-        o2, sm2, si2 = _rows_fwd(sync, rows, w2.detach(), b2.detach(), bn2)
+        o2, sm2, si2 = norm.rows_fwd(rows, w2.detach(), b2.detach(), *_buffers(bn2), large=True)
         hfeat = ops.act_mask_bwd(o2, o2, mask.view(n * h * w, c), slope=1.0) if mask is not None else o2  # o2 * mask
         k = h * w * c
         whwc = wfc.detach().view(wfc.shape[0], c, h * w).permute(0, 2, 1).contiguous().view(wfc.shape[0], k)  # (c,h,w)->(h,w,c)
         e = ops.linear(hfeat.view(n, k), whwc, bias=bfc.detach(), split_k=max(1, min(k // 32, 192 // ((n + 127) // 128))))
-        e2, sm1, si1 = _rows_fwd(sync, e, w1.detach(), b1.detach(), bn1, large=False)   # (one row per frame)
+        e2, sm1, si1 = norm.rows_fwd(e, w1.detach(), b1.detach(), *_buffers(bn1))   # (one row per frame)
         ctx.save_for_backward(rows, mask, hfeat, e, e2, sm2, si2, sm1, si1, whwc, w2.detach(), w1.detach())
         ctx.dims = (n, h, w, c)
-        ctx.sync = sync
+        ctx.norm = norm
         return ops.l2norm_rows(e2)
 
     @staticmethod
@@ -388,14 +372,14 @@ class _ReleasedHead(torch.autograd.Function):
         n, h, w, c = ctx.dims
         k = h * w * c
         de2 = ops.l2norm_rows_bwd(demb.contiguous(), e2)
-        de, dw1, db1 = _rows_bwd(ctx.sync, de2, e, sm1, si1, w1)
+        de, dw1, db1 = ctx.norm.rows_bwd(de2, e, sm1, si1, w1)
         dwhwc = ops.conv1d_wgrad(de, hfeat.view(n, k), n, 1, 1).view(-1, h * w, c)      # dW[o][(h,w,c)] = de^T hfeat
         dwfc = dwhwc.permute(0, 2, 1).reshape(-1, k)                                     # back to the (c,h,w) flatten order
         dbfc = ops.col_sum(de)
         dh = ops.linear(de, whwc.t().contiguous())                                       # [n, k] = de @ W
         do2 = ops.act_mask_bwd(dh.view(n * h * w, c), dh.view(n * h * w, c), mask.view(n * h * w, c), slope=1.0) \
             if mask is not None else dh.view(n * h * w, c)
-        dy, dw2, db2 = _rows_bwd(ctx.sync, do2, rows, sm2, si2, w2)
+        dy, dw2, db2 = ctx.norm.rows_bwd(do2, rows, sm2, si2, w2)
         dy = dy.view(n, h, w, c) if ctx.needs_input_grad[0] else None  # only when body units below are released too
         return dy, None, None, None, None, dw2, db2, dwfc, dbfc, dw1, db1, None
 
@@ -714,7 +698,7 @@ class IR50(nn.Module):
         else:
             # the input layer is write-bound: statistics pass, then the conv again with BatchNorm + PReLU applied (stem_conv.hip)
             xc = x.contiguous()
-            s, t = self._finalize(ops.stem_conv(xc, P["stem_w"]), n * x.shape[2] * x.shape[3], self.input_layer[1])
+            s, t = self._norm().encoder_finalize(ops.stem_conv(xc, P["stem_w"]), n * x.shape[2] * x.shape[3], self.input_layer[1])
             r = ops.stem_conv(xc, P["stem_w"], s, t, self.input_layer[2].weight.detach(),
                               out="f32" if first_released == 0 else dtype, want_stats=True)
             ys, xst, y = r.get("n16"), r["stats"], r.get("y")
@@ -724,7 +708,7 @@ class IR50(nn.Module):
                 y = self._released_unit(u, y, "fp16" if dtype == torch.float16 else "bf16")
                 continue
             last = i + 1 == first_released  # the next consumer (released unit or head) wants fp32
-            s1, t1 = self._finalize(xst, ys.numel() // u.cin, u.res_layer[0])
+            s1, t1 = self._norm().encoder_finalize(xst, ys.numel() // u.cin, u.res_layer[0])
             w1, b9 = ops.fold_bn_3x3_packed(d["w1_f32"], s1, t1, dtype)
             s2d = "w2_s2d" in d and self._s2d_pair_ok(tuple(ys.shape), u.depth, narrow=True)
             tt = ops.conv2d_n16(ys, w1, 3, 3, pad=(1, 1), alpha=u.res_layer[2].weight.detach(),
@@ -733,10 +717,10 @@ class IR50(nn.Module):
             del tt
             z = r["n16"]
             cnt = z.numel() // u.depth
-            s2, t2 = self._finalize(r["stats"], cnt, u.res_layer[4])
+            s2, t2 = self._norm().encoder_finalize(r["stats"], cnt, u.res_layer[4])
             if u.cin != u.depth:
                 rs = ops.conv2d_n16(ys, d["ws"], 1, 1, stride=u.stride, want_stats=True)
-                ss, stt = self._finalize(rs["stats"], cnt, u.shortcut_layer[1])
+                ss, stt = self._norm().encoder_finalize(rs["stats"], cnt, u.shortcut_layer[1])
                 o = ops.bn_apply_nhwc_n16(z, s2, t2, res=rs["n16"], res_scale=ss, res_shift=stt, want_stats=True,
                                           out_f32=last, out_n16=not last)
             else:
@@ -754,13 +738,14 @@ class IR50(nn.Module):
                                          y.device)
         if plan is not None:
             return self._released_head(y, head_mask)
-        s0, t0 = self._finalize(xst, y.numel() // c, self.output_layer[0])
+        s0, t0 = self._norm().encoder_finalize(xst, y.numel() // c, self.output_layer[0])
         hfeat = ops.bn_apply_nhwc_n16(y, s0, t0, dtype=dtype, mask=head_mask)["n16"]
         k = h * w * c
         fc = self.output_layer[3]
         e = ops.conv2d_n16(hfeat.view(n, 1, 1, k), P["head_w"], 1, 1, bias=fc.bias.detach(),
                            split_k=self._head_split_k(n, k), out_f32=True, out_n16=False)["y"].view(n, -1)
-        e = self._head_bn(e)
+        bn1 = self.output_layer[4]
+        e = self._norm().rows_fwd(e, bn1.weight.detach(), bn1.bias.detach(), *_buffers(bn1))[0]
         torch._foreach_add_([m.num_batches_tracked for m in self.modules()
                              if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d))], 1)
         return ops.l2norm_rows(e)
@@ -831,7 +816,7 @@ class IR50(nn.Module):
         else:
             # the input layer is write-bound: statistics pass, then the conv again with BatchNorm + PReLU applied (stem_conv.hip)
             xc = x.contiguous()
-            s, t = self._finalize(ops.stem_conv(xc, P["stem_w"]), n * x.shape[2] * x.shape[3], self.input_layer[1])
+            s, t = self._norm().encoder_finalize(ops.stem_conv(xc, P["stem_w"]), n * x.shape[2] * x.shape[3], self.input_layer[1])
             r = ops.stem_conv(xc, P["stem_w"], s, t, self.input_layer[2].weight.detach(),
                               out="f32" if first_released == 0 else "split", want_stats=True)
             ys, xst, y = r.get("split"), r["stats"], r.get("y")
@@ -841,7 +826,7 @@ class IR50(nn.Module):
                 y = self._released_unit(u, y, "bf16x3")
                 continue
             last = i + 1 == first_released  # the next consumer (released unit or head) wants fp32
-            s1, t1 = self._finalize(xst, ys.hi.numel() // u.cin, u.res_layer[0])
+            s1, t1 = self._norm().encoder_finalize(xst, ys.hi.numel() // u.cin, u.res_layer[0])
             w1, b9 = ops.fold_bn_3x3_packed(d["w1_f32"], s1, t1, "split")
             s2d = "w2_s2d" in d and self._s2d_pair_ok(tuple(ys.shape), u.depth)
             tt = ops.conv2d_b3(ys, w1, 3, 3, pad=(1, 1), alpha=u.res_layer[2].weight.detach(),
@@ -851,10 +836,10 @@ class IR50(nn.Module):
             del tt
             z = r["y"]
             cnt = z.numel() // u.depth
-            s2, t2 = self._finalize(r["stats"], cnt, u.res_layer[4])
+            s2, t2 = self._norm().encoder_finalize(r["stats"], cnt, u.res_layer[4])
             if u.cin != u.depth:
                 rs = ops.conv2d_b3(ys, d["ws"], 1, 1, stride=u.stride, out_f32=True, out_split=False, want_stats=True)
-                ss, stt = self._finalize(rs["stats"], cnt, u.shortcut_layer[1])
+                ss, stt = self._norm().encoder_finalize(rs["stats"], cnt, u.shortcut_layer[1])
                 o = ops.bn_apply_nhwc_b3(z, s2, t2, res=rs["y"], res_scale=ss, res_shift=stt, want_stats=True,
                                          out_f32=last, out_split=not last)
             else:
@@ -872,13 +857,14 @@ class IR50(nn.Module):
                                          y.device)
         if plan is not None:
             return self._released_head(y, head_mask)
-        s0, t0 = self._finalize(xst, y.numel() // c, self.output_layer[0])
+        s0, t0 = self._norm().encoder_finalize(xst, y.numel() // c, self.output_layer[0])
         hfeat = ops.bn_apply_nhwc_b3(y, s0, t0, mask=head_mask)["split"]
         k = h * w * c
         fc = self.output_layer[3]
         e = ops.conv2d_b3(hfeat.view(n, 1, 1, k), P["head_w"], 1, 1, bias=fc.bias.detach(),
                           split_k=self._head_split_k(n, k), out_f32=True, out_split=False)["y"].view(n, -1)
-        e = self._head_bn(e)
+        bn1 = self.output_layer[4]
+        e = self._norm().rows_fwd(e, bn1.weight.detach(), bn1.bias.detach(), *_buffers(bn1))[0]
         torch._foreach_add_([m.num_batches_tracked for m in self.modules()
                              if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d))], 1)
         return ops.l2norm_rows(e)
@@ -920,11 +906,15 @@ class IR50(nn.Module):
 
     def _released_stem(self, x):
         il = self.input_layer
-        return _ReleasedStem.apply(x, il[1], il[0].weight, il[1].weight, il[1].bias, il[2].weight, self._release_sync())
+        return _ReleasedStem.apply(x, il[1], il[0].weight, il[1].weight, il[1].bias, il[2].weight, self._released_norm())
 
-    def _release_sync(self):
-        """The BatchNormSync of the released parts, or None (their statistics stay the rank's own)."""
-        return self.bn_sync if self.sync_released else None
+    def _norm(self):
+        """Where the batch-statistics forwards take their BatchNorm statistics: ``bn_sync``, or the local batch."""
+        return self.bn_sync or LOCAL
+
+    def _released_norm(self):
+        """The same for the released head / units / stem: ``bn_sync`` under ``sync_released``, else the local batch."""
+        return (self.bn_sync if self.sync_released else None) or LOCAL
 
     def _resolve_activation_memory(self, frames, hw, device=None):
         """What the released units of THIS forward keep (see ``activation_memory``); called once per forward.  Under
@@ -937,15 +927,9 @@ class IR50(nn.Module):
         if mode == "auto":
             released = sum(1 for u in self.body if all(p.requires_grad for p in u.parameters()))
             raw = 410e6 * (hw / 224.0) ** 2 * frames * released / len(self.body)      # fp32 raw tensors of the released units
-            sync = self._release_sync()
-            if sync is not None:
-                free, _ = torch.cuda.mem_get_info(device)
-                free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
-                mode = "raw" if sync.agree_min(1.6 * raw < free, device) else "recompute"
-            else:
-                free, _ = torch.cuda.mem_get_info()
-                free += torch.cuda.memory_reserved() - torch.cuda.memory_allocated()  # the allocator's cached blocks are reusable
-                mode = "raw" if 1.6 * raw < free else "recompute"
+            free, _ = torch.cuda.mem_get_info(device)
+            free += torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)  # (cached blocks are reusable)
+            mode = "raw" if self._released_norm().agree_min(1.6 * raw < free, device) else "recompute"
         self._act_mem = mode
         return mode
 
@@ -955,12 +939,12 @@ class IR50(nn.Module):
         return _ReleasedUnit.apply(y, u, prec, self._act_mem, pr[0].weight, pr[0].bias, pr[1].weight, pr[2].weight, pr[3].weight, pr[4].weight,
                                    pr[4].bias, sc[0].weight if sc is not None else None,
                                    sc[1].weight if sc is not None else None, sc[1].bias if sc is not None else None,
-                                   self._release_sync())
+                                   self._released_norm())
 
     def _released_head(self, y, head_mask):
         bn2, fc, bn1 = self.output_layer[0], self.output_layer[3], self.output_layer[4]
         out = _ReleasedHead.apply(y, head_mask, bn2, fc, bn1, bn2.weight, bn2.bias, fc.weight, fc.bias, bn1.weight, bn1.bias,
-                                  self._release_sync())
+                                  self._released_norm())
         torch._foreach_add_([m.num_batches_tracked for m in self.modules()
                              if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d))], 1)
         return out
@@ -970,25 +954,11 @@ class IR50(nn.Module):
         tiles = ((n + 127) // 128) * 4
         return max(1, min(k // 32, (768 + tiles - 1) // tiles))
 
-    def _finalize(self, stats, count, bn):
-        if self.bn_sync is not None:
-            return self.bn_sync.encoder_finalize(stats, count, bn)
-        return ops.bn_finalize(stats, count, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
-                               momentum=bn.momentum, eps=bn.eps)
-
-    def _head_bn(self, e):
-        """The head BatchNorm1d of the batch-statistics forwards (no autograd: the frozen encoder's head)."""
-        bn1 = self.output_layer[4]
-        if self.bn_sync is not None:
-            return self.bn_sync.rows_fwd(e, bn1.weight.detach(), bn1.bias.detach(), bn1.running_mean, bn1.running_var,
-                                         bn1.eps, bn1.momentum)[0]
-        return ops.bn_rows_fwd(e, bn1.weight.detach(), bn1.bias.detach(), bn1.running_mean, bn1.running_var, True,
-                               bn1.eps, bn1.momentum)[0]
-
     def check_sync_release(self):
         """Synchronised statistics cover the released units / head / stem only under ``sync_released``: otherwise refuse them
         before anything runs."""
-        if self.bn_sync is not None and not self.sync_released and self.training and self.bn_mode == "reference" and torch.is_grad_enabled() and \
+        synced_frozen_only = self._released_norm() is not self._norm()     # bn_sync without sync_released
+        if synced_frozen_only and self.training and self.bn_mode == "reference" and torch.is_grad_enabled() and \
                 any(p.requires_grad for p in self.parameters()):
             raise NotImplementedError("sync_bn with released encoder parameters is not implemented on the default path "
                                       "(synchronised statistics in _ReleasedUnit / _ReleasedStem / _ReleasedHead are opt-in: "
@@ -1010,23 +980,24 @@ class IR50(nn.Module):
             y = self._released_stem(x)
         else:
             xc = x.contiguous()
-            s, t = self._finalize(ops.stem_conv(xc, P["stem_w"]), x.shape[0] * x.shape[2] * x.shape[3], self.input_layer[1])
+            s, t = self._norm().encoder_finalize(ops.stem_conv(xc, P["stem_w"]), x.shape[0] * x.shape[2] * x.shape[3],
+                                                 self.input_layer[1])
             r = ops.stem_conv(xc, P["stem_w"], s, t, self.input_layer[2].weight.detach(), out="f32", want_stats=True)
             y, xst = r["y"], r["stats"]
         for i, (u, d) in enumerate(zip(self.body, P["units"])):
             if i >= first_released:
                 y = self._released_unit(u, y)
                 continue
-            s1, t1 = self._finalize(xst, y.numel() // u.cin, u.res_layer[0])
+            s1, t1 = self._norm().encoder_finalize(xst, y.numel() // u.cin, u.res_layer[0])
             tt = ops.conv2d(y, d["w1"], 3, 3, pad=(1, 1), in_scale=s1, in_shift=t1,
                             alpha=u.res_layer[2].weight.detach(), act1=ops.ACT_PRELU)
             z, zst = ops.conv2d(tt, d["w2"], 3, 3, stride=u.stride, pad=(1, 1), want_stats=True)
             del tt
             cnt = z.numel() // u.depth
-            s2, t2 = self._finalize(zst, cnt, u.res_layer[4])
+            s2, t2 = self._norm().encoder_finalize(zst, cnt, u.res_layer[4])
             if u.cin != u.depth:
                 sz, sst = ops.conv2d(y, d["ws"], 1, 1, stride=u.stride, want_stats=True)
-                ss, stt = self._finalize(sst, cnt, u.shortcut_layer[1])
+                ss, stt = self._norm().encoder_finalize(sst, cnt, u.shortcut_layer[1])
                 y, xst = ops.bn_apply_nhwc(z, s2, t2, res=sz, res_scale=ss, res_shift=stt, want_stats=True)
             else:
                 y, xst = ops.bn_apply_nhwc(z, s2, t2, res=y, res_stride=u.stride, want_stats=True)
@@ -1041,12 +1012,13 @@ class IR50(nn.Module):
                                          y.device)
         if plan is not None:
             return self._released_head(y, head_mask)
-        s0, t0 = self._finalize(xst, y.numel() // c, self.output_layer[0])
+        s0, t0 = self._norm().encoder_finalize(xst, y.numel() // c, self.output_layer[0])
         hfeat = ops.bn_apply_nhwc(y, s0, t0, mask=head_mask)
         k = h * w * c
         fc = self.output_layer[3]
         e = ops.linear(hfeat.view(n, k), P["head_w"], bias=fc.bias.detach(), split_k=self._head_split_k(n, k))
-        e = self._head_bn(e)
+        bn1 = self.output_layer[4]
+        e = self._norm().rows_fwd(e, bn1.weight.detach(), bn1.bias.detach(), *_buffers(bn1))[0]
         torch._foreach_add_([m.num_batches_tracked for m in self.modules()
                              if isinstance(m, (nn.BatchNorm2d, nn.BatchNorm1d))], 1)
         return ops.l2norm_rows(e)

@@ -164,19 +164,10 @@ int cer_from_n16(const uint16_t *x, float *out, size_t n, int storage, void *str
  * (reference models/arcface_model.py:44-60; PReLU :54, BatchNorm2d :53,57):
  *   cer_prelu_split        t = prelu(x) -> split
  *   cer_prelu_bwd_split    torch's PReLU backward; dx as fp32 (dx) and / or split (dx_hi, dx_lo); dalpha_terms as cer_prelu_bwd
- *   cer_bn_rows_bwd_split  cer_bn_rows_bwd (train mode, dense rows) with dx as a split tensor; workspace as cer_col_sum */
+ * (cer_bn_rows_bwd_apply writes the BatchNorm backward's dx as a split tensor, or with the shortcut branch's gradient added.) */
 int cer_prelu_split(const float *x, const float *alpha, uint16_t *hi, uint16_t *lo, size_t rows, int C, void *stream);
 int cer_prelu_bwd_split(const float *dy, const float *x, const float *alpha, float *dx, uint16_t *dx_hi, uint16_t *dx_lo,
                         float *dalpha_terms, size_t rows, int C, void *stream);
-int cer_bn_rows_bwd_split(const float *dy, const float *x, const float *save_mean, const float *save_invstd, const float *w,
-                          uint16_t *dx_hi, uint16_t *dx_lo, float *dw, float *db, int R, int C, void *workspace,
-                          size_t workspace_bytes, void *stream);
-/* cer_bn_rows_bwd (train mode, dense rows, C % 4 == 0) with an addend: dx = BatchNorm-backward(dy) + add (add may be NULL; it may
- * alias dx).  The gradient of a unit's input is the sum of its residual branch (through the unit's first BatchNorm) and its
- * shortcut branch (models/arcface_model.py:58-60): one pass instead of a BatchNorm-backward pass and an add pass. */
-int cer_bn_rows_bwd_add(const float *dy, const float *x, const float *save_mean, const float *save_invstd, const float *w,
-                        const float *add, float *dx, float *dw, float *db, int R, int C, void *workspace, size_t workspace_bytes,
-                        void *stream);
 
 /* v' = v*scale[c]+shift[c] (channels-last, C channels; scale/shift may be NULL) -> (bf16(v'), bf16(v' - bf16(v'))),
  * round-to-nearest-even on both parts. */
@@ -298,10 +289,6 @@ int cer_prelu_bwd(const float *dy, const float *x, const float *alpha, float *dx
  * sum_r ((b[r][c]-mean[c])*invstd[c])^2; deterministic tree.
  * Bias gradients and the BatchNorm / LayerNorm parameter gradients. */
 size_t cer_col_sum_workspace_bytes(int R, int C);
-/* db = sum dy, dw = sum dy * (x - mean) * invstd over dense rows [R, C] -- the two reductions of the train-mode BatchNorm
- * backward -- in ONE pass over dy and x when C % 4 == 0 and R spans several slabs (two passes otherwise); workspace as cer_col_sum */
-int cer_bn_bwd_sums(const float *dy, const float *x, const float *save_mean, const float *save_invstd, float *db, float *dw,
-                    int R, int C, void *workspace, size_t workspace_bytes, void *stream);
 int cer_col_sum(const float *a, int a_ld, const float *b, int b_ld, const float *mean, const float *invstd,
                 float *out, int R, int C, void *workspace, size_t workspace_bytes, void *stream);
 
@@ -322,22 +309,25 @@ size_t cer_bn_rows_fwd_workspace_bytes(int R, int C);   /* 0 for R <= 2048; larg
 int cer_bn_rows_fwd(const float *x, int x_ld, const float *w, const float *b, float *running_mean,
                     float *running_var, float *save_mean, float *save_invstd, float *y, int y_ld,
                     int R, int C, int train, float eps, float momentum, void *workspace, size_t workspace_bytes, void *stream);
-int cer_bn_rows_bwd(const float *dy, int dy_ld, const float *x, int x_ld, const float *save_mean,
-                    const float *save_invstd, const float *w, float *dx, float *dw, float *db,
-                    int R, int C, int train, void *workspace, size_t workspace_bytes, void *stream);
 
-/* The train-mode row BatchNorm split at its statistics, so that a cross-rank exchange can sit between the local reduction
+/* The row BatchNorm split at its statistics, so that a cross-rank exchange can sit between the local reduction
  * and its use (synchronised BatchNorm over data-parallel ranks).  Forward:
  *   cer_bn_rows_moments  moments [3][C] float64 = (count, mean, M2 = sum (x - mean)^2) of the rows of x (pitch x_ld);
  *   cer_bn_rows_merge    K gathered moment blocks [K][3][C] merged in block order (Chan's pairwise update) -> save_mean,
  *                        save_invstd (1 / sqrt(var + eps), biased var) and, when non-NULL, the running update with the
  *                        unbiased variance of the union; every caller with the same blocks gets the same bits;
  *   cer_bn_rows_apply    y = (x - mean) * invstd * w + b, y with pitch y_ld (a column slice of a wider buffer).
- * Backward:
- *   cer_bn_rows_bwd_sums   sums [2][C] float32 = (sum dy, sum dy * x_hat) over the local rows -- db and dw of this rank, the
- *                          same reductions as cer_bn_rows_bwd; workspace as cer_col_sum;
- *   cer_bn_rows_bwd_apply  dx = w * invstd * (dy - (sum_dy + x_hat * sum_dy_xhat) / count) with sums and count of the
- *                          global batch, over the local rows. */
+ * Backward, in two calls so that the same exchange can sit between them (local BatchNorm: the local sums, count = R):
+ *   cer_bn_rows_bwd_sums   sums [2][C] float32 = (sum dy, sum dy * x_hat) over the local rows -- db and dw of this rank; one
+ *                          pass over dy and x when the rows are dense, C % 4 == 0 and R spans several slabs, two column sums
+ *                          otherwise; workspace as cer_col_sum;
+ *   cer_bn_rows_bwd_apply  train != 0: dx = w * invstd * (dy - (sum_dy + x_hat * sum_dy_xhat) / count) with sums and count of
+ *                          the batch the statistics were taken over, for the local rows; train == 0: dx = dy * w * invstd.
+ *                          The outputs given pick the pass: dx_hi and dx_lo -> dx as a split tensor (hi / lo bf16 planes);
+ *                          else add -> fp32 dx = BatchNorm-backward(dy) + add (add may alias dx), the gradient of a released
+ *                          encoder unit's input as the sum of its residual branch (through the unit's first BatchNorm) and
+ *                          its shortcut branch (models/arcface_model.py:58-60) in one pass; else fp32 dx with pitches dy_ld /
+ *                          x_ld.  The split and addend forms are train mode over dense rows, C % 4 == 0, 16-byte aligned. */
 int cer_bn_rows_moments(const float *x, int x_ld, int R, int C, double *moments, void *stream);
 int cer_bn_rows_merge(const double *moments, int K, int C, float eps, float momentum, float *save_mean, float *save_invstd,
                       float *running_mean, float *running_var, void *stream);
@@ -346,23 +336,15 @@ int cer_bn_rows_apply(const float *x, int x_ld, const float *mean, const float *
 int cer_bn_rows_bwd_sums(const float *dy, int dy_ld, const float *x, int x_ld, const float *save_mean, const float *save_invstd,
                          float *sums, int R, int C, void *workspace, size_t workspace_bytes, void *stream);
 int cer_bn_rows_bwd_apply(const float *dy, int dy_ld, const float *x, int x_ld, const float *save_mean,
-                          const float *save_invstd, const float *w, const float *sums, double count, float *dx, int R, int C,
-                          void *stream);
-/* The same split for the released encoder units' row BatchNorms (dense rows, C % 4 == 0, 16-byte aligned):
+                          const float *save_invstd, const float *w, const float *sums, double count, int train,
+                          const float *add, float *dx, uint16_t *dx_hi, uint16_t *dx_lo, int R, int C, void *stream);
+/* The forward statistics of the released encoder units' row BatchNorms (dense rows, C % 4 == 0, 16-byte aligned):
  *   cer_bn_rows_moments_large  moments [3][C] float64 like cer_bn_rows_moments, for any R (up to 51 M rows and R * C > 2^31):
  *                              ONE read of x by many row slabs, each summing about its own first row in fp32, then the slab
  *                              partials merged in float64 in a fixed order (deterministic); workspace of
- *                              cer_bn_rows_moments_large_workspace_bytes(R, C) bytes;
- *   cer_bn_rows_bwd_apply_split  the apply pass of cer_bn_rows_bwd_split (dx as hi / lo bf16 planes) from given sums [2][C]
- *                              (sum dy | sum dy * x_hat) over count rows;
- *   cer_bn_rows_bwd_apply_add  the apply pass of cer_bn_rows_bwd_add (fp32 dx, optional addend) from given sums over count rows.
- * With the local sums of cer_bn_rows_bwd_sums and count == R the two apply passes write the unsynchronised entry points' bits. */
+ *                              cer_bn_rows_moments_large_workspace_bytes(R, C) bytes. */
 size_t cer_bn_rows_moments_large_workspace_bytes(int R, int C);
 int cer_bn_rows_moments_large(const float *x, int R, int C, double *moments, void *workspace, size_t workspace_bytes, void *stream);
-int cer_bn_rows_bwd_apply_split(const float *dy, const float *x, const float *save_mean, const float *save_invstd, const float *w,
-                                const float *sums, double count, uint16_t *dx_hi, uint16_t *dx_lo, int R, int C, void *stream);
-int cer_bn_rows_bwd_apply_add(const float *dy, const float *x, const float *save_mean, const float *save_invstd, const float *w,
-                              const float *sums, double count, const float *add, float *dx, int R, int C, void *stream);
 
 /* LFAN cross-modal attention core (reference models/transformer.py:11-19,133-159): for each
  * (row, head) an M x M softmax over MODALITIES, vals = softmax(q k^T/sqrt(hd)) v + v.

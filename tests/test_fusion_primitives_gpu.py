@@ -435,7 +435,7 @@ def _bn_bounds(x, w, b, rstd_ref, mean_ref, y_ref):
     return tol_mean, tol_inv, tol_y, Dv
 
 
-BN_CASES = [  # (R, C, x layout, id): every statistics path of cer_bn_rows_fwd and both of cer_bn_rows_bwd
+BN_CASES = [  # (R, C, x layout, id): every statistics path of cer_bn_rows_fwd and both of cer_bn_rows_bwd_sums
     (2, 36, "dense", "R2"),                          # kernel path, unbiased-variance denominator R - 1 = 1
     (300, 70, "dense", "small"),                     # one-block statistics kernel; bwd fallback (C % 4 != 0)
     (300, 36, "dense", "small_pair"),                # one-block statistics; bwd pair path (R > 256)

@@ -395,7 +395,7 @@ def test_prelu_fwd_bwd_vs_autograd():
 
 def test_fused_split_passes_equal_the_two_pass_forms():
     """Round 3: PReLU forward / backward and the BatchNorm backward's apply pass write the Split tensor the matrix-core kernels
-    read in the same pass (cer_prelu_split, cer_prelu_bwd_split, cer_bn_rows_bwd_split).  Same arithmetic as "fp32 result, then
+    read in the same pass (cer_prelu_split, cer_prelu_bwd_split, cer_bn_rows_bwd_apply).  Same arithmetic as "fp32 result, then
     cer_split_bf16": the PReLU forms bit for bit, the BatchNorm form to fp32 rounding (the two kernels contract a*b+c differently)."""
     from feature_vs_text_compound_emotion_amd import ops
     gen = torch.Generator().manual_seed(12)

@@ -101,10 +101,10 @@ def test_new_batchnorm_wrappers_reject_bad_arguments_before_launching():
         lambda: ops.bn_rows_moments_large(torch.zeros(4, c, dtype=torch.float64)),
         lambda: ops.bn_rows_moments_large(torch.zeros(4, c)[:, :6]),
         lambda: ops.bn_rows_moments_large(torch.zeros(c)),
-        lambda: ops.bn_rows_bwd_apply_fused(x, x, v, v, v, sums, 4),
-        lambda: ops.bn_rows_bwd_apply_fused(x, x, v, v, v, sums, 4, split_out=True),
-        lambda: ops.bn_rows_bwd_apply_fused(x, x, v, v, v, sums, 4, add=x),
-        lambda: ops.bn_rows_bwd_apply_fused(x, x, v, v, None, sums, 4),
+        lambda: ops.bn_rows_bwd_apply(x, x, v, v, v, sums, 4),
+        lambda: ops.bn_rows_bwd_apply(x, x, v, v, v, sums, 4, split_out=True),
+        lambda: ops.bn_rows_bwd_apply(x, x, v, v, v, sums, 4, add=x),
+        lambda: ops.bn_rows_bwd_apply(x, x, v, v, None, sums, 4),
     ]
     for call in calls:
         with pytest.raises(ValueError):

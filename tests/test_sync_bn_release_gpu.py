@@ -1,7 +1,7 @@
 """Synchronised batch statistics through the RELEASED parts of the IR-50 encoder (``ClipDataParallel(sync_bn=...,
-sync_released=True)``): the large-row moments kernel and the fused backward apply passes against float64 and against the
-unsynchronised kernels, 2 gloo ranks x B/2 clips against 1 process x B clips with the reference's release groups and the
-whole encoder, the forced single-rank RCCL path and the agreed memory plan."""
+sync_released=True)``): the large-row moments kernel and the fused backward apply passes against float64, the synchronised
+backward of one rank against the local one, 2 gloo ranks x B/2 clips against 1 process x B clips with the reference's release
+groups and the whole encoder, the forced single-rank RCCL path and the agreed memory plan."""
 import math
 import os
 import socket
@@ -112,22 +112,57 @@ def _bwd_inputs(r, c, seed):
     return x, dy, w, add, sm, si
 
 
-def _check_fused_equal(r, c, seed):
-    from feature_vs_text_compound_emotion_amd import ops
-    x, dy, w, add, sm, si = _bwd_inputs(r, c, seed)
-    sums = ops.bn_rows_bwd_sums(dy, x, sm, si)
-    ref, dw, db = ops.bn_rows_bwd(dy, x, sm, si, w, split_out=True)
-    assert torch.equal(sums[0], db) and torch.equal(sums[1], dw)
-    got = ops.bn_rows_bwd_apply_fused(dy, x, sm, si, w, sums, r, split_out=True)
-    assert torch.equal(got.hi, ref.hi) and torch.equal(got.lo, ref.lo)
-    del ref, got
-    ref, _, _ = ops.bn_rows_bwd(dy, x, sm, si, w, add=add)
-    assert torch.equal(ops.bn_rows_bwd_apply_fused(dy, x, sm, si, w, sums, r, add=add), ref)
+BWD_CASES = [(2049, 64), (40000, 256), (1000003, 512)]
 
 
-@pytest.mark.parametrize("r,c", [(2049, 64), (40000, 256), (1000003, 512)])
-def test_fused_backward_apply_with_local_sums_is_the_unsynchronised_pass_bit_for_bit(r, c):
-    _check_fused_equal(r, c, seed=r)
+def _child_one_rank_backward(rank, port, cases, out):
+    """``BatchNormSync.rows_bwd`` on a one-rank RCCL group against ``BatchNormLocal.rows_bwd`` in the three output forms: the
+    all-reduced sums over R x 1 rows drive the same apply pass as the local sums over R rows."""
+    os.environ.update(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                      HSA_ENABLE_IPC_MODE_LEGACY="0")
+    import sys
+    sys.modules.setdefault("triton", None)
+    import torch.distributed as dist
+    from feature_vs_text_compound_emotion_amd.batchnorm import LOCAL
+    from feature_vs_text_compound_emotion_amd.data_parallel import BatchNormSync, init_process_group_from_env
+    init_process_group_from_env(backend="nccl", single_rank_group=True)
+    sync = BatchNormSync(dist.new_group(), 1, 0)
+    res = {}
+    for r, c, seed in cases:
+        x, dy, w, add, sm, si = _bwd_inputs(r, c, seed)
+        for form, kw in (("fp32", {}), ("split", {"split_out": True}), ("add", {"add": add})):
+            ref, got = LOCAL.rows_bwd(dy, x, sm, si, w, **kw), sync.rows_bwd(dy, x, sm, si, w, **kw)
+            dx_equal = (torch.equal(got[0].hi, ref[0].hi) and torch.equal(got[0].lo, ref[0].lo) if form == "split"
+                        else torch.equal(got[0], ref[0]))
+            res[(r, c, form)] = (dx_equal, torch.equal(got[1], ref[1]), torch.equal(got[2], ref[2]))
+            del ref, got
+            torch.cuda.empty_cache()
+    out.update(res)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _one_rank_backward(cases):
+    ctx = mp.get_context("spawn")
+    with ctx.Manager() as mgr:
+        out = mgr.dict()
+        mp.spawn(_child_one_rank_backward, args=(_free_port(), cases, out), nprocs=1, join=True)
+        return dict(out)
+
+
+def _check_one_rank_equal(res, r, c):
+    for form in ("fp32", "split", "add"):
+        assert res[(r, c, form)] == (True, True, True), (r, c, form, res[(r, c, form)])
+
+
+@pytest.fixture(scope="module")
+def one_rank_backward():
+    return _one_rank_backward([(r, c, r) for r, c in BWD_CASES])
+
+
+@pytest.mark.parametrize("r,c", BWD_CASES)
+def test_one_rank_synchronised_backward_is_the_local_backward_bit_for_bit(one_rank_backward, r, c):
+    _check_one_rank_equal(one_rank_backward, r, c)
 
 
 def test_at_the_timed_size():
@@ -137,8 +172,7 @@ def test_at_the_timed_size():
     _check_against_local(x, seed=12)
     del x
     torch.cuda.empty_cache()
-    _check_fused_equal(r, c, seed=13)
-    torch.cuda.empty_cache()
+    _check_one_rank_equal(_one_rank_backward([(r, c, 13)]), r, c)
 
 
 @pytest.mark.parametrize("r,c", [(2049, 64), (40000, 256)])
@@ -151,8 +185,8 @@ def test_fused_backward_apply_with_summed_sums_of_two_blocks_matches_float64_aut
     blocks = [(x[:r].contiguous(), dy[:r].contiguous()), (x[r:].contiguous(), dy[r:].contiguous())]
     sm, si = ops.bn_rows_merge(torch.stack([ops.bn_rows_moments_large(xb) for xb, _ in blocks]), eps=EPS)
     sums = sum(ops.bn_rows_bwd_sums(dyb, xb, sm, si) for xb, dyb in blocks)
-    dx = torch.cat([ops.bn_rows_bwd_apply_fused(dyb, xb, sm, si, w, sums, 2 * r, add=None) for xb, dyb in blocks])
-    dxs = torch.cat([ops.bn_rows_bwd_apply_fused(dyb, xb, sm, si, w, sums, 2 * r, split_out=True).float()
+    dx = torch.cat([ops.bn_rows_bwd_apply(dyb, xb, sm, si, w, sums, 2 * r, add=torch.zeros_like(dyb)) for xb, dyb in blocks])
+    dxs = torch.cat([ops.bn_rows_bwd_apply(dyb, xb, sm, si, w, sums, 2 * r, split_out=True).float()
                      for xb, dyb in blocks])
     x64 = x.double().requires_grad_(True)
     y = torch.nn.functional.batch_norm(x64, None, None, w.double(), b.double(), training=True, eps=EPS)
