@@ -294,8 +294,7 @@ class VGGish(nn.Module):
         lm = ops.logmel(pcm.contiguous(), sample_rate, self._mel, 0.01)  # pad = one second of edge samples
         win = int(round(window_sec * 100.0))
         starts = example_starts(lm.shape[1], win, hop_sec * 100.0)
-        st = torch.tensor(starts, dtype=torch.int32, device=dev)
-        return ops.frame_examples(lm, st, win)
+        return ops.frame_examples(lm, starts, win)   # host list: bounds-checked there before the launch
 
 
 class AudioBackbone(nn.Module):

@@ -209,9 +209,12 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(AttnArgs p) {
 //             tiles (K, V in LDS):      dQ^T += K^T dS^T
 //   DKV mode: a wave OWNS 32 keys (K, V in registers) and streams query tiles (Q, dO in LDS; LSE,
 //             Delta per register row):  dV^T += dO^T P,  dK^T += Q^T dS
-// with S = (owner1 . streamed1) * scale, P = exp(S - LSE[query]), dP = owner2 . streamed2,
+// with S = K . (Q * scale), P = exp(S - LSE[query]), dP = owner2 . streamed2,
 // dS = P * (dP - Delta[query]) * scale.  Both modes recompute S/P, so no atomics are needed and the
 // result is deterministic.  Delta = rowsum(dO * O) comes from attn_delta_kernel.
+// S is formed exactly as the forward forms it -- Q rounded once after the scale, the same products summed in the same
+// order -- so P is consistent with the saved LSE and its rows sum to 1: scaling the finished product instead leaves a
+// score difference of |S| * 2^-23 or so between the two passes, which at |S| ~ 100 is 1e-5 relative on every P.
 struct AttnBwdArgs {
     const float *q, *k, *v, *dout, *lse, *delta;
     const int *key_mask;
@@ -270,6 +273,10 @@ __global__ __launch_bounds__(256, 1) void attention_bwd_kernel(AttnBwdArgs p) {
     float my_lse = INFINITY, my_delta = 0.f;
     bool my_keyok = true;
     if (!DKV) {
+        // the owner is Q and feeds only S: pre-scale it like the forward's Q fragment
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+            r1[g] = make_float4(r1[g].x * p.scale, r1[g].y * p.scale, r1[g].z * p.scale, r1[g].w * p.scale);
         if (ook) { my_lse = lse[orow]; my_delta = delta[orow]; }
     } else {
         my_keyok = ook && (!mbase || mbase[orow] != 0);
@@ -339,14 +346,16 @@ __global__ __launch_bounds__(256, 1) void attention_bwd_kernel(AttnBwdArgs p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
         const float *a1 = &T1[l31 * KP + 4 * half], *a2 = &T2[l31 * KP + 4 * half];
+        // DKV streams Q (the tile itself stays unscaled: it is also the operand of dK^T += Q^T dS)
+        const float qscale = DKV ? p.scale : 1.f;
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             const float4 x = *reinterpret_cast<const float4 *>(a1 + 8 * g);
             const float4 y = *reinterpret_cast<const float4 *>(a2 + 8 * g);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x, r1[g].x, s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(x.y, r1[g].y, s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(x.z, r1[g].z, s, 0, 0, 0);
-            s = __builtin_amdgcn_mfma_f32_32x32x2f32(x.w, r1[g].w, s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(x.x * qscale, r1[g].x, s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(x.y * qscale, r1[g].y, s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(x.z * qscale, r1[g].z, s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x2f32(x.w * qscale, r1[g].w, s, 0, 0, 0);
             dp = __builtin_amdgcn_mfma_f32_32x32x2f32(y.x, r2[g].x, dp, 0, 0, 0);
             dp = __builtin_amdgcn_mfma_f32_32x32x2f32(y.y, r2[g].y, dp, 0, 0, 0);
             dp = __builtin_amdgcn_mfma_f32_32x32x2f32(y.z, r2[g].z, dp, 0, 0, 0);
@@ -366,7 +375,7 @@ __global__ __launch_bounds__(256, 1) void attention_bwd_kernel(AttnBwdArgs p) {
                 const int key = t0 + srow;
                 ok = ook && key < p.Sk && (!mbase || mbase[key] != 0);
             }
-            const float pr = ok ? expf(s[r] * p.scale - l) : 0.f;
+            const float pr = ok ? expf(s[r] - l) : 0.f;
             s[r] = pr;                                   // P
             dp[r] = pr * (dp[r] - dl) * p.scale;         // dS (already times the score scale)
         }

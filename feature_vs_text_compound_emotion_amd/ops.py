@@ -1446,20 +1446,40 @@ def logmel(pcm_int16, pad_samples, mel_matrix_f64, log_offset=0.01):
         raise ValueError("mel matrix: expected a contiguous [257, 64] float64 GPU tensor")
     lib = _lib.load()
     clips, n = pcm_int16.shape
-    frames = lib.cer_logmel_num_frames(n, pad_samples)
+    frames = lib.cer_logmel_num_frames(n, pad_samples) if n > 0 and pad_samples >= 0 else 0
+    if frames <= 0:
+        raise ValueError(f"logmel: {n} samples + {pad_samples} of padding are shorter than one 400-sample frame")
     out = torch.empty((clips, frames, 64), device=pcm_int16.device, dtype=torch.float32)
     check(lib.cer_logmel_fwd(ptr(pcm_int16), clips, n, pad_samples, ptr(mel_matrix_f64), log_offset, ptr(out),
                              current_stream()), "cer_logmel_fwd")
     return out
 
 
-def frame_examples(logmel_t, starts_i32, win=96):
-    """[clips, frames, 64] -> [clips, n_examples, win, 64] at the given start rows."""
+def frame_examples(logmel_t, starts, win=96):
+    """[clips, frames, 64] -> [clips, n_examples, win, 64] at the given start rows.
+
+    ``starts`` are HOST integers (a list, or a CPU integer tensor): the kernel reads ``logmel[starts[e] + f]`` unchecked,
+    so every start is checked against [0, frames - win] here, before the upload and the launch, without touching the
+    device.  A GPU tensor is refused: checking it would cost a synchronisation."""
     _dev_f32(logmel_t, "logmel")
-    if not (starts_i32.is_cuda and starts_i32.dtype == torch.int32 and starts_i32.is_contiguous()):
-        raise ValueError("starts: expected a contiguous int32 GPU tensor")
+    if logmel_t.dim() != 3 or logmel_t.shape[2] != 64:
+        raise ValueError(f"logmel: expected [clips, frames, 64], got {tuple(logmel_t.shape)}")
+    if isinstance(starts, torch.Tensor):
+        if starts.is_cuda or starts.is_floating_point() or starts.dim() != 1:
+            raise ValueError("starts: expected host integers (a list or a 1-D CPU integer tensor), so that they can be "
+                             "bounds-checked without a device synchronisation")
+        starts = starts.tolist()
+    starts = [int(s) for s in starts]
     clips, frames, _ = logmel_t.shape
-    n = starts_i32.numel()
+    win = int(win)
+    if not starts or win <= 0 or win > frames:
+        raise ValueError(f"frame_examples: need at least one start and 0 < win <= frames, got {len(starts)} starts, "
+                         f"win {win}, {frames} frames")
+    if min(starts) < 0 or max(starts) > frames - win:
+        raise ValueError(f"frame_examples: starts must lie in [0, {frames - win}] ({frames} frames, win {win}), got "
+                         f"[{min(starts)}, {max(starts)}]")
+    n = len(starts)
+    starts_i32 = torch.tensor(starts, dtype=torch.int32).to(logmel_t.device, non_blocking=True)
     out = torch.empty((clips, n, win, 64), device=logmel_t.device, dtype=torch.float32)
     check(_lib.load().cer_frame_examples(ptr(logmel_t), ptr(starts_i32), ptr(out), clips, frames, n, win,
                                          current_stream()), "cer_frame_examples")

@@ -125,6 +125,13 @@ class BertEncoderHIP(nn.Module):
         """ids [B,S] int64, mask [B,S] (1 = token) -> sum of the last ``last_n_sum`` hidden states [B,S,768]."""
         packed = self._pack()
         dev = self.embeddings.word_embeddings.weight.device
+        if not input_ids.is_cuda and input_ids.numel():
+            # nn.Embedding raises on an id outside the table; the kernel clamps (include/cer_hip.h).  Ids that are still on
+            # the host are checked here for free; ids already on the GPU are not (that would be a synchronisation)
+            vocab = self.embeddings.word_embeddings.weight.shape[0]
+            lo, hi = int(input_ids.min()), int(input_ids.max())
+            if lo < 0 or hi >= vocab:
+                raise ValueError(f"input_ids out of range: [{lo}, {hi}] outside the {vocab}-row word-embedding table")
         ids = input_ids.to(dev).long().contiguous()
         b, s = ids.shape
         mask = None if attention_mask is None else attention_mask.to(dev).to(torch.int32).contiguous()

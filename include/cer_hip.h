@@ -474,12 +474,17 @@ int cer_logmel_num_frames(int num_samples, int pad_samples);
 int cer_logmel_fwd(const int16_t *pcm, int clips, int num_samples, int pad_samples, const double *mel_matrix,
                    float log_offset, float *logmel, void *stream);
 /* examples[c][e][f][:] = logmel[c][starts[e]+f][:] (my_frame, mel_features.py:21-49; the caller
- * computes `starts` with the reference's round-half-to-even rule). */
+ * computes `starts` with the reference's round-half-to-even rule).  `starts` is device memory and is NOT bounds-checked
+ * here: every start must lie in [0, frames_per_clip - win].  The tensor wrapper (ops.frame_examples) takes the starts as
+ * host integers, refuses any outside that range before the launch and uploads them itself. */
 int cer_frame_examples(const float *logmel, const int *starts, float *examples, int clips, int frames_per_clip,
                        int n_examples, int win, void *stream);
 
 /* BERT embeddings: y[b][s] = LayerNorm(word[ids[b][s]] + pos[s] + type[0]) (transformers
- * BertEmbeddings; reference call site abaw5_pre_processing/base/speech.py:603-606). ids int64. */
+ * BertEmbeddings; reference call site abaw5_pre_processing/base/speech.py:603-606). ids int64.
+ * An id outside [0, vocab) is CLAMPED to the nearest valid row (id < 0 reads row 0, id >= vocab reads row vocab - 1);
+ * nn.Embedding raises instead, which BertEncoderHIP.forward restates for ids that arrive on the host.  S > max_pos is
+ * CER_ERR_INVALID_ARG. */
 int cer_bert_embed_ln(const long long *ids, const float *word, const float *pos, const float *type,
                       const float *gamma, const float *beta, float *y, int B, int S, int Hd, int vocab,
                       int max_pos, float eps, void *stream);
@@ -487,13 +492,19 @@ int cer_bert_embed_ln(const long long *ids, const float *word, const float *pos,
 /* out = softmax(q k^T * scale + key mask) v on the fp32 matrix cores (flash style, exact fp32).
  * Element (b, s, h, d) of a tensor sits at ptr + b*strides[0] + s*strides[1] + h*strides[2] + d.
  * key_mask [B][Sk] (1 = attend) or NULL.  D in {32, 64, 128}.  Replaces BertSelfAttention and the
- * nn.MultiheadAttention of the JMT/MT heads (reference models/model.py:716-750, 967-972). */
+ * nn.MultiheadAttention of the JMT/MT heads (reference models/model.py:716-750, 967-972).
+ * lse [B][H][Sq] (optional, dense) receives log(sum_k exp(score)) over the visible keys.
+ * Degenerate rows: a query with NO visible key (its batch row's mask is all zero) gets out = 0 and lse = +inf, never NaN
+ * (torch's softmax returns NaN there).  Rows query >= Sq of out / lse are never written, keys >= Sk never read. */
 int cer_attention_fwd(const float *q, const float *k, const float *v, const int *key_mask, float *out, float *lse,
                       int B, int H, int Sq, int Sk, int D, const long long *q_strides, const long long *k_strides,
                       const long long *v_strides, const long long *o_strides, float scale, void *stream);
 /* Backward of cer_attention_fwd (JMT/MT heads train through nn.MultiheadAttention).  lse [B,H,Sq] is the
  * forward's optional output; delta [B,H,Sq] is scratch.  Two recompute passes (one owning queries, one
- * owning keys), no atomics: deterministic. */
+ * owning keys), no atomics: deterministic.  dout may have other strides than out (do_strides).
+ * Degenerate rows: a query whose lse is +inf (no visible key) has P = exp(score - inf) = 0 everywhere, so its dq = 0 and it
+ * adds nothing to dk or dv; a masked key gets dk = dv = 0.  Every row < Sq of dq and < Sk of dk / dv is written (zeros
+ * included), no row beyond them is. */
 int cer_attention_bwd(const float *q, const float *k, const float *v, const float *out, const float *dout,
                       const float *lse, const int *key_mask, float *delta, float *dq, float *dk, float *dv,
                       int B, int H, int Sq, int Sk, int D, const long long *q_strides, const long long *k_strides,

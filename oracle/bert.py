@@ -54,9 +54,13 @@ def bert_hidden_states(ids, attention_mask, sd, num_layers=12, num_heads=12, pre
 
 
 def bert_token_features(ids, attention_mask, sd, **kw):
-    """Sum of the last four hidden states, [B,S,768] (speech.py:617-624)."""
+    """Sum of the last four hidden states, [B,S,768] (speech.py:617-624).  An encoder of fewer than three layers has fewer
+    than four states: then all of them are summed, the embedding output included (what BertEncoderHIP does)."""
     hs = bert_hidden_states(ids, attention_mask, sd, **kw)
-    return hs[-1] + hs[-2] + hs[-3] + hs[-4]
+    total = hs[-1]
+    for h in hs[-2:-5:-1]:      # hs[-2], hs[-3], hs[-4]: the order of the sum is kept, so twelve layers give the same bits
+        total = total + h
+    return total
 
 
 def exclude_padding(token_vecs_sum, attention_mask):
