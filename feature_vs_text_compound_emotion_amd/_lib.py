@@ -109,6 +109,8 @@ _SIGNATURES = {
     "cer_softmax_gate_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, _P]),
     "cer_logmel_num_frames": (c_int, [c_int, c_int]),
     "cer_logmel_fwd": (c_int, [_P, c_int, c_int, c_int, _P, c_float, _P, _P]),
+    "cer_logmel_f64_fwd": (c_int, [_P, c_int, c_int, _P, c_float, _P, _P]),
+    "cer_resample_pcm": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "cer_frame_examples": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "cer_bert_embed_ln": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
     "cer_attention_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_float, _P]),

@@ -2,13 +2,16 @@
 
 Mirror of the reference's ``VGG`` / ``VGGish`` / ``AudioBackbone`` (models/backbone.py:16-66,
 133-145; pre-processing twin abaw5_pre_processing/base/vggish/vggish.py) and of the numpy front
-end ``waveform_to_examples`` / ``wavfile_to_examples`` (vggish_input.py:37-98): same state-dict
-keys (``features.N`` / ``embeddings.N``), ``forward(x [n,96,64]) -> [n,128]``.
+end ``waveform_to_examples`` / ``wavfile_to_examples`` (vggish_input.py:37-98), its channel mixdown
+and resampling to 16 kHz included: same state-dict keys (``features.N`` / ``embeddings.N``),
+``forward(x [n,96,64]) -> [n,128]``.
 
 Pipeline: the 1-channel stem conv reads the log-mel patch directly (small-Cin gather path), every
 conv fuses bias + ReLU, max-pools are NHWC kernels, and the reference's two transposes before the
 flatten are free because the activations already are (H, W, C).
 """
+import math
+
 import numpy as np
 import torch
 from torch import nn
@@ -51,6 +54,47 @@ def example_starts(num_frames, window_frames, hop_frames):
     """my_frame (mel_features.py:21-49): Python round() -> half to even, fractional hop."""
     n = 1 + int(np.floor((num_frames - window_frames) / hop_frames))
     return [round(hop_frames * i) for i in range(max(n, 0))]
+
+
+# resampy's windowed-sinc filters: (zero crossings per side, Kaiser beta, roll-off as a share of Nyquist)
+RESAMPLE_FILTERS = {"kaiser_best": (64, 14.769656459379492, 0.9475937167399596),
+                    "kaiser_fast": (16, 8.555504641634386, 0.85)}
+MAX_RESAMPLE_TAPS = 1 << 22
+
+
+def resampled_length(n_in, sr_in):
+    """resampy's output length: the Python float expression, not an integer floor (the two can differ by one)."""
+    return int(n_in * (float(SAMPLE_RATE) / sr_in))
+
+
+def resample_taps(sr_in, filter):
+    """Polyphase table of the band-limited interpolation  y[n] = scale sum_k x[k] h(scale (n / ratio - k)),
+    ratio = 16000 / sr_in, scale = min(1, ratio),  h(u) = rolloff sinc(rolloff u) I0(beta sqrt(1 - (u / zeros)^2)) / I0(beta)
+    inside |u| < zeros  (resampy.resample's definition with the continuous window: resampy itself interpolates linearly in
+    a sampled one).  With L / M = ratio in lowest terms, output n sits at input position q + r / L (q, r = divmod(n M, L)):
+    ``taps[r][j] = scale h(scale (r / L + J - j))`` multiplies input q - J + j, J = ceil(zeros / scale), j < T = 2 J + 2.
+    Returns (taps [L, T] float64, L, M).  At 16 kHz the reference does not filter at all: the table is the identity."""
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"unknown resampling filter {filter!r}: one of {sorted(RESAMPLE_FILTERS)}")
+    if int(sr_in) != sr_in or sr_in <= 0:
+        raise ValueError(f"sample rate must be a positive integer, got {sr_in!r}")
+    sr_in = int(sr_in)
+    if sr_in == SAMPLE_RATE:
+        return np.array([[1.0, 0.0]]), 1, 1
+    zeros, beta, rolloff = RESAMPLE_FILTERS[filter]
+    g = math.gcd(SAMPLE_RATE, sr_in)
+    L, M = SAMPLE_RATE // g, sr_in // g
+    scale = min(1.0, float(SAMPLE_RATE) / sr_in)
+    J = int(math.ceil(zeros / scale))
+    T = 2 * J + 2
+    if L * T > MAX_RESAMPLE_TAPS:
+        raise ValueError(f"resampling {sr_in} Hz -> {SAMPLE_RATE} Hz with {filter!r} needs a {L} x {T} tap table, more than "
+                         f"{MAX_RESAMPLE_TAPS} entries: resample to a rate with a larger common divisor first")
+    # r / L + J - j as ONE rounded quotient of an exact integer
+    u = scale * ((np.arange(L)[:, None] + (J - np.arange(T)[None, :]) * L) / float(L))
+    inside = np.abs(u) < zeros
+    window = np.i0(beta * np.sqrt(np.where(inside, 1.0 - (u / zeros) ** 2, 0.0))) / np.i0(beta)
+    return np.where(inside, scale * rolloff * np.sinc(rolloff * u) * window, 0.0), L, M
 
 
 def _fc_split_k(n):
@@ -129,6 +173,7 @@ class VGGish(nn.Module):
                                         nn.Linear(4096, 128))
         self._packed, self._key = None, None
         self._mel = None
+        self._taps = {}   # (sample rate, filter) -> (device tap table, L, M)
         # "bf16x3": convs 2-6 and the three FCs on the split-bf16 kernels (<= 2^-15 relative per product); "fp32": exact fp32;
         # "bf16" / "fp16": narrow storage (one 16-bit plane per tensor, one MFMA per product, fp32 accumulate) -- what the
         # reference's autocast computes (trainer.py:367) and BASELINE cfg5's "bf16" asks of the whole tri-modal step
@@ -280,18 +325,42 @@ class VGGish(nn.Module):
         return cur.view(n, 1, 1, k)
 
     # ---------------------------------------------------------------- front end
-    def wav_int16_to_examples(self, pcm_int16, sample_rate, window_sec=0.96, hop_sec=0.96):
+    def _resample_table(self, sample_rate, filter, dev):
+        hit = self._taps.get((sample_rate, filter))
+        if hit is None or hit[0].device != dev:
+            taps, L, M = resample_taps(sample_rate, filter)
+            hit = self._taps[(sample_rate, filter)] = (torch.from_numpy(taps).to(dev).contiguous(), L, M)
+        return hit
+
+    def wav_int16_to_examples(self, pcm_int16, sample_rate, window_sec=0.96, hop_sec=0.96, resample=None):
         """wavfile_to_examples for PCM already in memory: pcm [clips, S] (or [S]) int16 at 16 kHz ->
-        [clips, n_examples, 96, 64] float32 on the GPU."""
-        if sample_rate != SAMPLE_RATE:
-            raise ValueError("no resampler on the HIP path: feed 16 kHz PCM (the reference resamples with resampy)")
+        [clips, n_examples, 96, 64] float32 on the GPU.
+
+        With ``resample`` = "kaiser_best" / "kaiser_fast" any positive integer rate and interleaved multi-channel PCM
+        [clips, S, C] are taken as well: channel mean, one second of edge padding at the input rate, band-limited
+        interpolation to 16 kHz (``resample_taps``), then the log-mel on the float64 samples."""
+        if resample is None:
+            if sample_rate != SAMPLE_RATE:
+                raise ValueError(f"{sample_rate} Hz PCM needs resample='kaiser_best' or 'kaiser_fast' (the reference resamples "
+                                 "with resampy); without it only 16 kHz is taken")
+        elif resample not in RESAMPLE_FILTERS:
+            raise ValueError(f"unknown resampling filter {resample!r}: one of {sorted(RESAMPLE_FILTERS)}")
+        elif int(sample_rate) != sample_rate or sample_rate <= 0:
+            raise ValueError(f"sample rate must be a positive integer, got {sample_rate!r}")
         dev = self.features[0].weight.device
         pcm = torch.as_tensor(pcm_int16).to(dev)
         if pcm.dim() == 1:
             pcm = pcm[None]
         if self._mel is None or self._mel.device != dev:
             self._mel = torch.from_numpy(mel_matrix()).to(dev).contiguous()
-        lm = ops.logmel(pcm.contiguous(), sample_rate, self._mel, 0.01)  # pad = one second of edge samples
+        if resample is None or (sample_rate == SAMPLE_RATE and pcm.dim() == 2):
+            lm = ops.logmel(pcm.contiguous(), sample_rate, self._mel, 0.01)  # pad = one second of edge samples
+        else:
+            sample_rate = int(sample_rate)
+            taps, L, M = self._resample_table(sample_rate, resample, dev)
+            n_out = resampled_length(pcm.shape[1] + sample_rate, sample_rate)
+            samples = ops.resample_pcm(pcm.contiguous(), pcm.dim() == 3, sample_rate, taps, L, M, n_out)
+            lm = ops.logmel_f64(samples, self._mel, 0.01)
         win = int(round(window_sec * 100.0))
         starts = example_starts(lm.shape[1], win, hop_sec * 100.0)
         return ops.frame_examples(lm, starts, win)   # host list: bounds-checked there before the launch

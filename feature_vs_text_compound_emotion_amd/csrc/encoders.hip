@@ -7,6 +7,9 @@
 //    float64 for the DFT and the mel product (MI355X has a full-rate fp64 vector pipe and the
 //    whole front end is ~11 MFLOP per clip), and rounds to fp32 only at the output, exactly
 //    where the reference casts for the VGGish input.
+//  * resampling: interleaved int16 PCM at any rate -> channel mean -> edge pad -> band-limited sinc interpolation to
+//    16 kHz through a host-built polyphase tap table (what resampy.resample does for the reference,
+//    vggish_input.py:51-56), float64 throughout; its output feeds the float64 instantiation of the log-mel.
 //  * example framing: gather 96-frame windows at host-computed start rows (the reference's
 //    fractional hop uses Python's round-half-to-even, vggish_input.py:77-81 / my_frame).
 //  * BERT embeddings: word + position + token-type gather fused with LayerNorm(eps 1e-12).
@@ -18,20 +21,24 @@ namespace cer {
 
 constexpr int LM_WIN = 400, LM_HOP = 160, LM_FFT = 512, LM_BINS = 257, LM_MEL = 64;
 
+__device__ __forceinline__ double lm_sample(int16_t v) { return (double)v / 32768.0; }
+__device__ __forceinline__ double lm_sample(double v) { return v; }   // already in [-1, 1): the resampler's output
+
 // One block per STFT frame.  Direct DFT with an LDS twiddle table: 257 bins x 400 taps.
-__global__ __launch_bounds__(256) void logmel_kernel(const int16_t *__restrict__ pcm, int num_samples,
+template <typename T>
+__global__ __launch_bounds__(256) void logmel_kernel(const T *__restrict__ pcm, int num_samples,
                                                      int frames_per_clip, const double *__restrict__ mel,
                                                      float log_offset, float *__restrict__ out) {
     __shared__ double xs[LM_WIN];
     __shared__ double cs[LM_FFT], sn[LM_FFT];
     __shared__ double mag[LM_BINS + 3];
     const int clip = blockIdx.y, frame = blockIdx.x, tid = threadIdx.x;
-    const int16_t *src = pcm + (size_t)clip * num_samples;
+    const T *src = pcm + (size_t)clip * num_samples;
     for (int n = tid; n < LM_WIN; n += 256) {
         int idx = frame * LM_HOP + n;
         idx = idx < num_samples ? idx : num_samples - 1;  // np.pad(..., 'edge')
         const double w = 0.5 - 0.5 * cospi(2.0 * (double)n / (double)LM_WIN);
-        xs[n] = ((double)src[idx] / 32768.0) * w;
+        xs[n] = lm_sample(src[idx]) * w;
     }
     for (int j = tid; j < LM_FFT; j += 256) {
         double s, c;
@@ -55,6 +62,50 @@ __global__ __launch_bounds__(256) void logmel_kernel(const int16_t *__restrict__
         for (int k = 0; k < LM_BINS; ++k) acc += mag[k] * mel[k * LM_MEL + tid];
         out[((size_t)clip * frames_per_clip + frame) * LM_MEL + tid] = (float)log(acc + (double)log_offset);
     }
+}
+
+constexpr int RS_BLOCK = 256, RS_WIN = 2048;
+
+// out[c][n] = sum_j taps[r][j] * x[c][q - J + j] with q = (n M) div L, r = (n M) mod L, J = (T - 2) / 2, where
+// x[c][k] is the channel mean of pcm[c][k][:] / 32768 for 0 <= k < S, the last of those for S <= k < S + pad (np.pad
+// 'edge', read by clamping the index like logmel_kernel) and zero outside.  One thread per output.  A block's 256
+// outputs read one contiguous run of inputs; it is mixed down once into LDS, RS_WIN samples at a time, so the LDS need
+// does not grow with M / L or T, and every thread still adds its taps in the order j = 0 .. T - 1.
+__global__ __launch_bounds__(RS_BLOCK) void resample_pcm_kernel(const int16_t *__restrict__ pcm, int S, int C, int pad,
+                                                                const double *__restrict__ taps, int L, int M, int T,
+                                                                int n_out, double *__restrict__ out) {
+    __shared__ double xs[RS_WIN];
+    const int clip = blockIdx.y, tid = threadIdx.x;
+    const long long n_first = (long long)blockIdx.x * RS_BLOCK;
+    const long long n_last = (n_first + RS_BLOCK < n_out ? n_first + RS_BLOCK : (long long)n_out) - 1;
+    const long long n = n_first + tid;
+    const long long nl = n <= n_last ? n : n_last;   // threads past the end shadow the last output and store nothing
+    const long long J = (T - 2) / 2;
+    const long long k0 = n_first * M / L - J;                 // first input the block reads
+    const long long span = n_last * M / L - J + T - k0;       // ... and how many
+    const long long d = nl * M / L - J - k0;                  // this thread's first input, relative to k0
+    const double *row = taps + (size_t)((nl * M) % L) * T;
+    const int16_t *src = pcm + (size_t)clip * S * C;
+    const long long padded = (long long)S + pad;
+    double acc = 0.0;
+    for (long long w = 0; w < span; w += RS_WIN) {
+        const int fill = (int)(span - w < RS_WIN ? span - w : RS_WIN);
+        for (int i = tid; i < fill; i += RS_BLOCK) {
+            const long long k = k0 + w + i;
+            double v = 0.0;
+            if (k >= 0 && k < padded) {
+                const int16_t *p = src + (size_t)(k < S ? k : S - 1) * C;
+                for (int ch = 0; ch < C; ++ch) v += (double)p[ch] / 32768.0;
+                v /= (double)C;
+            }
+            xs[i] = v;
+        }
+        __syncthreads();
+        const long long j_lo = w > d ? w - d : 0, j_hi = w + fill - d < T ? w + fill - d : T;
+        for (long long j = j_lo; j < j_hi; ++j) acc += row[j] * xs[d + j - w];
+        __syncthreads();
+    }
+    if (n <= n_last) out[(size_t)clip * n_out + n] = acc;
 }
 
 // examples[c][e][f][:] = logmel[c][starts[e] + f][:]
@@ -118,8 +169,30 @@ extern "C" int cer_logmel_fwd(const int16_t *pcm, int clips, int num_samples, in
     const int frames = cer_logmel_num_frames(num_samples, pad_samples);
     if (!pcm || !mel_matrix || !logmel || clips <= 0 || num_samples <= 0 || pad_samples < 0 || frames <= 0)
         return cer_set_error(CER_ERR_INVALID_ARG, "logmel_fwd: bad argument (need at least 400 samples incl. padding)");
-    CER_LAUNCH(logmel_kernel, dim3(frames, clips), dim3(256), 0, (hipStream_t)stream, pcm, num_samples, frames, mel_matrix,
-               log_offset, logmel);
+    CER_LAUNCH(logmel_kernel<int16_t>, dim3(frames, clips), dim3(256), 0, (hipStream_t)stream, pcm, num_samples, frames,
+               mel_matrix, log_offset, logmel);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_logmel_f64_fwd(const double *samples, int clips, int num_samples, const double *mel_matrix,
+                                  float log_offset, float *logmel, void *stream) {
+    const int frames = cer_logmel_num_frames(num_samples, 0);
+    if (!samples || !mel_matrix || !logmel || clips <= 0 || clips > 65535 || num_samples <= 0 || frames <= 0)
+        return cer_set_error(CER_ERR_INVALID_ARG, "logmel_f64_fwd: bad argument (need at least 400 samples, <= 65535 clips)");
+    CER_LAUNCH(logmel_kernel<double>, dim3(frames, clips), dim3(256), 0, (hipStream_t)stream, samples, num_samples, frames,
+               mel_matrix, log_offset, logmel);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_resample_pcm(const int16_t *pcm, int clips, int num_samples, int channels, int pad_samples,
+                                const double *taps, int L, int M, int T, int n_out, double *out, void *stream) {
+    if (!pcm || !taps || !out || clips <= 0 || clips > 65535 || num_samples <= 0 || channels <= 0 || pad_samples < 0 ||
+        L <= 0 || M <= 0 || T < 2 || (T & 1) || n_out <= 0)
+        return cer_set_error(CER_ERR_INVALID_ARG, "resample_pcm: bad argument (taps [L][T] with T even, <= 65535 clips)");
+    CER_LAUNCH(resample_pcm_kernel, dim3(cer_blocks((size_t)n_out, RS_BLOCK), clips), dim3(RS_BLOCK), 0, (hipStream_t)stream,
+               pcm, num_samples, channels, pad_samples, taps, L, M, T, n_out, out);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }

@@ -42,9 +42,10 @@ class MultimodalFeatureExtractor(torch.nn.Module):
         self.fps = fps
 
     @torch.no_grad()
-    def audio_features(self, pcm_int16, num_frames, sample_rate=16000):
-        """pcm [B,S] int16 -> [B,1,L,128]."""
-        ex = self.audio.backbone.wav_int16_to_examples(pcm_int16, sample_rate, 0.96, 1.0 / self.fps)
+    def audio_features(self, pcm_int16, num_frames, sample_rate=16000, resample=None):
+        """pcm [B,S] int16 -> [B,1,L,128].  With ``resample`` ("kaiser_best" / "kaiser_fast") any ``sample_rate`` and
+        interleaved [B,S,C] PCM: mixed down and resampled to 16 kHz on the GPU (VGGish.wav_int16_to_examples)."""
+        ex = self.audio.backbone.wav_int16_to_examples(pcm_int16, sample_rate, 0.96, 1.0 / self.fps, resample=resample)
         b, n = ex.shape[:2]
         use = min(n, num_frames)
         emb = self.audio(ex[:, :use].reshape(b * use, 96, 64)).view(b, use, 128)
@@ -80,8 +81,9 @@ class MultimodalFeatureExtractor(torch.nn.Module):
         return rows.view(bsz, 1, num_frames, hd)
 
     @torch.no_grad()
-    def forward(self, frames, pcm_int16, token_ids, attention_mask, attention_mask_cpu=None):
+    def forward(self, frames, pcm_int16, token_ids, attention_mask, attention_mask_cpu=None, sample_rate=16000,
+                resample=None):
         """-> dict in the model's modality order {video, vggish, bert}."""
         length = frames.shape[1]
-        return {"video": frames, "vggish": self.audio_features(pcm_int16, length),
+        return {"video": frames, "vggish": self.audio_features(pcm_int16, length, sample_rate, resample),
                 "bert": self.text_features(token_ids, attention_mask, length, attention_mask_cpu)}

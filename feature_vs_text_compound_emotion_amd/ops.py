@@ -1455,6 +1455,50 @@ def logmel(pcm_int16, pad_samples, mel_matrix_f64, log_offset=0.01):
     return out
 
 
+def logmel_f64(samples_f64, mel_matrix_f64, log_offset=0.01):
+    """samples [clips, S] float64 in [-1, 1) at 16 kHz (``resample_pcm``'s output) -> log-mel [clips, frames, 64] float32.
+    No padding: the resampler has already read it."""
+    if not (samples_f64.is_cuda and samples_f64.dtype == torch.float64 and samples_f64.is_contiguous()
+            and samples_f64.dim() == 2):
+        raise ValueError("samples: expected a contiguous [clips, samples] float64 GPU tensor")
+    if not (mel_matrix_f64.is_cuda and mel_matrix_f64.dtype == torch.float64 and tuple(mel_matrix_f64.shape) == (257, 64)
+            and mel_matrix_f64.is_contiguous()):
+        raise ValueError("mel matrix: expected a contiguous [257, 64] float64 GPU tensor")
+    lib = _lib.load()
+    clips, n = samples_f64.shape
+    frames = lib.cer_logmel_num_frames(n, 0) if n > 0 else 0
+    if frames <= 0:
+        raise ValueError(f"logmel_f64: {n} samples are shorter than one 400-sample frame")
+    out = torch.empty((clips, frames, 64), device=samples_f64.device, dtype=torch.float32)
+    check(lib.cer_logmel_f64_fwd(ptr(samples_f64), clips, n, ptr(mel_matrix_f64), log_offset, ptr(out), current_stream()),
+          "cer_logmel_f64_fwd")
+    return out
+
+
+def resample_pcm(pcm_int16, channels_last, pad_samples, taps, L, M, n_out):
+    """pcm [clips, S] int16, or interleaved [clips, S, C] with ``channels_last`` -> [clips, n_out] float64: the channel
+    mean of pcm / 32768, ``pad_samples`` of edge padding, then out[n] = sum_j taps[(n M) mod L][j] * x[(n M) div L - J + j]
+    with J = (T - 2) / 2 and zeros outside the padded signal.  ``taps`` [L, T] float64 on the GPU
+    (``audio_backbone.resample_taps``); ``n_out`` is the caller's (``audio_backbone.resampled_length``)."""
+    want = 3 if channels_last else 2
+    if not (pcm_int16.is_cuda and pcm_int16.dtype == torch.int16 and pcm_int16.is_contiguous() and pcm_int16.dim() == want):
+        raise ValueError("pcm: expected a contiguous int16 GPU tensor, [clips, samples, channels] with channels_last, "
+                         "else [clips, samples]")
+    L, M, n_out, pad_samples = int(L), int(M), int(n_out), int(pad_samples)
+    if not (taps.is_cuda and taps.dtype == torch.float64 and taps.is_contiguous() and taps.dim() == 2
+            and taps.shape[0] == L and taps.shape[1] >= 2 and taps.shape[1] % 2 == 0):
+        raise ValueError("taps: expected a contiguous [L, T] float64 GPU tensor with T even")
+    clips, n = pcm_int16.shape[:2]
+    channels = pcm_int16.shape[2] if channels_last else 1
+    if min(clips, n, channels, L, M, n_out) <= 0 or pad_samples < 0:
+        raise ValueError(f"resample_pcm: empty input or bad sizes (pcm {tuple(pcm_int16.shape)}, L {L}, M {M}, "
+                         f"n_out {n_out}, pad {pad_samples})")
+    out = torch.empty((clips, n_out), device=pcm_int16.device, dtype=torch.float64)
+    check(_lib.load().cer_resample_pcm(ptr(pcm_int16), clips, n, channels, pad_samples, ptr(taps), L, M, taps.shape[1],
+                                       n_out, ptr(out), current_stream()), "cer_resample_pcm")
+    return out
+
+
 def frame_examples(logmel_t, starts, win=96):
     """[clips, frames, 64] -> [clips, n_examples, win, 64] at the given start rows.
 

@@ -473,6 +473,20 @@ int cer_gather_rows(const float *src, const int64_t *index, float *out, int n_ou
 int cer_logmel_num_frames(int num_samples, int pad_samples);
 int cer_logmel_fwd(const int16_t *pcm, int clips, int num_samples, int pad_samples, const double *mel_matrix,
                    float log_offset, float *logmel, void *stream);
+/* The same log-mel on samples that already are float64 in [-1, 1) (the output of cer_resample_pcm), with no padding:
+ * samples [clips][num_samples] -> logmel [clips][cer_logmel_num_frames(num_samples, 0)][64].  One kernel template, two
+ * sample types; clips <= 65535. */
+int cer_logmel_f64_fwd(const double *samples, int clips, int num_samples, const double *mel_matrix, float log_offset,
+                       float *logmel, void *stream);
+/* Mixdown + edge padding + polyphase resampling ahead of the log-mel (vggish_input.py:51-56,93-98; the reference calls
+ * resampy.resample): pcm [clips][num_samples][channels] int16 ->
+ *   x[k] = mean over channels of pcm[k][:] / 32768 for k < num_samples, x[num_samples - 1] for the `pad_samples` after
+ *   that, 0 outside;   out[c][n] = sum_j taps[r][j] * x[q - J + j],  q = (n M) div L, r = (n M) mod L, J = (T - 2) / 2
+ * in float64.  taps [L][T] float64 (T even, >= 2) is device memory built by the caller
+ * (audio_backbone.resample_taps: a Kaiser-windowed sinc at the L phases); out [clips][n_out] float64; clips <= 65535.
+ * Any n_out is memory-safe: inputs outside the padded signal read as zero. */
+int cer_resample_pcm(const int16_t *pcm, int clips, int num_samples, int channels, int pad_samples, const double *taps,
+                     int L, int M, int T, int n_out, double *out, void *stream);
 /* examples[c][e][f][:] = logmel[c][starts[e]+f][:] (my_frame, mel_features.py:21-49; the caller
  * computes `starts` with the reference's round-half-to-even rule).  `starts` is device memory and is NOT bounds-checked
  * here: every start must lie in [0, frames_per_clip - win].  The tensor wrapper (ops.frame_examples) takes the starts as
