@@ -15,6 +15,8 @@ namespace cer {
 
 // out[f][c] = (sum over windows w covering frame f, in window order, of win[w][f - start_w][c]) / (number of such windows)
 // -- the reference adds window after window into a zero tensor and divides at the end; same order, same rounding.
+// A frame that no window covers is 0 here and NaN (0 / 0) in the reference: eval_device.py refuses such a window set
+// before the launch, so the kernel never sees one.
 __global__ void window_stitch_kernel(const float *__restrict__ win, const int *__restrict__ starts, int nw, int Lw, int C,
                                      int total, float *__restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -61,11 +63,18 @@ __global__ void window_stitch_multi_kernel(const float *__restrict__ win, const 
     out[i] = cnt > 0 ? s / (float)cnt : 0.f;
 }
 
+// numpy.argmax: the first NaN if there is one (NaN propagates through numpy's maximum), otherwise the first maximum.
+// A NaN needs no NaN logit: softmax without max subtraction gives inf / inf for a logit above ~88.7 and 0 / 0 for a row
+// whose expf all underflow.
 __device__ __forceinline__ int argmax_first(const float *z, int n) {
     int b = 0;
     float m = z[0];
-    for (int c = 1; c < n; ++c)
-        if (z[c] > m) { m = z[c]; b = c; }   // first maximum, like numpy.argmax
+    if (m != m) return 0;
+    for (int c = 1; c < n; ++c) {
+        const float x = z[c];
+        if (x != x) return c;
+        if (x > m) { m = x; b = c; }
+    }
     return b;
 }
 
@@ -89,8 +98,10 @@ __global__ void frame_confusion_kernel(const float *__restrict__ logits, const f
 // Video level: one block per video (rows [off[v], off[v+1]) of the concatenated logits).  The three decisions of
 // metrics.py:118-139: majority vote over the frame predictions (ties: the class that reaches the winning count and
 // was seen FIRST, like collections.Counter.most_common), argmax of the mean logits, argmax of the mean of
-// softmax(logits) (no max subtraction, like the reference).  A video whose frames carry different labels is an error in
-// the reference (assert len(unique) == 1): counted in `bad`.
+// softmax(logits) (no max subtraction, like the reference: a logit above ~88.7 makes that column's mean NaN, which
+// argmax_first then picks as numpy.argmax does).  A video whose frames carry different labels is an error in the
+// reference (assert len(unique) == 1): counted in `bad`.  `off` must rise strictly from 0 to the number of rows:
+// DeviceEvalAccumulator.add checks that on the host, nothing here does.
 __global__ __launch_bounds__(256) void video_confusion_kernel(const float *__restrict__ logits, const float *__restrict__ labels,
                                                               const int *__restrict__ off, int C, int ignore_class,
                                                               unsigned long long *__restrict__ cm3, int *__restrict__ vpred,

@@ -14,8 +14,17 @@ from ._lib import check, current_stream, ptr
 from .metrics import (CFUSE_MATRIX, CL_ACC, FRAME_LEVEL, FRM_AVG_LOGITS, FRM_AVG_PROBS, FRM_VOTE, MACRO_F1, VIDEO_LEVEL, W_F1)
 
 
+def _check_coverage(what, starts, lw, total):
+    """Every frame of a ``total``-frame video lies in one of the ``lw``-frame windows at ``starts`` (all inside the video).  The
+    reference divides by the overlap count, so an uncovered frame is 0 / 0 = NaN there; the kernels would write 0."""
+    s = sorted(starts)
+    if not s or s[0] > 0 or s[-1] + lw < total or any(b - a > lw for a, b in zip(s, s[1:])):
+        raise ValueError(f"{what}: the {lw}-frame windows starting at {s} leave frames of the {total}-frame video uncovered")
+
+
 def stitch_windows(win_out, starts, total):
-    """win_out [nw, Lw, C] (GPU), starts: list of window start frames -> [total, C]; trainer.py:832-892 in one launch."""
+    """win_out [nw, Lw, C] (GPU), starts: list of window start frames -> [total, C]; trainer.py:832-892 in one launch.
+    The windows must lie inside the video and cover every frame of it (checked here, before the launch)."""
     if not (isinstance(win_out, torch.Tensor) and win_out.is_cuda and win_out.dtype == torch.float32 and win_out.dim() == 3):
         raise ValueError("stitch_windows: expected a [n_windows, window_length, n_classes] float32 GPU tensor")
     nw, lw, c = win_out.shape
@@ -24,6 +33,7 @@ def stitch_windows(win_out, starts, total):
         raise ValueError(f"stitch_windows: {nw} windows but {len(starts)} start frames (one video per call)")
     if nw and (min(starts) < 0 or max(starts) + lw > total):
         raise ValueError(f"stitch_windows: a window of {lw} frames starting at {max(starts)} leaves the {total}-frame video")
+    _check_coverage("stitch_windows", starts, lw, total)
     st = torch.tensor(list(starts), dtype=torch.int32, device=win_out.device)
     out = torch.empty((total, c), device=win_out.device, dtype=torch.float32)
     check(_lib.load().cer_window_stitch(ptr(win_out.contiguous()), ptr(st), nw, lw, c, total, ptr(out), current_stream()),
@@ -32,10 +42,14 @@ def stitch_windows(win_out, starts, total):
 
 
 def _offsets(name, offsets, end):
+    """A list (or tensor / array, brought to the host in one copy) of at least two offsets that start at 0, rise strictly
+    and, with ``end``, stop there."""
+    if isinstance(offsets, (torch.Tensor, np.ndarray)):
+        offsets = offsets.reshape(-1).tolist()
     offsets = [int(o) for o in offsets]
     if len(offsets) < 2 or offsets[0] != 0 or any(b <= a for a, b in zip(offsets, offsets[1:])) or \
             (end is not None and offsets[-1] != end):
-        raise ValueError(f"stitch_windows_multi: {name} must rise strictly from 0"
+        raise ValueError(f"{name} must rise strictly from 0"
                          + ("" if end is None else f" to {end}") + f", got {offsets}")
     return offsets
 
@@ -45,15 +59,16 @@ def stitch_windows_multi(win_out, starts, win_offsets, frame_offsets):
     video v owns windows ``win_offsets[v]:win_offsets[v+1]``, whose start frames ``starts`` are relative to the video, and rows
     ``frame_offsets[v]:frame_offsets[v+1]`` of the result [R = frame_offsets[-1], C] -- the concatenation
     ``DeviceEvalAccumulator.add(..., video_offsets=frame_offsets)`` takes.  Every row is bit-identical to ``stitch_windows`` on
-    its video alone.  All arguments are checked here, before the launch."""
+    its video alone.  All arguments are checked here, before the launch: the offsets, that every window lies inside its video
+    and that every frame of every video lies in a window."""
     if not (isinstance(win_out, torch.Tensor) and win_out.is_cuda and win_out.dtype == torch.float32 and win_out.dim() == 3):
         raise ValueError("stitch_windows_multi: expected a [n_windows, window_length, n_classes] float32 GPU tensor")
     nw, lw, c = win_out.shape
     starts = [int(s) for s in starts]
     if len(starts) != nw:
         raise ValueError(f"stitch_windows_multi: {nw} windows but {len(starts)} start frames")
-    woff = _offsets("win_offsets", win_offsets, nw)
-    foff = _offsets("frame_offsets", frame_offsets, None)
+    woff = _offsets("stitch_windows_multi: win_offsets", win_offsets, nw)
+    foff = _offsets("stitch_windows_multi: frame_offsets", frame_offsets, None)
     if len(woff) != len(foff):
         raise ValueError(f"stitch_windows_multi: {len(woff) - 1} videos in win_offsets, {len(foff) - 1} in frame_offsets")
     for v in range(len(woff) - 1):
@@ -62,6 +77,7 @@ def stitch_windows_multi(win_out, starts, win_offsets, frame_offsets):
             if starts[w] < 0 or starts[w] + lw > total:
                 raise ValueError(f"stitch_windows_multi: window {w} ({lw} frames from {starts[w]}) leaves video {v} "
                                  f"({total} frames)")
+        _check_coverage(f"stitch_windows_multi: video {v}", starts[woff[v]:woff[v + 1]], lw, total)
     dev = win_out.device
     st = torch.tensor(starts, dtype=torch.int32, device=dev)
     wo = torch.tensor(woff, dtype=torch.int32, device=dev)
@@ -101,7 +117,8 @@ class DeviceEvalAccumulator:
 
     def add(self, logits, labels, video_offsets=None):
         """logits [R, C] float32 GPU, labels [R] (float or long) GPU; ``video_offsets`` = row offsets [V+1] when several
-        videos are concatenated (default: one video)."""
+        videos are concatenated (default: one video): a list, or a tensor read in one copy, that starts at 0, rises strictly
+        and ends at R.  The kernel reads rows ``video_offsets[v]:video_offsets[v+1]`` unchecked, so anything else is refused here."""
         if not (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == self.c):
             raise ValueError("logits: expected a [R, n_classes] float32 GPU tensor")
         if not (isinstance(labels, torch.Tensor) and labels.is_cuda):
@@ -111,7 +128,8 @@ class DeviceEvalAccumulator:
         r = logits.shape[0]
         if labels.numel() != r:
             raise ValueError("one label per logits row")
-        off = torch.tensor([0, r] if video_offsets is None else list(video_offsets), dtype=torch.int32, device=logits.device)
+        offsets = [0, r] if video_offsets is None else _offsets("DeviceEvalAccumulator.add: video_offsets", video_offsets, r)
+        off = torch.tensor(offsets, dtype=torch.int32, device=logits.device)
         v = off.numel() - 1
         lib = _lib.load()
         for ic, cm in self.cm.items():

@@ -532,7 +532,9 @@ int cer_attention_bwd(const float *q, const float *k, const float *v, const floa
 
 /* Stitch the outputs of the sliding inference windows of ONE video (trainer.py:832-892): out[f][c] = sum over the windows
  * covering frame f, in window order, of win_out[w][f - starts[w]][c], divided by the number of such windows.
- * win_out [nw][Lw][C], starts [nw] (device int32), out [total][C]. */
+ * win_out [nw][Lw][C], starts [nw] (device int32), out [total][C].  The caller keeps every window inside the video and
+ * every frame inside a window (eval_device.py checks both before the launch): a frame no window covers is written as 0,
+ * where the reference's 0 / 0 gives NaN. */
 int cer_window_stitch(const float *win_out, const int *starts, int nw, int Lw, int C, int total, float *out, void *stream);
 
 /* cer_window_stitch for V videos in one launch.  win_out [nw][Lw][C] holds the videos' windows, video after video, each in
@@ -543,7 +545,9 @@ int cer_window_stitch_multi(const float *win_out, const int *win_start, const in
                             int V, int nw, int Lw, int C, int R, float *out, void *stream);
 
 /* Accumulate (+=) the confusion counts of a batch of V videos: logits [R][C] (the videos' frames concatenated), labels [R]
- * (float class ids), video_offsets [V+1] (device int32 row offsets).  frame_cm [C][C]: counts[label][argmax]; video_cm
+ * (float class ids), video_offsets [V+1] (device int32 row offsets; the caller makes them rise strictly from 0 to R, the
+ * kernels read rows [video_offsets[v], video_offsets[v+1]) unchecked).  Every argmax is numpy.argmax: the first NaN if
+ * there is one, otherwise the first maximum.  frame_cm [C][C]: counts[label][argmax]; video_cm
  * [3][C][C]: the same per video for the reference's three frame -> video decisions (majority vote / mean logits / mean
  * softmax probabilities, metrics.py:118-139); ignore_class >= 0 drops the LAST logit column and skips frames / videos
  * labelled ignore_class (C-EXPR-DB's 'Other', metrics.py:62-84); video_pred [V][3] (optional) receives the decisions;
