@@ -118,6 +118,10 @@ _SIGNATURES = {
     "cer_window_stitch": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "cer_window_stitch_multi": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "cer_eval_accumulate": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "cer_tanh_fwd": (c_int, [_P, _P, c_size_t, _P]),
+    "cer_tanh_bwd": (c_int, [_P, _P, _P, c_size_t, _P]),
+    "cer_ccc_loss": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "cer_regression_moments": (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     "cer_add_inplace": (c_int, [_P, _P, c_size_t, _P]),
     "cer_l2norm_rows": (c_int, [_P, _P, c_int, c_int, _P]),
     "cer_l2norm_rows_bwd": (c_int, [_P, _P, _P, c_int, c_int, _P]),

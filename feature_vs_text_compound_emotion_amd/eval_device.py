@@ -177,3 +177,70 @@ class DeviceEvalAccumulator:
                 put(VIDEO_LEVEL, k, scores_from_confusion(counts[1 + i]))
             out[ic] = perf
         return out
+
+
+class DeviceRegressionAccumulator:
+    """The regression task's scores (base/logger.py:274-351: RMSE, Pearson's r, Lin's CCC, per trial and over the concatenated
+    partition) from per-video moments gathered ON THE DEVICE.  Each ``add`` leaves one ``{n, mean_p, mean_l, M2_p, M2_l, C_pl,
+    SSE, 0}`` float64 row per video on the card (``cer_regression_moments``); ``compute`` brings all rows to the host in ONE
+    copy, scores every video from its row and folds the rows, in loader order, into the ``"overall"`` scores."""
+
+    def __init__(self, device="cuda"):
+        self.device = device
+        self.rows, self.keys = [], []        # [V, 8] float64 tensors; one (loader position, trial) per row
+
+    def add(self, outputs, labels, video_offsets=None, keys=None):
+        """outputs [R, 1] or [R] float32 GPU, labels [R] or [R, 1] GPU; ``video_offsets`` as ``DeviceEvalAccumulator.add``
+        takes them (default: one video).  ``keys``: one ``(loader position, trial)`` per video (default: the running video
+        count for both).  Everything is checked here, before the launch: the kernel reads rows unchecked, and a video of fewer
+        than two frames has no variance (the reference divides by ``len - 1``)."""
+        if not (isinstance(outputs, torch.Tensor) and outputs.is_cuda and outputs.dtype == torch.float32 and outputs.dim() in (1, 2)):
+            raise ValueError("outputs: expected a [R, 1] or [R] float32 GPU tensor")
+        if outputs.dim() == 2 and outputs.shape[1] != 1:
+            raise ValueError(f"outputs: output_dim = {outputs.shape[1]}, but the regression scores cover ONE output column "
+                             "(the reference scores column 0 only, base/logger.py:105-108)")
+        if not (isinstance(labels, torch.Tensor) and labels.is_cuda):
+            raise ValueError("labels: expected a GPU tensor (one label per output row)")
+        r = outputs.shape[0]
+        if labels.numel() != r:
+            raise ValueError("one label per output row")
+        offsets = [0, r] if video_offsets is None else _offsets("DeviceRegressionAccumulator.add: video_offsets", video_offsets, r)
+        short = [v for v, (a, b) in enumerate(zip(offsets, offsets[1:])) if b - a < 2]
+        if short:
+            raise ValueError(f"DeviceRegressionAccumulator.add: video(s) {short} have fewer than 2 frames (no variance)")
+        v = len(offsets) - 1
+        if keys is None:
+            keys = [(len(self.keys) + i,) * 2 for i in range(v)]
+        if len(keys) != v:
+            raise ValueError(f"DeviceRegressionAccumulator.add: {len(keys)} keys for {v} videos")
+        from . import ops
+        self.rows.append(ops.regression_moments(outputs.reshape(-1).contiguous(), labels.reshape(-1).float().contiguous(), offsets))
+        self.keys.extend((int(pos), trial) for pos, trial in keys)
+
+    def _host_rows(self):
+        if not self.rows:
+            return np.zeros((0, 8))
+        rows = [r if isinstance(r, torch.Tensor) else torch.as_tensor(r) for r in self.rows]
+        return (rows[0] if len(rows) == 1 else torch.cat(rows)).cpu().numpy().reshape(-1, 8)
+
+    def all_gather(self, group=None):
+        """Sharded evaluation: every rank receives every rank's moment rows with their loader positions; ``compute`` orders
+        them by position, so every rank folds the same rows in the same order and reports identical scores."""
+        import torch.distributed as dist
+        parts = [None] * dist.get_world_size(group)
+        dist.all_gather_object(parts, (list(self.keys), self._host_rows()), group=group)
+        self.keys = [k for keys, _ in parts for k in keys]
+        self.rows = [np.concatenate([rows for _, rows in parts])]
+
+    def compute(self):
+        """``{trial: {"rmse", "pcc", "ccc"}, ..., "overall": {...}}``.  Videos in loader order; a trial id that comes back
+        replaces the earlier video of that name, as in the per-video dictionary ``inference`` returns."""
+        from .metrics import OVERALL, fold_moments, scores_from_moments
+        rows = self._host_rows()
+        assert len(rows) == len(self.keys) and len(rows) > 0, (len(rows), len(self.keys))
+        by_trial = {}
+        for i in sorted(range(len(rows)), key=lambda i: self.keys[i][0]):
+            by_trial[self.keys[i][1]] = rows[i]
+        out = {trial: scores_from_moments(row) for trial, row in by_trial.items()}
+        out[OVERALL] = scores_from_moments(fold_moments(list(by_trial.values())))
+        return out

@@ -109,6 +109,20 @@ class LeakyReLUFn(torch.autograd.Function):
         return ops.act_mask_bwd(dy.contiguous(), ctx.y, None)
 
 
+class TanhFn(torch.autograd.Function):
+    """The REGRESSION output (models/model.py:523,681,1164): tanh with the backward from the saved output."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y = ops.tanh_fwd(x.contiguous())
+        ctx.y = y
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.tanh_bwd(dy.contiguous(), ctx.y)
+
+
 class SoftmaxGateFn(torch.autograd.Function):
     """out = softmax(z) * c (CAN's AttentionFusion gate)."""
 
@@ -361,7 +375,7 @@ class _TailModel(nn.Module):
         c = batchnorm_rows(c, self.bn1, self.training, self.bn_sync or LOCAL)
         c = linear(LeakyReLUFn.apply(c), self.fc2)
         c = c.view(bsz, length, -1)
-        return torch.tanh(c) if self.task == REGRESSION else c
+        return TanhFn.apply(c) if self.task == REGRESSION else c
 
 
 class JMT(_TailModel):

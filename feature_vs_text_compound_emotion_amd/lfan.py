@@ -2,7 +2,7 @@
 
 Mirror of the reference's ``LFAN`` (models/model.py:375-526), its
 ``MultimodalTransformerEncoder`` fusion (models/transformer.py:102-215) and the
-criterion ``nn.CrossEntropyLoss`` (experiment.py:133): same constructor
+criteria ``nn.CrossEntropyLoss`` (experiment.py:133) and ``CCCLoss`` (base/loss_function.py): same constructor
 arguments, ``.init()``, ``forward(dict) -> [B, L, n_cls]``, ``state_dict``
 keys, ``model.spatial['visual']``.
 
@@ -127,6 +127,27 @@ def cross_entropy_loss(outputs, labels):
     outputs [B,L,C] or [B*L,C]; labels float or long with B*L elements."""
     c = outputs.shape[-1]
     return CrossEntropyFunction.apply(outputs.reshape(-1, c), labels.reshape(-1).float())
+
+
+class CCCLossFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gold, pred):
+        loss, dp = ops.ccc_loss(gold.contiguous(), pred.contiguous(), want_grad=True)
+        ctx.dp = dp
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        return None, ctx.dp * gout
+
+
+def ccc_loss(gold, pred):
+    """The reference's ``CCCLoss()(gold, pred)`` (base/loss_function.py:6-24; gold first, as base/trainer.py:278 calls it) on
+    [B, L, D] tensors: the mean over all elements of ``1 - 2 (g - mean g)(p - mean p) / (var g + var p + (mean g - mean p)^2)``
+    with the statistics taken along L.  Inputs are cast to float32, so it also serves under the ``--amp`` autocast."""
+    if gold.dim() != 3 or tuple(gold.shape) != tuple(pred.shape):
+        raise ValueError(f"ccc_loss: expected gold and pred of one [B, L, D] shape, got {tuple(gold.shape)} and {tuple(pred.shape)}")
+    return CCCLossFunction.apply(gold.detach().float(), pred.float())
 
 
 class MultimodalMultiheadAttention(nn.Module):
@@ -309,5 +330,6 @@ class LFAN(nn.Module):
             X[m] = y.view(bsz, length, -1)
         out = logits.view(bsz, self.example_length, -1)
         if self.task == REGRESSION:
-            out = torch.tanh(out)
+            from .fusion_heads import TanhFn   # fusion_heads imports this module
+            out = TanhFn.apply(out)
         return out

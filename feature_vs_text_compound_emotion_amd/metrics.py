@@ -123,3 +123,80 @@ def compute_perf(data, ignore_classes=(None,)):
             perf[CFUSE_MATRIX][VIDEO_LEVEL][k] = {"master": cm, "per_cl": cm}
         out[ic] = perf
     return out
+
+
+# ------------------------------------------------------------------ the regression task (base/logger.py:213-246,274-351)
+OVERALL = "overall"
+RMSE, PCC, CCC = "rmse", "pcc", "ccc"
+
+
+def _pearson_p_value(r, n):
+    """Two-sided p-value of Pearson's r on n points (what ``scipy.stats.pearsonr`` reports: r is Beta(n/2 - 1, n/2 - 1) on
+    [-1, 1] under the null hypothesis); NaN when scipy is absent."""
+    try:
+        from scipy import stats
+    except ImportError:
+        return float("nan")
+    if n < 3 or not np.isfinite(r):
+        return 1.0 if n == 2 and np.isfinite(r) else float("nan")
+    ab = n / 2.0 - 1.0
+    return float(2.0 * stats.beta(ab, ab, loc=-1.0, scale=2.0).cdf(-abs(min(max(r, -1.0), 1.0))))
+
+
+def regression_scores(pred, label):
+    """``ContinuousMetricsCalculator.calculator`` for its three metrics on one pair of 1-D arrays, in float64:
+    ``{"rmse": sqrt(mean((p - l)^2)), "pcc": (r, p_value), "ccc": calculate_ccc(p, l)}`` -- Lin's CCC exactly as
+    base/logger.py:213-246 (biased covariance, variances over n - 1, ``+ 1e-100`` in the denominator).  ``p_value`` comes
+    from ``scipy.stats.pearsonr`` when scipy imports and is NaN otherwise."""
+    p, l = np.asarray(pred, dtype=np.float64).reshape(-1), np.asarray(label, dtype=np.float64).reshape(-1)
+    assert p.shape == l.shape and p.size >= 2, (p.shape, l.shape)
+    n = p.size
+    dp, dl = p - p.mean(), l - l.mean()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = float(np.sum(dp * dl) / np.sqrt(np.sum(dp * dp) * np.sum(dl * dl)))
+    try:
+        from scipy.stats import pearsonr
+        p_value = float(pearsonr(p, l)[1])
+    except ImportError:
+        p_value = float("nan")
+    ccc = 2.0 * np.mean(dp * dl) / (np.sum(dp * dp) / (n - 1) + np.sum(dl * dl) / (n - 1) + (p.mean() - l.mean()) ** 2 + 1e-100)
+    return {RMSE: float(np.sqrt(np.mean((p - l) ** 2))), PCC: (r, p_value), CCC: float(ccc)}
+
+
+def compute_regression_perf(per_video):
+    """``{trial: {"labels", "outputs"}}`` -> ``{trial: {"rmse", "pcc", "ccc"}, ..., "overall": {...}}`` like
+    ``ContinuousMetricsCalculator.calculate_metrics`` (base/logger.py:325-351): every trial on its own, then the trials'
+    arrays concatenated in the dictionary's (loader) order."""
+    out = {trial: regression_scores(v["outputs"], v["labels"]) for trial, v in per_video.items()}
+    def cat(key):
+        return np.concatenate([np.asarray(v[key], dtype=np.float64).reshape(-1) for v in per_video.values()])
+    out[OVERALL] = regression_scores(cat("outputs"), cat("labels"))
+    return out
+
+
+def fold_moments(rows):
+    """Rows ``{n, mean_p, mean_l, M2_p, M2_l, C_pl, SSE, 0}`` of consecutive segments -> the row of their concatenation, folded
+    in order with the pairwise centred update (Chan et al.): ``M2 += M2_b + delta^2 n_a n_b / n`` and likewise for C."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 8)
+    acc = rows[0].copy()
+    for b in rows[1:]:
+        na, nb = acc[0], b[0]
+        n = na + nb
+        dp, dl = b[1] - acc[1], b[2] - acc[2]
+        acc[3] += b[3] + dp * dp * na * nb / n
+        acc[4] += b[4] + dl * dl * na * nb / n
+        acc[5] += b[5] + dp * dl * na * nb / n
+        acc[1] += dp * nb / n
+        acc[2] += dl * nb / n
+        acc[6] += b[6]
+        acc[0] = n
+    return acc
+
+
+def scores_from_moments(row):
+    """One moment row -> the ``regression_scores`` dictionary of the frames it summarises."""
+    n, mp, ml, m2p, m2l, c, sse = (float(x) for x in np.asarray(row, dtype=np.float64)[:7])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = float(np.float64(c) / np.sqrt(np.float64(m2p) * np.float64(m2l)))
+    ccc = 2.0 * (c / n) / (m2p / (n - 1) + m2l / (n - 1) + (mp - ml) ** 2 + 1e-100)
+    return {RMSE: float(np.sqrt(sse / n)), PCC: (r, _pearson_p_value(r, int(n))), CCC: float(ccc)}

@@ -1409,6 +1409,63 @@ def leaky_relu(x, slope=LEAKY_SLOPE):
     return y
 
 
+def tanh_fwd(x):
+    """y = tanh(x) (evaluated in double, rounded once); any shape."""
+    _dev_f32(x, "x")
+    if x.numel() == 0:
+        raise ValueError("tanh_fwd: empty tensor")
+    y = torch.empty_like(x)
+    check(_lib.load().cer_tanh_fwd(ptr(x), ptr(y), x.numel(), current_stream()), "cer_tanh_fwd")
+    return y
+
+
+def tanh_bwd(dy, y):
+    """dx = dy * (1 - y^2) from the saved output ``y`` of ``tanh_fwd``."""
+    _dev_f32(y, "y")
+    _dev_f32(dy, "dy", shape=y.shape)
+    if y.numel() == 0:
+        raise ValueError("tanh_bwd: empty tensor")
+    dx = torch.empty_like(y)
+    check(_lib.load().cer_tanh_bwd(ptr(dy), ptr(y), ptr(dx), y.numel(), current_stream()), "cer_tanh_bwd")
+    return dx
+
+
+def ccc_loss(gold, pred, want_grad=True):
+    """The reference's ``CCCLoss()(gold, pred)`` (base/loss_function.py) on [B, L, D] float32 tensors: (loss scalar tensor,
+    d loss / d pred or None).  Double arithmetic, no atomics: two calls give identical bits."""
+    _dev_f32(gold, "gold")
+    _dev_f32(pred, "pred", shape=gold.shape)
+    if gold.dim() != 3 or gold.numel() == 0:
+        raise ValueError(f"ccc_loss: expected non-empty [B, L, D] tensors, got shape {tuple(gold.shape)}")
+    b, l, d = gold.shape
+    loss = _empty((), pred)
+    dpred = torch.empty_like(pred) if want_grad else None
+    ws = torch.empty((b * d,), device=pred.device, dtype=torch.float64)
+    check(_lib.load().cer_ccc_loss(ptr(gold), ptr(pred), ptr(loss), ptr(dpred), ptr(ws), b, l, d, current_stream()),
+          "cer_ccc_loss")
+    return loss, dpred
+
+
+def regression_moments(pred, label, video_offsets):
+    """pred, label [R] float32 (the frames of V videos, concatenated); ``video_offsets``: V+1 host integers rising strictly
+    from 0 to R (the kernel reads the rows unchecked, so anything else is refused here) -> [V, 8] float64
+    ``{n, mean_p, mean_l, M2_p, M2_l, C_pl, SSE, 0}``."""
+    _dev_f32(pred, "pred")
+    _dev_f32(label, "label", shape=pred.shape)
+    if pred.dim() != 1 or not 0 < pred.numel() < 2 ** 31:
+        raise ValueError(f"regression_moments: expected non-empty [R] tensors (R < 2^31), got shape {tuple(pred.shape)}")
+    off = [int(o) for o in video_offsets]
+    r = pred.numel()
+    if len(off) < 2 or off[0] != 0 or off[-1] != r or any(b <= a for a, b in zip(off, off[1:])):
+        raise ValueError(f"regression_moments: video_offsets must rise strictly from 0 to {r}, got {off}")
+    v = len(off) - 1
+    off_d = torch.tensor(off, dtype=torch.int32, device=pred.device)
+    out = torch.empty((v, 8), device=pred.device, dtype=torch.float64)
+    check(_lib.load().cer_regression_moments(ptr(pred), ptr(label), ptr(off_d), v, r, ptr(out), current_stream()),
+          "cer_regression_moments")
+    return out
+
+
 def softmax_gate_fwd(z, c):
     _dense2d(z, "z")
     _dev_f32(c, "c", shape=z.shape)

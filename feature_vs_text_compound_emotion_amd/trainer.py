@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import metrics
-from .lfan import cross_entropy_loss
+from .lfan import CLASSIFICATION, REGRESSION, TASKS, ccc_loss, cross_entropy_loss
 
 VIDEO, VGGISH, BERT, LOGMEL = "video", "vggish", "bert", "logmel"
 EXPR = "EXPR_continuous_label"
@@ -75,6 +75,14 @@ def _is_gpu(device):
     return torch.device(device).type == "cuda"
 
 
+def _task(task):
+    """None -> CLASSIFICATION; otherwise one of the reference's two task names (constants.py:17-20), any letter case."""
+    task = CLASSIFICATION if task is None else str(task).upper()
+    if task not in TASKS:
+        raise ValueError(f"task must be one of {TASKS}, got {task!r}")
+    return task
+
+
 class DeviceEvalMixin:
     """``inference`` / ``inference_forward_windows`` / ``window_input`` with the reference's signatures
     (trainer.py:436,788,832) on top of whatever trainer provides ``self.model``, ``self.device``, ``self.number_classes``,
@@ -90,7 +98,11 @@ class DeviceEvalMixin:
     share forwards -- groups of at most ``eval_frame_budget`` frames that may span videos -- and every ``eval_video_batch``
     videos are stitched with one launch and folded into the counts with one call.  ``self.eval_shard`` under an initialised
     ``torch.distributed`` with world > 1: rank r evaluates the videos at loader positions p % world == r, the device counts
-    are summed with one all-reduce and the per-video logits are gathered back into loader order."""
+    are summed with one all-reduce and the per-video logits are gathered back into loader order.
+
+    ``task`` = "REGRESSION" (``self.args.task`` or ``self.task``): the model's [1, n, 1] outputs go through the same windows,
+    stitch kernel, batching and sharding, and are scored with RMSE / Pearson's r / Lin's CCC per trial and overall
+    (``DeviceRegressionAccumulator``, or ``metrics.compute_regression_perf`` on the host path)."""
 
     eval_aggregate = None          # None -> "device" on a GPU, "host" otherwise
     eval_frame_budget = None
@@ -182,6 +194,8 @@ class DeviceEvalMixin:
         ``keep_logits`` (default ``self.eval_keep_logits`` = True, as the reference; False skips the per-video copies).
         ``eval_video_batch`` / ``eval_shard``: see the class docstring; the returned dictionary has the same keys in the
         same (loader) order either way."""
+        if _task(self._arg("task")) == REGRESSION:
+            return self._inference_regression(dataloader, keep_logits, aggregate)
         aggregate = self._aggregate(aggregate)
         keep_logits = self.eval_keep_logits if keep_logits is None else keep_logits
         video_batch = int(self.eval_video_batch or 1)
@@ -261,6 +275,94 @@ class DeviceEvalMixin:
         if acc is not None:
             return acc.compute(), per_video
         return metrics.compute_perf(per_video, self.ignore_classes), per_video
+
+
+    def _inference_regression(self, dataloader, keep_logits=None, aggregate=None):
+        """``inference`` for ``task`` = "REGRESSION" (the reference: base/trainer.py:262-313 with base/logger.py:89-129,274-351).
+        Returns ``(scores, {trial: {"labels", "outputs"}})`` with ``scores = {trial: {"rmse", "pcc", "ccc"}, ..., "overall":
+        {...}}``.  Device path: every video leaves one row of moments on the card and the scores come from one small copy at
+        the end; the per-video arrays are copied only when ``keep_logits``.  Windows, ``eval_video_batch`` and ``eval_shard``
+        work as in the classification path; the stitch kernel averages the overlapping windows' outputs."""
+        aggregate = self._aggregate(aggregate)
+        keep = self.eval_keep_logits if keep_logits is None else keep_logits
+        video_batch = int(self.eval_video_batch or 1)
+        if video_batch < 1:
+            raise ValueError(f"eval_video_batch must be >= 1, got {self.eval_video_batch!r}")
+        self.model.eval()
+        rank, world = self._eval_shard_rank_world()
+        entries = []                                      # (loader position, trial, {labels, outputs})
+        acc = None
+        if aggregate == "device":
+            from .eval_device import DeviceRegressionAccumulator
+            acc = DeviceRegressionAccumulator(device=self.device)
+        amp = bool(self._arg("amp", False)) and _is_gpu(self.device)
+        wlen = int(self._arg("window_length"))
+
+        def forward(batch):
+            with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
+                return self.model(batch)
+
+        batched = None
+        if acc is not None and video_batch > 1 and self._arg("model_name") == "LFAN":
+            budget = self.eval_frame_budget or max(1, int(self._arg("train_batch_size", 1))) * wlen
+            batched = _VideoWindowBatch(forward, max(1, budget // wlen))
+
+        def fold(outputs, labels, offsets, keys):
+            acc.add(outputs, labels, video_offsets=offsets, keys=keys)
+            if keep:
+                og, lb = outputs.reshape(-1).cpu().numpy(), labels.reshape(-1).float().cpu().numpy()
+                for (pos, trial), a, b in zip(keys, offsets, offsets[1:]):
+                    entries.append((pos, trial, {"labels": lb[a:b], "outputs": og[a:b]}))
+
+        for pos, (X, trials, lengths, indices) in enumerate(dataloader):
+            if pos % world != rank:
+                continue
+            inputs = {k: v.to(self.device) for k, v in X.items()}
+            labels = inputs.pop("continuous_label", None)
+            if labels is None:
+                labels = inputs.pop(EXPR, None)
+            nframes = 0
+            for m, t in inputs.items():
+                assert t.shape[0] == 1, f"{t.shape[0]} | {m}"
+                nframes = _num_frames(m, t)
+            assert tuple(labels.shape) == (1, nframes, 1), tuple(labels.shape)
+            labels = labels.float()
+            if batched is not None and nframes >= wlen:
+                batched.add((pos, trials[0]), self.window_input(inputs), labels)
+                if len(batched) >= video_batch:
+                    fold(*batched.flush())
+                continue
+            with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
+                if nframes > wlen and self._arg("model_name") == "LFAN":
+                    outputs = self.inference_forward_windows(inputs, aggregate)
+                else:
+                    outputs = self.model(inputs)
+            outputs = outputs.detach().float()
+            if outputs.shape[-1] != 1:
+                raise ValueError(f"output_dim = {outputs.shape[-1]}: the regression scores cover ONE output column (the "
+                                 "reference scores column 0 only, base/logger.py:105-108)")
+            assert tuple(outputs.shape) == tuple(labels.shape), (tuple(outputs.shape), tuple(labels.shape))
+            if acc is not None:
+                fold(outputs.reshape(-1), labels.reshape(-1), [0, nframes], [(pos, trials[0])])
+            else:
+                entries.append((pos, trials[0], {"labels": labels.reshape(-1).cpu().numpy(),
+                                                 "outputs": outputs.reshape(-1).cpu().numpy()}))
+        if batched is not None and len(batched):
+            fold(*batched.flush())
+        if world > 1:                                   # every rank takes part, with or without videos of its own
+            import torch.distributed as dist
+            if acc is not None:
+                acc.all_gather()
+            if keep or acc is None:
+                parts = [None] * world
+                dist.all_gather_object(parts, entries)
+                entries = [e for part in parts for e in part]
+        per_video = {}
+        for _, trial, entry in sorted(entries, key=lambda e: e[0]):   # loader order; a repeated trial id: the last one wins
+            per_video[trial] = entry
+        if acc is not None:
+            return acc.compute(), per_video
+        return metrics.compute_regression_perf(per_video), per_video
 
 
 class _VideoWindowBatch:
@@ -388,7 +490,7 @@ class Trainer(DeviceEvalMixin):
 
     def __init__(self, model=None, optimizer=None, criterion=None, device="cuda", window_length=300, hop_length=200,
                  model_name="LFAN", train_batch_size=2, number_classes=None, data_parallel=None, ignore_classes=(None,),
-                 **kwargs):
+                 task=None, **kwargs):
         if model is None:
             if "models" not in kwargs:
                 raise TypeError("Trainer needs the model: Trainer(model, ...) or Trainer(models=model, ...) as experiment.py does")
@@ -402,12 +504,14 @@ class Trainer(DeviceEvalMixin):
         self.model = model.to(device) if hasattr(model, "to") else model     # base/trainer.py:25
         self.optimizer, self.scheduler = optimizer, None
         self.scaler = None                               # the --amp GradScaler (trainer.py:341), one per train_one_epoch
-        self.criterion = criterion if criterion is not None else cross_entropy_loss
+        self._default_criterion = criterion is None      # then the criterion follows the task: cross entropy / CCC loss
+        self.criterion = criterion if criterion is not None else (ccc_loss if _task(task) == REGRESSION else cross_entropy_loss)
         self.model_name, self.train_batch_size = model_name, train_batch_size
         self.number_classes = number_classes if number_classes is not None else 7
         self.ddp, self.ignore_classes = data_parallel, tuple(ignore_classes)
         # trainer.py:436-523,832 read the window rule and model name from the argparse namespace
-        self.args = SimpleNamespace(window_length=window_length, hop_length=hop_length, model_name=model_name, amp=False)
+        self.args = SimpleNamespace(window_length=window_length, hop_length=hop_length, model_name=model_name, amp=False,
+                                    task=_task(task))
         self.epoch, self.counter, self.seed = 0, 0, 0
         self.dataloaders = None
         self.fit_finished = False
@@ -418,6 +522,7 @@ class Trainer(DeviceEvalMixin):
     # the short form's attribute names stay readable
     window_length = property(lambda self: self.args.window_length)
     hop_length = property(lambda self: self.args.hop_length)
+    task = property(lambda self: _task(self.args.task))
 
     # ------------------------------------------------------------------ the calls experiment.py:178-182 makes
     def set_args(self, args):
@@ -430,6 +535,8 @@ class Trainer(DeviceEvalMixin):
         self.args = args
         if getattr(args, "model_name", None):
             self.model_name = args.model_name
+        if self._default_criterion:
+            self.criterion = ccc_loss if self.task == REGRESSION else cross_entropy_loss
 
     def post_set_args(self, class_id=None):
         """trainer.py:95-105 loads ``<folds_dir>/split-<fold>/class_id.yaml``; the file belongs to the dataset folds, which
@@ -503,7 +610,7 @@ class Trainer(DeviceEvalMixin):
         forward and loss, then ``scaler.scale(loss).backward()``, the gradient all-reduce, ``scaler.step``, ``scaler.update``
         -- a step with a non-finite gradient is skipped and halves the scale, as the reference's GradScaler does."""
         inputs, labels = self._split(X)
-        if labels.numel() == self.train_batch_size:  # the reference's "todo : fix this." label hack (:360-363)
+        if self.task != REGRESSION and labels.numel() == self.train_batch_size:  # the reference's "todo : fix this." label hack (:360-363)
             n = len(indices[0]) if indices is not None else labels.shape[1]
             labels = torch.zeros((self.train_batch_size, n, 1), dtype=torch.float32, device=self.device)
         if self.ddp is not None:
@@ -513,10 +620,14 @@ class Trainer(DeviceEvalMixin):
         amp = self._train_amp()
         with torch.autocast("cuda", dtype=torch.float16) if amp else contextlib.nullcontext():
             outputs = self.model(inputs)
-            bsz, nfms, d = labels.shape
-            assert d == 1, d
-            assert outputs.ndim == 3 and tuple(outputs.shape) == (bsz, nfms, self.number_classes), tuple(outputs.shape)
-            loss = self.criterion(outputs.contiguous().view(bsz * nfms, -1), labels.contiguous().view(bsz * nfms).long())  # trainer.py:380-383
+            if self.task == REGRESSION:                  # base/trainer.py:278: float labels, [B, L, D], gold first
+                assert outputs.ndim == 3 and tuple(outputs.shape) == tuple(labels.shape), (tuple(outputs.shape), tuple(labels.shape))
+                loss = self.criterion(labels.float(), outputs)
+            else:
+                bsz, nfms, d = labels.shape
+                assert d == 1, d
+                assert outputs.ndim == 3 and tuple(outputs.shape) == (bsz, nfms, self.number_classes), tuple(outputs.shape)
+                loss = self.criterion(outputs.contiguous().view(bsz * nfms, -1), labels.contiguous().view(bsz * nfms).long())  # trainer.py:380-383
         if not amp:
             loss.backward()
             if self.ddp is not None:
@@ -548,7 +659,8 @@ class Trainer(DeviceEvalMixin):
 
     def optimize(self, dataloader_dict, checkpoint_controller=None, parameter_controller=None):
         """trainer.py:611-770 without its control plane: validate, ``max_epoch`` x (train epoch, scheduler step,
-        validate, remember the best weights by frame-level weighted F1), then test the best weights.  Returns
+        validate, remember the best weights by frame-level weighted F1 -- by the overall CCC when ``task`` is "REGRESSION",
+        base/trainer.py:174-176), then test the best weights.  Returns
         ``{"valid": [perf per evaluation], "loss": [epoch losses], "test": perf, "best_epoch": i}``."""
         self.dataloaders = dataloader_dict
         if self.optimizer is None:
@@ -556,6 +668,8 @@ class Trainer(DeviceEvalMixin):
         history = {"valid": [], "loss": []}
 
         def master(perf):
+            if self.task == REGRESSION:
+                return perf[metrics.OVERALL][metrics.CCC]
             return perf[self.ignore_classes[0]][metrics.W_F1][metrics.FRAME_LEVEL]["master"]
 
         def evaluate(loader, **kwargs):

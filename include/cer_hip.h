@@ -557,6 +557,35 @@ int cer_eval_accumulate(const float *logits, const float *labels, const int *vid
                         int ignore_class, unsigned long long *frame_cm, unsigned long long *video_cm, int *video_pred, int *bad,
                         void *stream);
 
+/* ------------------------------------------------------------------------
+ * The regression task (reference models/model.py:400,523,681,1164; base/loss_function.py; base/logger.py:213-351).
+ * ---------------------------------------------------------------------- */
+
+/* y = tanh(x), elementwise fp32 (the REGRESSION output of LFAN / CAN / JMT / MT).  tanh is evaluated in double and rounded
+ * once.  +-inf -> +-1, NaN -> NaN, |x| >= 20 -> exactly +-1.  Backward from the saved output: dx = dy * (1 - y * y), the
+ * product taken in double and rounded once. */
+int cer_tanh_fwd(const float *x, float *y, size_t n, void *stream);
+int cer_tanh_bwd(const float *dy, const float *y, float *dx, size_t n, void *stream);
+
+/* The reference's CCCLoss(gold, pred) with weights=None (base/loss_function.py:6-24) and its gradient with respect to pred.
+ * gold, pred [B][L][D] dense; *loss one float; dpred [B][L][D] or NULL; col_ws [B * D] doubles of scratch.  Per column
+ * (b, d), n = L: means gm, pm; S = sum (g - gm)(p - pm); Vg, Vp the unbiased variances; m = gm - pm; Q = Vg + Vp + m^2;
+ *   loss = (1 / N) sum over columns of (L - 2 S / Q),                                   N = B * L * D
+ *   dpred[j] = ( -2 (g_j - gm) / Q + (2 S / Q^2) (2 (p_j - pm) / (n - 1) - 2 m / n) ) / N.
+ * All sums are double: one 256-thread block per column (two passes, wave shuffles, fixed-order LDS tree), then one block
+ * adds the column terms in index order.  No atomics: two calls give identical bits.  The reference's `+ 1e-50` is 0 in its
+ * fp32 arithmetic and is not added: a column with Q = 0 (gold and pred the same constant) or L = 1 gives a NaN loss and a
+ * NaN gradient in THAT column only, as the reference does. */
+int cer_ccc_loss(const float *gold, const float *pred, float *loss, float *dpred, double *col_ws, int B, int L, int D,
+                 void *stream);
+
+/* Sufficient statistics of RMSE / Pearson's r / Lin's CCC per video: pred, label [R] (the frames of V videos, concatenated),
+ * video_offsets [V+1] (device int32; the caller makes them rise strictly from 0 to R, rows are read unchecked);
+ * moments [V][8] double = {n, mean_p, mean_l, M2_p, M2_l, C_pl, SSE, 0} with M2 / C the centred sums and
+ * SSE = sum (p - l)^2.  One block per video, two passes, double, fixed-order tree: deterministic. */
+int cer_regression_moments(const float *pred, const float *label, const int *video_offsets, int V, int R, double *moments,
+                           void *stream);
+
 /* y += x */
 int cer_add_inplace(float *y, const float *x, size_t n, void *stream);
 
