@@ -202,11 +202,16 @@ def _tcn_pair(cin, channels, k, seed):
     return net.cuda(), sd, alias
 
 
-@pytest.mark.parametrize("train", [False, True])
-def test_tcn_forward_backward_vs_oracle(train):
+# the second geometry: B = 1, L = 5, 40 -> [32, 32]: the first level takes the element-wise gather path (Cin = 40), the downsample
+# 1x1 is present, and every dilation above 1 reaches past the start of the sequence ((k - 1) * 2 = 8 >= L)
+_TCN_GEOMETRIES = {"": (128, [64, 64, 32, 32], 3, 16), "-gather40-L5": (40, [32, 32], 1, 5)}
+
+
+@pytest.mark.parametrize("train,geometry", [pytest.param(t, g, id=f"{t}{g}") for g in _TCN_GEOMETRIES for t in (False, True)])
+def test_tcn_forward_backward_vs_oracle(train, geometry):
     from feature_vs_text_compound_emotion_amd import synth
     from oracle.tcn import tcn_forward
-    cin, channels, k, bsz, length = 128, [64, 64, 32, 32], 5, 3, 16
+    (cin, channels, bsz, length), k = _TCN_GEOMETRIES[geometry], 5
     net, sd, alias = _tcn_pair(cin, channels, k, 21)
     g = torch.Generator().manual_seed(22)
     x = torch.randn(bsz, cin, length, generator=g, requires_grad=True)
