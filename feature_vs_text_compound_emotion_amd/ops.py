@@ -72,16 +72,121 @@ def pack_conv_weight(w_oihw, out_scale=None, flip=False, transpose=False):
     return out
 
 
+def _conv_desc(n, h, w, cin, cout, kh, kw, *, stride=1, dil=(1, 1), pad=(0, 0), out_hw=None, res_stride=1, Hr=0, Wr=0,
+               act1=ACT_NONE, act2=ACT_NONE, slope=LEAKY_SLOPE, split_k=1, tile=0, x_nchw=False, x_ld=0, y_ld=0,
+               storage=STORE_NONE, x_s2d=False, y_s2d=False, kpad=None):
+    """The cer_conv_desc of one conv: (n, h, w, cin) is the input TENSOR's shape, so under ``x_s2d`` (a space-to-depth
+    tensor) the conv's own input is [n, 2h, 2w, cin/4].  ``kpad``: the packed weight's K, checked against ``conv_kpad``
+    (the only library call in here; without it this is plain ctypes)."""
+    if x_s2d:
+        if cin % 4:
+            raise ValueError("a space-to-depth input has 4 * Cin channels")
+        h, w, cin = 2 * h, 2 * w, cin // 4
+    if kpad is not None and kpad != conv_kpad(kh, kw, cin):
+        raise ValueError(f"packed weight has K={kpad}, expected {conv_kpad(kh, kw, cin)}")
+    if out_hw is None:
+        ho = (h + 2 * pad[0] - dil[0] * (kh - 1) - 1) // stride + 1
+        wo = (w + 2 * pad[1] - dil[1] * (kw - 1) - 1) // stride + 1
+    else:
+        ho, wo = out_hw
+    d = ConvDesc()
+    d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = n, h, w, cin, ho, wo, cout
+    d.KH, d.KW, d.stride, d.dil_h, d.dil_w, d.pad_t, d.pad_l = kh, kw, stride, dil[0], dil[1], pad[0], pad[1]
+    d.x_nchw, d.res_stride, d.Hr, d.Wr = int(x_nchw), res_stride, Hr, Wr
+    d.act1, d.act2, d.slope, d.split_k, d.tile = act1, act2, slope, split_k, tile
+    d.x_ld, d.y_ld, d.storage, d.x_s2d, d.y_s2d = x_ld, y_ld, storage, int(x_s2d), int(y_s2d)
+    return d
+
+
+def _res_kind(res, name, split=False, n16=None):
+    """An optional residual as (fp32 tensor, hi or narrow plane, lo plane, Hr, Wr): an fp32 tensor always passes, a Split
+    where ``split`` is set (bf16x3 family), a narrow tensor of dtype ``n16`` where that is given (narrow family)."""
+    if res is None:
+        return None, None, None, 0, 0
+    hr, wr = res.shape[1], res.shape[2]
+    if split and isinstance(res, Split):
+        _dev_bf16(res.hi, f"{name}.hi")
+        return None, res.hi, res.lo, hr, wr
+    if n16 is not None and res.dtype != torch.float32:
+        _dev_n16(res, name, n16)
+        return None, res, None, hr, wr
+    _dev_f32(res, name)
+    return res, None, None, hr, wr
+
+
+def _conv_epilogue(d, io, bias, alpha, bias9, residual, split=False, n16=None):
+    """What the three conv wrappers check and marshal alike: the per-output-channel vectors, ``bias9`` and the residual
+    (kinds as in ``_res_kind``), written into ``d`` / ``io``."""
+    n, cout = d.N, d.Cout
+    for t, nme in ((bias, "bias"), (alpha, "alpha")):
+        _dev_f32(t, nme)
+        if t is not None:
+            if t.numel() != cout:
+                raise ValueError(f"{nme} has {t.numel()} elements, expected {cout}")
+            setattr(io, nme, t.data_ptr())
+    if bias9 is not None:
+        _dev_f32(bias9, "bias9")
+        if tuple(bias9.shape) != (9, cout):
+            raise ValueError("bias9 must be [9, Cout]")
+        io.bias9 = bias9.data_ptr()
+    if residual is not None:
+        if residual.shape[0] != n or residual.shape[3] != cout:
+            raise ValueError(f"residual shape {tuple(residual.shape)} does not match N={n}, Cout={cout}")
+        r32, hi, lo, d.Hr, d.Wr = _res_kind(residual, "residual", split, n16)
+        for name, t in (("residual", r32), ("res_hi", hi), ("res_lo", lo)):
+            if t is not None:
+                setattr(io, name, t.data_ptr())
+
+
+def _next_affine_out(io, res, next_affine, shape, device):
+    """The second Split output, out * s2 + t2, of the kernels with split outputs: allocated into ``res['next']``."""
+    s2, t2 = next_affine
+    _dev_f32(s2, "s2")
+    _dev_f32(t2, "t2")
+    res["next"] = Split.empty(shape, device)
+    io.s2, io.t2 = s2.data_ptr(), t2.data_ptr()
+    io.y2_hi, io.y2_lo = res["next"].hi.data_ptr(), res["next"].lo.data_ptr()
+
+
+# bench.py sets this to a list to time every bf16x3 / narrow conv launch with HIP events on the launch stream:
+# (kernel variant id, algorithmic FLOPs, start event, end event, algorithmic bytes)
+CONV_TRACE = None
+
+
+def _conv_run(d, io, family, device, trace=None, want_stats=False):
+    """The one launch of every conv wrapper (cer_conv2d_run).  Allocates the split-K workspace and, with ``want_stats``,
+    the [tiles,2,Cout] partial sums of kernel family ``family`` (0 fp32, 1 bf16x3, 2 narrow), which it returns.  ``trace``
+    = (name of the family's tile query, algorithmic bytes): the launch enters ``CONV_TRACE`` when that is a list."""
+    lib = _lib.load()
+    stats = None
+    if want_stats:
+        stats = torch.empty((lib.cer_conv2d_stats_tiles(ctypes.byref(d), family), 2, d.Cout), device=device, dtype=torch.float32)
+        io.stats = stats.data_ptr()
+    ws_bytes = lib.cer_conv2d_workspace_bytes(ctypes.byref(d))
+    ws = torch.empty((ws_bytes // 4,), device=device, dtype=torch.float32) if ws_bytes else None
+    traced = trace is not None and CONV_TRACE is not None
+    if traced:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    check(lib.cer_conv2d_run(ctypes.byref(d), ctypes.byref(io), ptr(ws), ws_bytes, current_stream()), "cer_conv2d_run")
+    if traced:
+        e1.record()
+        tile_query, nbytes = trace
+        CONV_TRACE.append((getattr(lib, tile_query)(ctypes.byref(d)), 2.0 * d.N * d.Ho * d.Wo * d.Cout * d.Cin * d.KH * d.KW,
+                           e0, e1, nbytes))
+    return stats
+
+
 def conv2d(x, w_packed, kh, kw, *, stride=1, dil=(1, 1), pad=(0, 0), out_hw=None, in_scale=None,
            in_shift=None, bias=None, alpha=None, residual=None, res_stride=1, mask=None, act1=ACT_NONE,
            act2=ACT_NONE, slope=LEAKY_SLOPE, split_k=1, x_nchw=False, tile=0, out=None, aux=None, x_ld=0, y_ld=0,
            x_shape=None, want_stats=False, out_split=False, next_affine=None, want_f32=True, out_n16=None):
     """y[N,Ho,Wo,Cout] = act2(mask*act1(conv(affine(x), w)+bias) + residual).  x is NHWC
     (or NCHW with ``x_nchw`` on the small-Cin path).  ``x_shape`` = (N,H,W,Cin) overrides
-    x.shape when x is a column slice (then ``x_ld`` is its row pitch)."""
-    lib = _lib.load()
-    for t, n in ((w_packed, "w"), (in_scale, "in_scale"), (in_shift, "in_shift"), (bias, "bias"),
-                 (alpha, "alpha"), (residual, "residual"), (mask, "mask"), (aux, "aux")):
+    x.shape when x is a column slice (then ``x_ld`` is its row pitch).  Returns y, or (y, stats) with ``want_stats``;
+    with ``out_split`` / ``next_affine`` (Split outputs: feeds the bf16x3 layers) or ``out_n16`` (a narrow output of that
+    dtype: the Cin = 3 stem of the narrow encoder) a dict with 'y', 'stats' and 'split' / 'next' / 'n16'."""
+    for t, n in ((w_packed, "w"), (in_scale, "in_scale"), (in_shift, "in_shift"), (mask, "mask"), (aux, "aux")):
         _dev_f32(t, n)
     _dev_f32(x, "x", contiguous=(x_ld == 0))
     if x_shape is not None:
@@ -91,77 +196,43 @@ def conv2d(x, w_packed, kh, kw, *, stride=1, dil=(1, 1), pad=(0, 0), out_hw=None
     else:
         n, h, w, cin = x.shape
     cout = w_packed.shape[0]
-    if w_packed.shape[1] != conv_kpad(kh, kw, cin):
-        raise ValueError(f"packed weight has K={w_packed.shape[1]}, expected {conv_kpad(kh, kw, cin)}")
-    if out_hw is None:
-        ho = (h + 2 * pad[0] - dil[0] * (kh - 1) - 1) // stride + 1
-        wo = (w + 2 * pad[1] - dil[1] * (kw - 1) - 1) // stride + 1
-    else:
-        ho, wo = out_hw
-    d = ConvDesc()
-    d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = n, h, w, cin, ho, wo, cout
-    d.KH, d.KW, d.stride, d.dil_h, d.dil_w, d.pad_t, d.pad_l = kh, kw, stride, dil[0], dil[1], pad[0], pad[1]
-    d.x_nchw = 1 if x_nchw else 0
-    d.res_stride, d.Hr, d.Wr = res_stride, 0, 0
-    d.x_ld, d.y_ld = x_ld, y_ld
-    if residual is not None:
-        if residual.shape[0] != n or residual.shape[3] != cout:
-            raise ValueError(f"residual shape {tuple(residual.shape)} does not match N={n}, Cout={cout}")
-        d.Hr, d.Wr = residual.shape[1], residual.shape[2]
-    for t, nme, length in ((in_scale, "in_scale", cin), (in_shift, "in_shift", cin), (bias, "bias", cout),
-                           (alpha, "alpha", cout)):
-        if t is not None and t.numel() != length:
-            raise ValueError(f"{nme} has {t.numel()} elements, expected {length}")
+    if out_n16 is not None and (out_split or next_affine is not None):
+        raise ValueError("out_n16 excludes the split outputs")
+    d = _conv_desc(n, h, w, cin, cout, kh, kw, stride=stride, dil=dil, pad=pad, out_hw=out_hw, res_stride=res_stride,
+                   act1=act1, act2=act2, slope=slope, split_k=split_k, tile=tile, x_nchw=x_nchw, x_ld=x_ld, y_ld=y_ld,
+                   storage=STORE_NONE if out_n16 is None else storage_of(out_n16), kpad=w_packed.shape[1])
+    shape = (n, d.Ho, d.Wo, cout)
+    for t, nme in ((in_scale, "in_scale"), (in_shift, "in_shift")):
+        if t is not None and t.numel() != cin:
+            raise ValueError(f"{nme} has {t.numel()} elements, expected {cin}")
     for t, nme in ((mask, "mask"), (aux, "aux")):
-        if t is not None and t.numel() != n * ho * wo * cout:
+        if t is not None and t.numel() != n * d.Ho * d.Wo * cout:
             raise ValueError(f"{nme} must have the output's shape")
-    d.act1, d.act2, d.slope, d.split_k, d.tile = act1, act2, slope, split_k, tile
     if out is None and want_f32:
         if y_ld:
             raise ValueError("y_ld needs an explicit out buffer")
-        out = _empty((n, ho, wo, cout), x)
+        out = _empty(shape, x)
     elif out is not None:
         _dev_f32(out, "out", contiguous=(y_ld == 0))
-    ws_bytes = lib.cer_conv2d_workspace_bytes(ctypes.byref(d))
-    ws = _empty((ws_bytes // 4,), x) if ws_bytes else None
-    stats = _empty((lib.cer_conv2d_stats_tiles(ctypes.byref(d), 0), 2, cout), x) if want_stats else None
-    if out_n16 is not None:  # fp32 kernel, narrow (single bf16 / half plane) output: the Cin = 3 stem of the narrow encoder
-        if out_split or next_affine is not None:
-            raise ValueError("out_n16 excludes the split outputs")
-        io = ConvIO()
-        io.x, io.w = x.data_ptr(), w_packed.data_ptr()
-        for name, t in (("in_scale", in_scale), ("in_shift", in_shift), ("bias", bias), ("alpha", alpha),
-                        ("residual", residual), ("mask", mask), ("y", out), ("aux", aux), ("stats", stats)):
-            if t is not None:
-                setattr(io, name, t.data_ptr())
-        d.storage = storage_of(out_n16)
-        res = {"y": out, "stats": stats, "n16": torch.empty((n, ho, wo, cout), device=x.device, dtype=out_n16)}
-        io.y_hi = res["n16"].data_ptr()
-        check(lib.cer_conv2d_run(ctypes.byref(d), ctypes.byref(io), ptr(ws), ws_bytes, current_stream()), "cer_conv2d_run")
-        return res
-    if not (out_split or next_affine is not None):
-        check(lib.cer_conv2d_fwd(ctypes.byref(d), ptr(x), ptr(w_packed), ptr(in_scale), ptr(in_shift), ptr(bias),
-                                 ptr(alpha), ptr(residual), ptr(mask), ptr(out), ptr(aux), ptr(stats), ptr(ws), ws_bytes,
-                                 current_stream()), "cer_conv2d_fwd")
-        return (out, stats) if want_stats else out
-    # fp32 kernel with split (bf16 hi/lo) outputs: feeds the bf16x3 layers (e.g. the Cin = 3 stem)
     io = ConvIO()
     io.x, io.w = x.data_ptr(), w_packed.data_ptr()
-    for name, t in (("in_scale", in_scale), ("in_shift", in_shift), ("bias", bias), ("alpha", alpha),
-                    ("residual", residual), ("mask", mask), ("y", out), ("aux", aux), ("stats", stats)):
+    for name, t in (("in_scale", in_scale), ("in_shift", in_shift), ("mask", mask), ("y", out), ("aux", aux)):
         if t is not None:
             setattr(io, name, t.data_ptr())
-    res = {"y": out, "stats": stats}
+    _conv_epilogue(d, io, bias, alpha, None, residual)
+    res = {"y": out, "stats": None}
+    if out_n16 is not None:
+        res["n16"] = torch.empty(shape, device=x.device, dtype=out_n16)
+        io.y_hi = res["n16"].data_ptr()
     if out_split:
-        res["split"] = Split.empty((n, ho, wo, cout), x.device)
+        res["split"] = Split.empty(shape, x.device)
         io.y_hi, io.y_lo = res["split"].hi.data_ptr(), res["split"].lo.data_ptr()
     if next_affine is not None:
-        s2, t2 = next_affine
-        res["next"] = Split.empty((n, ho, wo, cout), x.device)
-        io.s2, io.t2 = s2.data_ptr(), t2.data_ptr()
-        io.y2_hi, io.y2_lo = res["next"].hi.data_ptr(), res["next"].lo.data_ptr()
-    check(lib.cer_conv2d_run(ctypes.byref(d), ctypes.byref(io), ptr(ws), ws_bytes, current_stream()), "cer_conv2d_run")
-    return res
+        _next_affine_out(io, res, next_affine, shape, x.device)
+    res["stats"] = _conv_run(d, io, 0, x.device, want_stats=want_stats)  # no trace: the fp32 convs stay out of CONV_TRACE
+    if len(res) > 2:
+        return res
+    return (out, res["stats"]) if want_stats else out
 
 
 class Split:
@@ -205,11 +276,6 @@ def _dev_bf16(t, name):
         raise ValueError(f"{name}: expected a contiguous bfloat16 GPU tensor")
 
 
-# bench.py sets this to a list to time every bf16x3 conv launch with HIP events on the launch stream:
-# (kernel variant id, algorithmic FLOPs, start event, end event, algorithmic bytes)
-CONV_TRACE = None
-
-
 def conv2d_b3(x, w, kh, kw, *, stride=1, dil=(1, 1), pad=(0, 0), out_hw=None, bias=None, alpha=None, residual=None,
               res_stride=1, act1=ACT_NONE, act2=ACT_NONE, slope=LEAKY_SLOPE, split_k=1, tile=0, out_f32=False,
               out_split=True, next_affine=None, want_stats=False, bias9=None, x_s2d=False, y_s2d=False):
@@ -219,50 +285,14 @@ def conv2d_b3(x, w, kh, kw, *, stride=1, dil=(1, 1), pad=(0, 0), out_hw=None, bi
     ``y_s2d``: the Split output is stored space-to-depth, [N, Ho/2, Wo/2, 4*Cout] (``space_to_depth`` is the torch
     statement of the layout); ``x_s2d``: x is such a tensor (of the [N, 2*x.shape[1], 2*x.shape[2], x.shape[3]/4] input of
     this 3x3 / stride 2 / pad 1 conv) and w went through ``pack_s2d_weight``."""
-    lib = _lib.load()
     for t, n in ((x.hi, "x.hi"), (x.lo, "x.lo"), (w.hi, "w.hi"), (w.lo, "w.lo")):
         _dev_bf16(t, n)
-    _dev_f32(bias, "bias")
-    _dev_f32(alpha, "alpha")
-    n, h, wd, cin = x.shape
-    if x_s2d:
-        if cin % 4:
-            raise ValueError("a space-to-depth input has 4 * Cin channels")
-        h, wd, cin = 2 * h, 2 * wd, cin // 4
-    cout = w.shape[0]
-    if w.shape[1] != conv_kpad(kh, kw, cin):
-        raise ValueError(f"packed weight has K={w.shape[1]}, expected {conv_kpad(kh, kw, cin)}")
-    if out_hw is None:
-        ho = (h + 2 * pad[0] - dil[0] * (kh - 1) - 1) // stride + 1
-        wo = (wd + 2 * pad[1] - dil[1] * (kw - 1) - 1) // stride + 1
-    else:
-        ho, wo = out_hw
-    d = ConvDesc()
-    d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = n, h, wd, cin, ho, wo, cout
-    d.KH, d.KW, d.stride, d.dil_h, d.dil_w, d.pad_t, d.pad_l = kh, kw, stride, dil[0], dil[1], pad[0], pad[1]
-    d.res_stride, d.Hr, d.Wr = res_stride, 0, 0
-    d.act1, d.act2, d.slope, d.split_k, d.tile = act1, act2, slope, split_k, tile
-    d.x_s2d, d.y_s2d = int(x_s2d), int(y_s2d)
+    d = _conv_desc(*x.shape, w.shape[0], kh, kw, stride=stride, dil=dil, pad=pad, out_hw=out_hw, res_stride=res_stride, act1=act1,
+                   act2=act2, slope=slope, split_k=split_k, tile=tile, x_s2d=x_s2d, y_s2d=y_s2d, kpad=w.shape[1])
+    n, ho, wo, cout = d.N, d.Ho, d.Wo, d.Cout
     io = ConvIO()
     io.x_hi, io.x_lo, io.w_hi, io.w_lo = x.hi.data_ptr(), x.lo.data_ptr(), w.hi.data_ptr(), w.lo.data_ptr()
-    io.bias = bias.data_ptr() if bias is not None else None
-    io.alpha = alpha.data_ptr() if alpha is not None else None
-    if bias9 is not None:
-        _dev_f32(bias9, "bias9")
-        if tuple(bias9.shape) != (9, cout):
-            raise ValueError("bias9 must be [9, Cout]")
-        io.bias9 = bias9.data_ptr()
-    if residual is not None:
-        rshape = residual.shape
-        if rshape[0] != n or rshape[3] != cout:
-            raise ValueError("residual shape does not match the output")
-        d.Hr, d.Wr = rshape[1], rshape[2]
-        if isinstance(residual, Split):
-            _dev_bf16(residual.hi, "residual.hi")
-            io.res_hi, io.res_lo = residual.hi.data_ptr(), residual.lo.data_ptr()
-        else:
-            _dev_f32(residual, "residual")
-            io.residual = residual.data_ptr()
+    _conv_epilogue(d, io, bias, alpha, bias9, residual, split=True)
     res = {}
     dev = x.hi.device
     if out_f32:
@@ -272,29 +302,17 @@ def conv2d_b3(x, w, kh, kw, *, stride=1, dil=(1, 1), pad=(0, 0), out_hw=None, bi
         res["split"] = Split.empty((n, ho // 2, wo // 2, 4 * cout) if y_s2d else (n, ho, wo, cout), dev)
         io.y_hi, io.y_lo = res["split"].hi.data_ptr(), res["split"].lo.data_ptr()
     if next_affine is not None:
-        s2, t2 = next_affine
-        _dev_f32(s2, "s2")
-        _dev_f32(t2, "t2")
-        res["next"] = Split.empty((n, ho, wo, cout), dev)
-        io.s2, io.t2 = s2.data_ptr(), t2.data_ptr()
-        io.y2_hi, io.y2_lo = res["next"].hi.data_ptr(), res["next"].lo.data_ptr()
-    if want_stats:
-        res["stats"] = torch.empty((lib.cer_conv2d_stats_tiles(ctypes.byref(d), 1), 2, cout), device=dev,
-                                   dtype=torch.float32)
-        io.stats = res["stats"].data_ptr()
-    ws_bytes = lib.cer_conv2d_workspace_bytes(ctypes.byref(d))
-    ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.float32) if ws_bytes else None
+        _next_affine_out(io, res, next_affine, (n, ho, wo, cout), dev)
+    trace = None
     if CONV_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.cer_conv2d_run(ctypes.byref(d), ctypes.byref(io), ptr(ws), ws_bytes, current_stream()), "cer_conv2d_run")
-    if CONV_TRACE is not None:
-        e1.record()
         # algorithmic bytes: split input (4 B/elt) + every output tensor written + split weights + residual read
         nout = n * ho * wo * cout
-        nbytes = 4.0 * n * h * wd * cin + 4.0 * nout * (int(out_f32) + int(out_split) + int(next_affine is not None)) + \
-            4.0 * cout * cin * kh * kw + (4.0 * nout if residual is not None else 0.0)
-        CONV_TRACE.append((lib.cer_conv2d_b3_tile(ctypes.byref(d)), 2.0 * n * ho * wo * cout * cin * kh * kw, e0, e1, nbytes))
+        nbytes = 4.0 * n * d.H * d.W * d.Cin + 4.0 * nout * (int(out_f32) + int(out_split) + int(next_affine is not None)) + \
+            4.0 * cout * d.Cin * kh * kw + (4.0 * nout if residual is not None else 0.0)
+        trace = ("cer_conv2d_b3_tile", nbytes)
+    stats = _conv_run(d, io, 1, dev, trace, want_stats)
+    if want_stats:
+        res["stats"] = stats
     return res
 
 
@@ -330,23 +348,20 @@ def stem_conv(x, w, scale=None, shift=None, alpha=None, out=None, want_stats=Fal
     return res
 
 
-def _tile_desc(n, h, w, cin, cout, kh, kw, stride, pad, x_s2d):
-    d = ConvDesc()
-    d.N, d.H, d.W, d.Cin, d.Cout = n, h, w, cin, cout
-    d.Ho, d.Wo = (h + 2 * pad[0] - kh) // stride + 1, (w + 2 * pad[1] - kw) // stride + 1
-    d.KH, d.KW, d.stride, d.dil_h, d.dil_w, d.pad_t, d.pad_l = kh, kw, stride, 1, 1, pad[0], pad[1]
-    d.split_k, d.x_s2d = 1, int(x_s2d)
-    return d
+def _tile_query(query, n, h, w, cin, cout, kh, kw, stride, pad, x_s2d):
+    d = _conv_desc(n, h, w, cin, cout, kh, kw, stride=stride, pad=pad)
+    d.x_s2d = int(x_s2d)  # (n, h, w, cin) is the conv's own input here, not the space-to-depth tensor
+    return getattr(_lib.load(), query)(ctypes.byref(d))
 
 
 def conv2d_b3_tile(n, h, w, cin, cout, kh, kw, stride, pad, x_s2d=False):
     """The bf16x3 kernel variant ``conv2d_b3`` would launch for this conv (cer_conv2d_b3_tile)."""
-    return _lib.load().cer_conv2d_b3_tile(ctypes.byref(_tile_desc(n, h, w, cin, cout, kh, kw, stride, pad, x_s2d)))
+    return _tile_query("cer_conv2d_b3_tile", n, h, w, cin, cout, kh, kw, stride, pad, x_s2d)
 
 
 def conv2d_n16_tile(n, h, w, cin, cout, kh, kw, stride, pad, x_s2d=False):
     """The narrow kernel variant ``conv2d_n16`` would launch for this conv (cer_conv2d_n16_tile)."""
-    return _lib.load().cer_conv2d_n16_tile(ctypes.byref(_tile_desc(n, h, w, cin, cout, kh, kw, stride, pad, x_s2d)))
+    return _tile_query("cer_conv2d_n16_tile", n, h, w, cin, cout, kh, kw, stride, pad, x_s2d)
 
 
 # the window / patch kernels: their epilogues can store space-to-depth
@@ -421,51 +436,15 @@ def conv2d_n16(x, w, kh, kw, *, stride=1, dil=(1, 1), pad=(0, 0), out_hw=None, b
     """Narrow convolution: x [N,H,W,Cin] and w [Cout,Kpad] are bf16 / float16 tensors of the same dtype (one MFMA per
     product, fp32 accumulate); residual: narrow or fp32.  Returns a dict with 'n16' (narrow output), 'y' (fp32), 'stats'.
     ``x_s2d`` / ``y_s2d``: space-to-depth input / narrow output, as in ``conv2d_b3`` (weights: ``pack_s2d_weight(w, cin, 64)``)."""
-    lib = _lib.load()
     _dev_n16(x, "x")
     _dev_n16(w, "w", x.dtype)
-    _dev_f32(bias, "bias")
-    _dev_f32(alpha, "alpha")
-    n, h, wd, cin = x.shape
-    if x_s2d:
-        if cin % 4:
-            raise ValueError("a space-to-depth input has 4 * Cin channels")
-        h, wd, cin = 2 * h, 2 * wd, cin // 4
-    cout = w.shape[0]
-    if w.shape[1] != conv_kpad(kh, kw, cin):
-        raise ValueError(f"packed weight has K={w.shape[1]}, expected {conv_kpad(kh, kw, cin)}")
-    if out_hw is None:
-        ho = (h + 2 * pad[0] - dil[0] * (kh - 1) - 1) // stride + 1
-        wo = (wd + 2 * pad[1] - dil[1] * (kw - 1) - 1) // stride + 1
-    else:
-        ho, wo = out_hw
-    d = ConvDesc()
-    d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout = n, h, wd, cin, ho, wo, cout
-    d.KH, d.KW, d.stride, d.dil_h, d.dil_w, d.pad_t, d.pad_l = kh, kw, stride, dil[0], dil[1], pad[0], pad[1]
-    d.res_stride, d.Hr, d.Wr = res_stride, 0, 0
-    d.act1, d.act2, d.slope, d.split_k, d.tile = act1, act2, slope, split_k, tile
-    d.storage = storage_of(x.dtype)
-    d.x_s2d, d.y_s2d = int(x_s2d), int(y_s2d)
+    d = _conv_desc(*x.shape, w.shape[0], kh, kw, stride=stride, dil=dil, pad=pad, out_hw=out_hw, res_stride=res_stride, act1=act1,
+                   act2=act2, slope=slope, split_k=split_k, tile=tile, storage=storage_of(x.dtype), x_s2d=x_s2d, y_s2d=y_s2d,
+                   kpad=w.shape[1])
+    n, ho, wo, cout = d.N, d.Ho, d.Wo, d.Cout
     io = ConvIO()
     io.x_hi, io.w_hi = x.data_ptr(), w.data_ptr()
-    io.bias = bias.data_ptr() if bias is not None else None
-    io.alpha = alpha.data_ptr() if alpha is not None else None
-    if bias9 is not None:
-        _dev_f32(bias9, "bias9")
-        if tuple(bias9.shape) != (9, cout):
-            raise ValueError("bias9 must be [9, Cout]")
-        io.bias9 = bias9.data_ptr()
-    if residual is not None:
-        rshape = residual.shape
-        if rshape[0] != n or rshape[3] != cout:
-            raise ValueError("residual shape does not match the output")
-        d.Hr, d.Wr = rshape[1], rshape[2]
-        if residual.dtype == torch.float32:
-            _dev_f32(residual, "residual")
-            io.residual = residual.data_ptr()
-        else:
-            _dev_n16(residual, "residual", x.dtype)
-            io.res_hi = residual.data_ptr()
+    _conv_epilogue(d, io, bias, alpha, bias9, residual, n16=x.dtype)
     res = {}
     dev = x.device
     if out_f32:
@@ -474,23 +453,26 @@ def conv2d_n16(x, w, kh, kw, *, stride=1, dil=(1, 1), pad=(0, 0), out_hw=None, b
     if out_n16:
         res["n16"] = torch.empty((n, ho // 2, wo // 2, 4 * cout) if y_s2d else (n, ho, wo, cout), device=dev, dtype=x.dtype)
         io.y_hi = res["n16"].data_ptr()
-    if want_stats:
-        res["stats"] = torch.empty((lib.cer_conv2d_stats_tiles(ctypes.byref(d), 2), 2, cout), device=dev, dtype=torch.float32)
-        io.stats = res["stats"].data_ptr()
-    ws_bytes = lib.cer_conv2d_workspace_bytes(ctypes.byref(d))
-    ws = torch.empty((ws_bytes // 4,), device=dev, dtype=torch.float32) if ws_bytes else None
+    trace = None
     if CONV_TRACE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib.cer_conv2d_run(ctypes.byref(d), ctypes.byref(io), ptr(ws), ws_bytes, current_stream()), "cer_conv2d_run")
-    if CONV_TRACE is not None:
-        e1.record()
         # algorithmic bytes: narrow input + every output tensor written + narrow weights + residual read
         nout = n * ho * wo * cout
-        nbytes = 2.0 * n * h * wd * cin + nout * (4.0 * int(out_f32) + 2.0 * int(out_n16)) + 2.0 * cout * cin * kh * kw + \
+        nbytes = 2.0 * n * d.H * d.W * d.Cin + nout * (4.0 * int(out_f32) + 2.0 * int(out_n16)) + 2.0 * cout * d.Cin * kh * kw + \
             (0.0 if residual is None else (4.0 if residual.dtype == torch.float32 else 2.0) * nout)
-        CONV_TRACE.append((lib.cer_conv2d_n16_tile(ctypes.byref(d)), 2.0 * n * ho * wo * cout * cin * kh * kw, e0, e1, nbytes))
+        trace = ("cer_conv2d_n16_tile", nbytes)
+    stats = _conv_run(d, io, 2, dev, trace, want_stats)
+    if want_stats:
+        res["stats"] = stats
     return res
+
+
+def _bn_apply_args(y, scale, shift, alpha, res, res_scale, res_shift, mask, split=False, n16=None):
+    """What the three ``bn_apply`` wrappers check alike: the (C,) vectors and the mask; returns ``_res_kind(res)``."""
+    c = y.shape[3]
+    for t, nme in ((scale, "scale"), (shift, "shift"), (alpha, "alpha"), (res_scale, "res_scale"), (res_shift, "res_shift")):
+        _dev_f32(t, nme, shape=(c,))
+    _dev_mask(mask, y)
+    return _res_kind(res, "res", split, n16)
 
 
 def bn_apply_nhwc_n16(y, scale, shift, dtype=None, alpha=None, res=None, res_stride=1, res_scale=None, res_shift=None, mask=None,
@@ -498,30 +480,19 @@ def bn_apply_nhwc_n16(y, scale, shift, dtype=None, alpha=None, res=None, res_str
     """``bn_apply_nhwc`` for the narrow encoder: ``y`` (the conv result) and ``res`` are fp32 or narrow tensors; the result
     comes back narrow ('n16', what the next conv reads) and/or fp32 ('y'); 'stats' as requested."""
     n, ho, wo, c = y.shape
-    for t, nme in ((scale, "scale"), (shift, "shift"), (alpha, "alpha"), (res_scale, "res_scale"), (res_shift, "res_shift")):
-        _dev_f32(t, nme, shape=(c,))
-    _dev_mask(mask, y)
     lib = _lib.load()
     if dtype is None:
         dtype = y.dtype if y.dtype != torch.float32 else (res.dtype if res is not None else None)
     if dtype is None or dtype == torch.float32:
         raise ValueError("bn_apply_nhwc_n16: pass dtype= when neither y nor res is a narrow tensor")
-    y32 = y16 = r32 = r16 = None
+    r32, r16, _, hr, wr = _bn_apply_args(y, scale, shift, alpha, res, res_scale, res_shift, mask, n16=dtype)
+    y32 = y16 = None
     if y.dtype == torch.float32:
         _dev_f32(y, "y")
         y32 = y
     else:
         _dev_n16(y, "y", dtype)
         y16 = y
-    hr = wr = 0
-    if res is not None:
-        hr, wr = res.shape[1], res.shape[2]
-        if res.dtype == torch.float32:
-            _dev_f32(res, "res")
-            r32 = res
-        else:
-            _dev_n16(res, "res", dtype)
-            r16 = res
     out = {}
     if out_f32:
         out["y"] = torch.empty(tuple(y.shape), device=y.device, dtype=torch.float32)
@@ -752,16 +723,12 @@ def bn_apply_nhwc(y, scale, shift, alpha=None, res=None, res_stride=1, res_scale
                   want_stats=False):
     """out = mask*prelu(y*scale+shift) + (res*res_scale+res_shift) on NHWC; optionally the partial
     statistics of ``out`` for the next BatchNorm."""
-    for t, nme in ((y, "y"), (res, "res")):
-        _dev_f32(t, nme)
+    _dev_f32(y, "y")
     n, ho, wo, c = y.shape
-    for t, nme in ((scale, "scale"), (shift, "shift"), (alpha, "alpha"), (res_scale, "res_scale"), (res_shift, "res_shift")):
-        _dev_f32(t, nme, shape=(c,))
-    _dev_mask(mask, y)
+    _, _, _, hr, wr = _bn_apply_args(y, scale, shift, alpha, res, res_scale, res_shift, mask)
     lib = _lib.load()
     out = torch.empty_like(y)
     stats = _empty((lib.cer_bn_apply_stats_tiles(n * ho * wo), 2, c), y) if want_stats else None
-    hr, wr = (res.shape[1], res.shape[2]) if res is not None else (0, 0)
     check(lib.cer_bn_apply_nhwc(ptr(y), ptr(scale), ptr(shift), ptr(alpha), ptr(res), ptr(res_scale), ptr(res_shift),
                                 ptr(mask), ptr(out), ptr(stats), n, ho, wo, c, res_stride, hr, wr, current_stream()),
           "cer_bn_apply_nhwc")
@@ -774,20 +741,8 @@ def bn_apply_nhwc_b3(y, scale, shift, alpha=None, res=None, res_stride=1, res_sc
     (what the next conv reads) and/or fp32.  Returns a dict with 'split', 'y', 'stats' as requested."""
     _dev_f32(y, "y")
     n, ho, wo, c = y.shape
-    for t, nme in ((scale, "scale"), (shift, "shift"), (alpha, "alpha"), (res_scale, "res_scale"), (res_shift, "res_shift")):
-        _dev_f32(t, nme, shape=(c,))
-    _dev_mask(mask, y)
+    r_f32, r_hi, r_lo, hr, wr = _bn_apply_args(y, scale, shift, alpha, res, res_scale, res_shift, mask, split=True)
     lib = _lib.load()
-    r_f32 = r_hi = r_lo = None
-    hr = wr = 0
-    if res is not None:
-        hr, wr = res.shape[1], res.shape[2]
-        if isinstance(res, Split):
-            _dev_bf16(res.hi, "res.hi")
-            r_hi, r_lo = res.hi, res.lo
-        else:
-            _dev_f32(res, "res")
-            r_f32 = res
     out = {}
     if out_f32:
         out["y"] = torch.empty_like(y)

@@ -405,28 +405,17 @@ class IR50(nn.Module):
                                           nn.Linear(embedding_dim * head_hw * head_hw, embedding_dim),
                                           nn.BatchNorm1d(embedding_dim))
         self.body = nn.Sequential(*[_Unit(*u) for u in ir50_units()])
-        self._packed = None
-        self._packed_key = None
-        self._packed_train = None
-        self._packed_train_key = None
+        self._packs = {}  # (kind, train) -> (state key, packed dict): see _cached
         self.bn_mode = "reference"  # or "frozen": encoder BatchNorm/Dropout stay in eval behaviour under train()
         # "bf16x3": split hi/lo bf16 operands, 3 bf16 MFMAs per product (<= 2^-15 relative per product, logit error
         # ~1e-6, 2-2.5x faster than fp32); "fp32": the exact-fp32 MFMA kernels
         self.precision = "bf16x3"
-        self._packed_b3 = None
-        self._packed_b3_key = None
-        self._packed_train_b3 = None
-        self._packed_train_b3_key = None
         # "bf16" / "fp16": narrow storage -- ONE 16-bit plane per tensor, one MFMA per product, fp32 accumulate and fp32
         # epilogue arithmetic (csrc/conv_n16.hip): what the reference's --amp recipe computes (fp16 autocast,
         # trainer.py:341,367) and BASELINE cfg5's "bf16 storage / fp32 accumulate"
         # the reference trains under torch.cuda.amp.autocast when --amp is set (trainer.py:341,367): inside an autocast region
         # the encoder follows it onto the narrow kernels of the autocast dtype (float16 -> "fp16", bfloat16 -> "bf16")
         self.follow_autocast = True
-        self._packed_n16 = None
-        self._packed_n16_key = None
-        self._packed_train_n16 = None
-        self._packed_train_n16_key = None
         self.dropout_seed = 0
         self._dropout_calls = 0
         # released units (_ReleasedUnit): "raw" keeps the raw conv results for the backward, "recompute" only the unit inputs
@@ -437,17 +426,13 @@ class IR50(nn.Module):
 
     def __deepcopy__(self, memo):
         """trainer.py:656,705 deep-copies the model: copy parameters/buffers, not the packed caches."""
-        names = ("_packed", "_packed_train", "_packed_b3", "_packed_train_b3", "_packed_n16", "_packed_train_n16")
-        caches = [getattr(self, n) for n in names]
-        for n in names:
-            setattr(self, n, None)
+        packs, self._packs = self._packs, {}
         try:
             new = self.__class__.__new__(self.__class__)
             memo[id(self)] = new
             new.__dict__ = copy.deepcopy(self.__dict__, memo)
         finally:
-            for n, c in zip(names, caches):
-                setattr(self, n, c)
+            self._packs = packs
         return new
 
     # ------------------------------------------------------------------ packing
@@ -459,19 +444,44 @@ class IR50(nn.Module):
     def _state_key(self):
         return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
 
+    def _param_key(self):
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+
+    def _cached(self, kind, train, key, build):
+        """The pack of ``kind`` ("fp32", "b3", "n16") for the eval (``train`` False) or the batch-statistics path: the cached
+        one while ``key`` is unchanged, else ``build()``'s."""
+        hit = self._packs.get((kind, train))
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        if self.input_layer[0].weight.device.type != "cuda":
+            raise RuntimeError("IR50 runs on the HIP kernels only: move the module to a GPU (no CPU fallback)")
+        packed = build()
+        self._packs[(kind, train)] = (key, packed)
+        return packed
+
+    def _invalidate_eval_packs(self):
+        """The folded eval weights go stale when a batch-statistics forward moves the running statistics."""
+        for k in [k for k in self._packs if not k[1]]:
+            del self._packs[k]
+
+    def _pack_stem(self):
+        """Input layer with its eval-mode BatchNorm folded: packed weight (output scale folded in), bias, PReLU slopes."""
+        s, b = self._bn_affine(self.input_layer[1])
+        return {"stem_w": ops.pack_conv_weight(self.input_layer[0].weight.detach().contiguous(), s), "stem_b": b,
+                "stem_a": self.input_layer[2].weight.detach().contiguous()}
+
+    def _head_w_hwc(self):
+        """The FC weight with its K order (c,h,w) permuted to the kernels' (h,w,c): [512, hw*hw*c]."""
+        fc, hw = self.output_layer[3], self.head_hw
+        return fc.weight.detach().view(fc.out_features, -1, hw * hw).permute(0, 2, 1).contiguous().view(fc.out_features, -1)
+
     def pack(self):
         """Fold eval-mode BatchNorms and lay weights out for the kernels (cached until a
         parameter or buffer changes)."""
-        key = self._state_key()
-        if self._packed is not None and key == self._packed_key:
-            return self._packed
-        dev = self.input_layer[0].weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("IR50 runs on the HIP kernels only: move the module to a GPU (no CPU fallback)")
-        P = {}
-        s, b = self._bn_affine(self.input_layer[1])
-        P["stem_w"] = ops.pack_conv_weight(self.input_layer[0].weight.detach().contiguous(), s)
-        P["stem_b"], P["stem_a"] = b, self.input_layer[2].weight.detach().contiguous()
+        return self._cached("fp32", False, self._state_key(), self._pack_fp32)
+
+    def _pack_fp32(self):
+        P = self._pack_stem()
         units = []
         for u in self.body:
             d = {"stride": u.stride, "proj": u.cin != u.depth}
@@ -497,18 +507,14 @@ class IR50(nn.Module):
         w = (w * s0.view(1, -1, 1)).permute(0, 2, 1).contiguous().view(fc.out_features, -1)  # [512, (hw, c)]
         P["head_w"] = (w * s4.view(-1, 1)).contiguous()
         P["head_b"] = (bias * s4 + t4).contiguous()
-        self._packed, self._packed_key = P, key
         return P
 
     def pack_train(self):
         """Raw (un-folded) kernel layouts for the batch-statistics path; weights are frozen, so this
         is cached on the parameter versions only."""
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._packed_train is not None and key == self._packed_train_key:
-            return self._packed_train
-        dev = self.input_layer[0].weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("IR50 runs on the HIP kernels only: move the module to a GPU (no CPU fallback)")
+        return self._cached("fp32", True, self._param_key(), self._pack_train_fp32)
+
+    def _pack_train_fp32(self):
         P = {"stem_w": ops.pack_conv_weight(self.input_layer[0].weight.detach().contiguous()), "units": []}
         for u in self.body:
             d = {"w1": ops.pack_conv_weight(u.res_layer[1].weight.detach().contiguous()),
@@ -516,42 +522,35 @@ class IR50(nn.Module):
             if u.cin != u.depth:
                 d["ws"] = ops.pack_conv_weight(u.shortcut_layer[0].weight.detach().contiguous())
             P["units"].append(d)
-        fc, hw = self.output_layer[3], self.head_hw
-        P["head_w"] = fc.weight.detach().view(fc.out_features, -1, hw * hw).permute(0, 2, 1).contiguous().view(
-            fc.out_features, -1)  # K order (c,h,w) -> (h,w,c)
-        self._packed_train, self._packed_train_key = P, key
+        P["head_w"] = self._head_w_hwc()
         return P
 
-    # ------------------------------------------------------------------ bf16x3 packing
-    def pack_b3(self):
-        """Eval-mode layouts for the bf16x3 kernels: weights as split (hi/lo bf16) planes with EVERY BatchNorm folded in:
-        post-conv BatchNorms as output scale + bias, pre-conv BatchNorms through ``ops.fold_input_bn_3x3`` (input scale
-        into the weights, input shift into the border-dependent ``bias9``), the head's BatchNorm2d/BatchNorm1d into the FC.
-        Each unit then writes ONE split tensor (its raw output, which is both the next conv's input and the shortcut)."""
-        key = self._state_key()
-        if self._packed_b3 is not None and key == self._packed_b3_key:
-            return self._packed_b3
-        if self.input_layer[0].weight.device.type != "cuda":
-            raise RuntimeError("IR50 runs on the HIP kernels only: move the module to a GPU (no CPU fallback)")
-        P = {}
-        s, b = self._bn_affine(self.input_layer[1])
-        P["stem_w"] = ops.pack_conv_weight(self.input_layer[0].weight.detach().contiguous(), s)
-        P["stem_b"], P["stem_a"] = b, self.input_layer[2].weight.detach().contiguous()
+    # ------------------------------------------------------------------ bf16x3 and narrow (bf16 / fp16 storage) packing
+    NARROW = {"bf16": torch.bfloat16, "fp16": torch.float16}
+
+    def _pack_folded(self, convert, s2d_mod):
+        """Eval-mode layouts of the bf16x3 / narrow kernels with EVERY BatchNorm folded in, computed in fp32 and put through
+        ``convert`` (``ops.split_bf16`` / ``ops.to_n16``) once: post-conv BatchNorms as output scale + bias, pre-conv
+        BatchNorms through ``ops.fold_input_bn_3x3`` (input scale into the weights, input shift into the border-dependent
+        ``bias9``), the head's BatchNorm2d/BatchNorm1d into the FC.  Each unit then writes ONE tensor (its raw output, which
+        is both the next conv's input and the shortcut).  ``s2d_mod``: the stride-2 units whose depth is a multiple of it
+        also get ``w2_s2d``."""
+        P = self._pack_stem()
         units = []
         for u in self.body:
             d = {"stride": u.stride, "proj": u.cin != u.depth}
             in_s, in_b = self._bn_affine(u.res_layer[0])
             w1, d["b9"] = ops.fold_input_bn_3x3(u.res_layer[1].weight.detach(), in_s, in_b)
-            d["w1"] = ops.split_bf16(w1)
+            d["w1"] = convert(w1)
             d["a1"] = u.res_layer[2].weight.detach().contiguous()
             s2, b2 = self._bn_affine(u.res_layer[4])
-            d["w2"] = ops.split_bf16(ops.pack_conv_weight(u.res_layer[3].weight.detach().contiguous(), s2))
-            if u.stride == 2 and u.depth % 64 == 0:   # the same columns in the space-to-depth kernel's step order
+            d["w2"] = convert(ops.pack_conv_weight(u.res_layer[3].weight.detach().contiguous(), s2))
+            if u.stride == 2 and u.depth % s2d_mod == 0:   # the same columns in the space-to-depth kernel's step order
                 d["w2_s2d"] = ops.pack_s2d_weight(d["w2"], u.depth)
             d["b2"] = b2
             if d["proj"]:
                 ss, sb = self._bn_affine(u.shortcut_layer[1])
-                d["ws"] = ops.split_bf16(ops.pack_conv_weight(u.shortcut_layer[0].weight.detach().contiguous(), ss))
+                d["ws"] = convert(ops.pack_conv_weight(u.shortcut_layer[0].weight.detach().contiguous(), ss))
                 d["bs"] = sb
             units.append(d)
         P["units"] = units
@@ -562,98 +561,39 @@ class IR50(nn.Module):
         w = fc.weight.detach().view(fc.out_features, -1, hw * hw).permute(0, 2, 1)  # [o][(h,w)][c]: K order (c,h,w) -> (h,w,c)
         bias = fc.bias.detach() + (w * t0.view(1, 1, -1)).sum((1, 2))                 # W . t0
         w = (w * s0.view(1, 1, -1)).contiguous().view(fc.out_features, -1)            # W . diag(s0)
-        P["head_w"] = ops.split_bf16((w * s4.view(-1, 1)).contiguous())
+        P["head_w"] = convert((w * s4.view(-1, 1)).contiguous())
         P["head_b"] = (bias * s4 + t4).contiguous()
-        self._packed_b3, self._packed_b3_key = P, key
         return P
 
-    def pack_train_b3(self):
-        key = tuple((p.data_ptr(), p._version) for p in self.parameters())
-        if self._packed_train_b3 is not None and key == self._packed_train_b3_key:
-            return self._packed_train_b3
-        if self.input_layer[0].weight.device.type != "cuda":
-            raise RuntimeError("IR50 runs on the HIP kernels only: move the module to a GPU (no CPU fallback)")
-        P = {"stem_w": ops.pack_conv_weight(self.input_layer[0].weight.detach().contiguous()), "units": []}
-        for u in self.body:
-            d = {"w1_f32": ops.pack_conv_weight(u.res_layer[1].weight.detach().contiguous()),  # folded per step (batch statistics)
-                 "w2": ops.split_bf16(ops.pack_conv_weight(u.res_layer[3].weight.detach().contiguous()))}
-            if u.stride == 2 and u.depth % 64 == 0:
-                d["w2_s2d"] = ops.pack_s2d_weight(d["w2"], u.depth)
-            if u.cin != u.depth:
-                d["ws"] = ops.split_bf16(ops.pack_conv_weight(u.shortcut_layer[0].weight.detach().contiguous()))
-            P["units"].append(d)
-        fc, hw = self.output_layer[3], self.head_hw
-        P["head_w"] = ops.split_bf16(fc.weight.detach().view(fc.out_features, -1, hw * hw).permute(0, 2, 1).contiguous().view(
-            fc.out_features, -1))
-        self._packed_train_b3, self._packed_train_b3_key = P, key
-        return P
-
-    # ------------------------------------------------------------------ narrow (bf16 / fp16 storage) packing and forward
-    NARROW = {"bf16": torch.bfloat16, "fp16": torch.float16}
-
-    def pack_n16(self, dtype):
-        """Eval-mode layouts for the narrow kernels: the same folds as ``pack_b3`` (post-conv BatchNorms as output scale +
-        bias, pre-conv BatchNorms through ``fold_input_bn_3x3``, the head's two BatchNorms into the FC), computed in fp32
-        and rounded ONCE to the storage type."""
-        key = (dtype, self._state_key())
-        if self._packed_n16 is not None and key == self._packed_n16_key:
-            return self._packed_n16
-        if self.input_layer[0].weight.device.type != "cuda":
-            raise RuntimeError("IR50 runs on the HIP kernels only: move the module to a GPU (no CPU fallback)")
-        P = {}
-        s, b = self._bn_affine(self.input_layer[1])
-        P["stem_w"] = ops.pack_conv_weight(self.input_layer[0].weight.detach().contiguous(), s)
-        P["stem_b"], P["stem_a"] = b, self.input_layer[2].weight.detach().contiguous()
-        units = []
-        for u in self.body:
-            d = {"stride": u.stride, "proj": u.cin != u.depth}
-            in_s, in_b = self._bn_affine(u.res_layer[0])
-            w1, d["b9"] = ops.fold_input_bn_3x3(u.res_layer[1].weight.detach(), in_s, in_b)
-            d["w1"] = ops.to_n16(w1, dtype)
-            d["a1"] = u.res_layer[2].weight.detach().contiguous()
-            s2, b2 = self._bn_affine(u.res_layer[4])
-            d["w2"] = ops.to_n16(ops.pack_conv_weight(u.res_layer[3].weight.detach().contiguous(), s2), dtype)
-            if u.stride == 2 and u.depth % 128 == 0:   # the same columns in the space-to-depth kernel's step order
-                d["w2_s2d"] = ops.pack_s2d_weight(d["w2"], u.depth)
-            d["b2"] = b2
-            if d["proj"]:
-                ss, sb = self._bn_affine(u.shortcut_layer[1])
-                d["ws"] = ops.to_n16(ops.pack_conv_weight(u.shortcut_layer[0].weight.detach().contiguous(), ss), dtype)
-                d["bs"] = sb
-            units.append(d)
-        P["units"] = units
-        hw = self.head_hw
-        s0, t0 = self._bn_affine(self.output_layer[0])
-        s4, t4 = self._bn_affine(self.output_layer[4])
-        fc = self.output_layer[3]
-        w = fc.weight.detach().view(fc.out_features, -1, hw * hw).permute(0, 2, 1)  # K order (c,h,w) -> (h,w,c)
-        bias = fc.bias.detach() + (w * t0.view(1, 1, -1)).sum((1, 2))
-        w = (w * s0.view(1, 1, -1)).contiguous().view(fc.out_features, -1)
-        P["head_w"] = ops.to_n16((w * s4.view(-1, 1)).contiguous(), dtype)
-        P["head_b"] = (bias * s4 + t4).contiguous()
-        self._packed_n16, self._packed_n16_key = P, key
-        return P
-
-    def pack_train_n16(self, dtype):
-        key = (dtype, tuple((p.data_ptr(), p._version) for p in self.parameters()))
-        if self._packed_train_n16 is not None and key == self._packed_train_n16_key:
-            return self._packed_train_n16
-        if self.input_layer[0].weight.device.type != "cuda":
-            raise RuntimeError("IR50 runs on the HIP kernels only: move the module to a GPU (no CPU fallback)")
+    def _pack_raw(self, convert, s2d_mod):
+        """Un-folded layouts of the bf16x3 / narrow batch-statistics path (``w1_f32`` stays fp32: folded per step)."""
         P = {"stem_w": ops.pack_conv_weight(self.input_layer[0].weight.detach().contiguous()), "units": []}
         for u in self.body:
             d = {"w1_f32": ops.pack_conv_weight(u.res_layer[1].weight.detach().contiguous()),
-                 "w2": ops.to_n16(ops.pack_conv_weight(u.res_layer[3].weight.detach().contiguous()), dtype)}
-            if u.stride == 2 and u.depth % 128 == 0:
+                 "w2": convert(ops.pack_conv_weight(u.res_layer[3].weight.detach().contiguous()))}
+            if u.stride == 2 and u.depth % s2d_mod == 0:
                 d["w2_s2d"] = ops.pack_s2d_weight(d["w2"], u.depth)
             if u.cin != u.depth:
-                d["ws"] = ops.to_n16(ops.pack_conv_weight(u.shortcut_layer[0].weight.detach().contiguous()), dtype)
+                d["ws"] = convert(ops.pack_conv_weight(u.shortcut_layer[0].weight.detach().contiguous()))
             P["units"].append(d)
-        fc, hw = self.output_layer[3], self.head_hw
-        P["head_w"] = ops.to_n16(fc.weight.detach().view(fc.out_features, -1, hw * hw).permute(0, 2, 1).contiguous().view(
-            fc.out_features, -1), dtype)
-        self._packed_train_n16, self._packed_train_n16_key = P, key
+        P["head_w"] = convert(self._head_w_hwc())
         return P
+
+    def pack_b3(self):
+        """``_pack_folded`` as split (hi/lo bf16) planes, cached like ``pack``."""
+        return self._cached("b3", False, self._state_key(), lambda: self._pack_folded(ops.split_bf16, 64))
+
+    def pack_train_b3(self):
+        return self._cached("b3", True, self._param_key(), lambda: self._pack_raw(ops.split_bf16, 64))
+
+    def pack_n16(self, dtype):
+        """``_pack_folded`` rounded ONCE to the narrow storage type ``dtype`` (one cached pack: the last dtype asked for)."""
+        return self._cached("n16", False, (dtype, self._state_key()), lambda: self._pack_folded(lambda w: ops.to_n16(w, dtype), 128))
+
+    def pack_train_n16(self, dtype):
+        return self._cached("n16", True, (dtype, self._param_key()), lambda: self._pack_raw(lambda w: ops.to_n16(w, dtype), 128))
+
+    # ------------------------------------------------------------------ narrow and bf16x3 forwards
 
     def _forward_n16(self, x, dtype):
         """Eval / frozen forward on the narrow kernels (Cin = 3 stem on the fp32 small-Cin kernel, narrow output)."""
@@ -686,7 +626,7 @@ class IR50(nn.Module):
         ONE bandwidth-bound ``bn_apply`` pass per unit (6 bytes per element instead of 12), the next unit's pre-conv
         BatchNorm folded into its 3x3 conv."""
         P = self.pack_train_n16(dtype)
-        self._packed = self._packed_b3 = self._packed_n16 = None  # running statistics are about to change
+        self._invalidate_eval_packs()  # running statistics are about to change
         n = x.shape[0]
         plan = self._release_plan()
         first_released = len(P["units"]) if plan is None else plan
@@ -804,7 +744,7 @@ class IR50(nn.Module):
         the whole batch -- is folded into its 3x3 conv (input scale into the weights, input shift into a
         border-dependent bias, ``ops.fold_input_bn_3x3``), so no re-split pass over the activations is needed."""
         P = self.pack_train_b3()
-        self._packed = self._packed_b3 = self._packed_n16 = None  # running statistics are about to change
+        self._invalidate_eval_packs()  # running statistics are about to change
         n = x.shape[0]
         plan = self._release_plan()
         first_released = len(P["units"]) if plan is None else plan
@@ -969,7 +909,7 @@ class IR50(nn.Module):
         updates its running buffers; Dropout(0.4) before the head FC.  ``head_mask`` ([N,h,w,512],
         pre-scaled) overrides the generated dropout mask (parity tests)."""
         P = self.pack_train()
-        self._packed = self._packed_b3 = self._packed_n16 = None  # running statistics are about to change: folded eval weights go stale
+        self._invalidate_eval_packs()  # running statistics are about to change
         n = x.shape[0]
         plan = self._release_plan()
         first_released = len(P["units"]) if plan is None else plan
