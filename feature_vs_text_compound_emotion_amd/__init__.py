@@ -5,3 +5,11 @@ libcer_hip.so -- hand-written HIP kernels for gfx950 behind the C-ABI declared
 in ``include/cer_hip.h``.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # the streaming interface, imported on first use (it pulls in torch and the whole host package)
+    if name in ("TCNStream", "LFANStream", "stream_forward"):
+        from . import streaming
+        return getattr(streaming, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

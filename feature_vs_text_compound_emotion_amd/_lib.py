@@ -35,6 +35,12 @@ class ConvIO(Structure):
         "res_hi", "res_lo", "y", "aux", "stats", "y_hi", "y_lo", "s2", "t2", "y2_hi", "y2_lo", "bias9")]
 
 
+class TcnStreamDesc(Structure):
+    """cer_tcn_stream_desc (see include/cer_hip.h)."""
+    _fields_ = [(n, c_int32) for n in ("S", "c", "Cin", "Cout", "k", "dil", "R", "head", "res_C", "res_R", "res_head",
+                                       "out_R", "out_head")] + [("slope", c_float)]
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "cer_last_error": (c_char_p, []),
@@ -122,6 +128,8 @@ _SIGNATURES = {
     "cer_tanh_bwd": (c_int, [_P, _P, _P, c_size_t, _P]),
     "cer_ccc_loss": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "cer_regression_moments": (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
+    "cer_tcn_stream_conv": (c_int, [POINTER(TcnStreamDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cer_tcn_stream_append": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "cer_add_inplace": (c_int, [_P, _P, c_size_t, _P]),
     "cer_l2norm_rows": (c_int, [_P, _P, c_int, c_int, _P]),
     "cer_l2norm_rows_bwd": (c_int, [_P, _P, _P, c_int, c_int, _P]),

@@ -1607,3 +1607,86 @@ def add_inplace(y, x):
     _dev_f32(x, "x")
     check(_lib.load().cer_add_inplace(ptr(y), ptr(x), y.numel(), current_stream()), "cer_add_inplace")
     return y
+
+
+# ------------------------------------------------------------------ streaming TCN (csrc/tcn_stream.hip)
+STREAM_TRACE = None   # a list collects (entry point, weight bytes read) per launch
+
+
+def _ring(t, name, channels=None):
+    """A ring [S, R, C]: contiguous float32 on the GPU.  Returns (S, R, C)."""
+    _dev_f32(t, name)
+    if t.dim() != 3 or (channels is not None and t.shape[2] != channels):
+        raise ValueError(f"{name}: expected a ring [S, R, {channels if channels is not None else 'C'}], got {tuple(t.shape)}")
+    return tuple(t.shape)
+
+
+def pack_tcn_stream_weight(w_oik):
+    """Conv1d filter [Cout, Cin, k] -> the streaming kernel's [Cout4, k, Cin4] (channel counts rounded up to a multiple of 4,
+    zero padding).  A layout change only; done once per weight."""
+    _dev_f32(w_oik, "w", contiguous=False)
+    if w_oik.dim() != 3:
+        raise ValueError(f"w: expected [Cout, Cin, k], got {tuple(w_oik.shape)}")
+    cout, cin, k = w_oik.shape
+    out = torch.zeros((-(-cout // 4) * 4, k, -(-cin // 4) * 4), device=w_oik.device, dtype=torch.float32)
+    out[:cout, :, :cin] = w_oik.detach().permute(0, 2, 1)
+    return out
+
+
+def tcn_stream_append(rows, ring, head):
+    """ring[s, (head + i) % R, :] = rows[s, i, :]: ``rows`` [S, c, C] dense, ``ring`` [S, R, C]."""
+    s, r, ch = _ring(ring, "ring")
+    _dev_f32(rows, "rows")
+    if rows.dim() != 3 or rows.shape[0] != s or rows.shape[2] != ch or rows.shape[1] < 1:
+        raise ValueError(f"rows: expected [{s}, c, {ch}], got {tuple(rows.shape)}")
+    check(_lib.load().cer_tcn_stream_append(ptr(rows), ptr(ring), s, rows.shape[1], ch, r, int(head), current_stream()),
+          "cer_tcn_stream_append")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("append", 0))
+
+
+def tcn_stream_conv(ring, head, c, w_packed, bias, k, dil, *, res_ring=None, res_head=0, res_w=None, res_bias=None,
+                    out_ring=None, out_head=0, out_dense=None, slope=LEAKY_SLOPE):
+    """One conv of a streamed TemporalBlock over the ``c`` newest frames of ``ring`` [S, R, Cin] (written at ``head``):
+
+      v = leaky(conv_k,dil(ring) + bias)                     without ``res_ring``
+      v = leaky(leaky(conv_k,dil(ring) + bias) + res)        with it: res = the c newest frames of ``res_ring`` (at ``res_head``),
+                                                             or their 1x1 projection ``res_w`` (packed) + ``res_bias``
+
+    written to the c slots of ``out_ring`` [S, R', Cout] at ``out_head`` and / or to ``out_dense`` [S * c, Cout].
+    ``w_packed``: ``pack_tcn_stream_weight`` of the [Cout, Cin, k] filter."""
+    s, r, cin = _ring(ring, "ring")
+    _dev_f32(bias, "bias")
+    cout = bias.shape[0]
+    c4 = lambda n: -(-n // 4) * 4   # noqa: E731
+    _dev_f32(w_packed, "w_packed", shape=(c4(cout), k, c4(cin)))
+    d = _lib.TcnStreamDesc(S=s, c=int(c), Cin=cin, Cout=cout, k=int(k), dil=int(dil), R=r, head=int(head), slope=float(slope))
+    wbytes = w_packed.numel() * 4
+    if res_ring is not None:
+        rs, d.res_R, d.res_C = _ring(res_ring, "res_ring")
+        d.res_head = int(res_head)
+        if rs != s:
+            raise ValueError(f"res_ring: expected {s} streams, got {rs}")
+        if res_w is not None:
+            _dev_f32(res_w, "res_w", shape=(c4(cout), 1, c4(d.res_C)))
+            _dev_f32(res_bias, "res_bias", shape=(cout,))
+            if res_bias is None:
+                raise ValueError("res_bias: the projection needs its bias")
+            wbytes += res_w.numel() * 4
+        elif d.res_C != cout:
+            raise ValueError(f"res_ring: {d.res_C} channels for Cout = {cout} and no projection")
+    elif res_w is not None or res_bias is not None:
+        raise ValueError("res_w / res_bias without res_ring")
+    if out_ring is None and out_dense is None:
+        raise ValueError("tcn_stream_conv: no output")
+    if out_ring is not None:
+        os_, d.out_R, _ = _ring(out_ring, "out_ring", cout)
+        d.out_head = int(out_head)
+        if os_ != s:
+            raise ValueError(f"out_ring: expected {s} streams, got {os_}")
+    _dev_f32(out_dense, "out_dense", shape=(s * int(c), cout))
+    check(_lib.load().cer_tcn_stream_conv(ctypes.byref(d), ptr(ring), ptr(w_packed), ptr(bias), ptr(res_ring), ptr(res_w),
+                                          ptr(res_bias), ptr(out_ring), ptr(out_dense), current_stream()),
+          "cer_tcn_stream_conv")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("conv", wbytes))

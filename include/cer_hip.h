@@ -617,6 +617,48 @@ int cer_fc_bwd_elem(const float *da, int da_ld, const void *a, const uint16_t *a
 /* y[r, 0:C] (pitch y_ld) = x[r, 0:C] (pitch x_ld). */
 int cer_copy_cols(const float *x, int x_ld, float *y, int y_ld, int R, int C, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Streaming TCN: a TemporalBlock (reference models/temporal_convolutional_model.py:21-56) run on c new frames of S streams,
+ * its causal taps read from rings of past frames.
+ *
+ * A ring is [S][R][C] fp32, channels-last, R a power of two.  All streams advance together: the host keeps the write
+ * position `head` in [0, R) and passes it in; the device keeps no counters.  Row (s, i), i < c, is the frame at slot
+ * (head + i) & (R - 1).  An all-zero ring is a stream with no past: exactly the reference's left zero padding.
+ *
+ * cer_tcn_stream_conv, for every row (s, i) and output channel o:
+ *     z   = bias[o] + sum_{j < k, ci < Cin} w[o][j][ci] * ring[s][(head + i - (k - 1 - j) * dil) & (R - 1)][ci]
+ *     v   = leaky(z)                                         res_ring == NULL  (a block's first conv)
+ *     v   = leaky(leaky(z) + res)                            res_ring != NULL  (its second conv)
+ *     res = res_ring[s][(res_head + i) & (res_R - 1)][o]                                   res_w == NULL, res_C == Cout
+ *         = res_bias[o] + sum_ci res_w[o][ci] * res_ring[s][(res_head + i) & (res_R - 1)][ci]      the 1x1 downsample
+ *   v goes to out_ring[s][(out_head + i) & (out_R - 1)][o] and / or out_dense[s * c + i][o] (either may be NULL, not both).
+ *   leaky(t) = t >= 0 ? t : slope * t.  out_ring and out_dense must not overlap any ring the launch reads.
+ *   w is packed [Cout4][k][Cin4] with Cout4 / Cin4 the channel counts rounded up to a multiple of 4 and the padding zero;
+ *   res_w likewise [Cout4][res_C4].  Packed weights are 16-byte aligned; rings may sit at any float address.
+ *   Any Cin, Cout, k, dil >= 1; 1 <= c <= R - (k - 1) * dil.
+ *
+ * Each output is a fixed-order fp32 sum: it depends on its stream's own history only, never on S, c, head, the number
+ * of wraps or the other rows of the launch (no split over workgroups along K, no atomics, no path picked by row count).
+ *
+ * cer_tcn_stream_append: ring[s][(head + i) & (R - 1)][:] = rows[s * c + i][:] -- the first block's input.
+ *
+ * Invalid descriptors (null pointers, R not a power of two, head outside [0, R), c too large for R) return
+ * CER_ERR_INVALID_ARG before any launch.
+ * ---------------------------------------------------------------------- */
+typedef struct cer_tcn_stream_desc {
+    int32_t S, c;              /* streams, new frames per stream */
+    int32_t Cin, Cout, k, dil; /* the conv */
+    int32_t R, head;           /* the ring the taps read */
+    int32_t res_C, res_R, res_head; /* the residual ring (read when res_ring != NULL) */
+    int32_t out_R, out_head;   /* the ring written (when out_ring != NULL) */
+    float slope;
+} cer_tcn_stream_desc;
+
+int cer_tcn_stream_conv(const cer_tcn_stream_desc *d, const float *ring, const float *w, const float *bias,
+                        const float *res_ring, const float *res_w, const float *res_bias, float *out_ring, float *out_dense,
+                        void *stream);
+int cer_tcn_stream_append(const float *rows, float *ring, int S, int c, int C, int R, int head, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

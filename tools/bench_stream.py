@@ -1,0 +1,142 @@
+"""Per-push latency of streaming LFAN inference (``LFANStream.push_features``, tri-modal) against the only alternative the
+offline model offers for a live stream: ``LFAN.forward`` over the last 121 frames (the TCN's receptive field, k = 5, dilations
+1, 2, 4, 8) on a model built with ``example_length = 121``, once per new frame.
+
+    python tools/bench_stream.py [--reps 200] [--rounds 5] [--out profiles/stream_latency.json]
+
+Both run the same weights on pre-computed embeddings (the video modality enters as its 512-d embedding under the reference's
+``cnn_res50`` key, same TCN as ``video``), so neither side runs an encoder.  Settings: S in {1, 32} streams, c in {1, 32} new
+frames per push.  Each figure is the median over ``rounds * reps`` calls of the time between two HIP events around ONE call,
+after warm-up, the two methods alternating round by round in the same process; the host-clock median (call + synchronise) is
+kept next to it.  Before timing, the streamed logits of the window's last frame are compared with the offline forward's.
+Launches are counted as C-ABI calls of one push / one forward (each is one kernel launch); weight bytes from the shapes.
+Prints one JSON line and writes it to ``--out``.  Needs the GPU.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.modules.setdefault("triton", None)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+MODS = ["cnn_res50", "vggish", "bert"]
+FIELD = 121
+
+
+def build_model(example_length):
+    from feature_vs_text_compound_emotion_amd import synth
+    from feature_vs_text_compound_emotion_amd.lfan import LFAN
+    channels = dict(synth.TCN_CHANNELS, cnn_res50=synth.TCN_CHANNELS["video"])
+    torch.manual_seed(0)
+    m = LFAN(backbone_settings={}, output_dim=7, task="CLASSIFICATION", modality=MODS, example_length=example_length,
+             kernel_size=5, tcn_channel=channels, modal_dim=32, num_heads=2, root_dir="", device="cuda")
+    m.init(load_backbone=False)
+    return m.cuda().eval()
+
+
+def timed(fn, reps):
+    """Per-call (HIP-event ms, host ms incl. synchronise) lists."""
+    ev, host = [], []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        host.append((time.perf_counter() - t) * 1e3)
+        ev.append(e0.elapsed_time(e1))
+    return ev, host
+
+
+def count_calls(fn):
+    """C-ABI calls (one kernel launch each) and streamed-TCN weight bytes of one call of ``fn``."""
+    from feature_vs_text_compound_emotion_amd import ops
+    calls, real = [], ops.check
+
+    def counting(rc, what):
+        calls.append(what)
+        return real(rc, what)
+    ops.check, ops.STREAM_TRACE = counting, []
+    try:
+        fn()
+        torch.cuda.synchronize()
+        return len(calls), sum(b for _, b in ops.STREAM_TRACE)
+    finally:
+        ops.check, ops.STREAM_TRACE = real, None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_latency.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_stream.py measures on the GPU; none is visible")
+    from feature_vs_text_compound_emotion_amd.streaming import LFANStream
+    model = build_model(FIELD)
+    dims = {m: model.embedding_dim[m] for m in MODS}
+    g = torch.Generator(device="cuda").manual_seed(1)
+    result = {"modalities": MODS, "receptive_field": FIELD, "reps": a.reps, "rounds": a.rounds, "stream": {}, "offline": {}}
+
+    with torch.no_grad():
+        # the two methods agree on the newest frame of a 121-frame window
+        x = {m: torch.randn(2, FIELD, d, device="cuda", generator=g) for m, d in dims.items()}
+        want = model({m: v.unsqueeze(1) for m, v in x.items()})[:, -1]
+        got = LFANStream(model, 2).push_features(x)[:, -1]
+        result["newest_frame_max_abs_diff"] = (got - want).abs().max().item()
+
+        cases = {}
+        for s in (1, 32):
+            window = {m: torch.randn(s, 1, FIELD, d, device="cuda", generator=g) for m, d in dims.items()}
+            cases[f"offline_S{s}"] = (lambda window=window: model(dict(window)))
+            for c in (1, 32):
+                stream = LFANStream(model, s, max_new=32)
+                feats = {m: torch.randn(s, c, d, device="cuda", generator=g) for m, d in dims.items()}
+                cases[f"stream_S{s}_c{c}"] = (lambda stream=stream, feats=feats: stream.push_features(feats))
+        samples = {name: ([], []) for name in cases}
+        for fn in cases.values():
+            for _ in range(a.warmup):
+                fn()
+        for _ in range(a.rounds):       # alternate the methods: a drift of the machine hits all of them alike
+            for name, fn in cases.items():
+                ev, host = timed(fn, a.reps)
+                samples[name][0].extend(ev)
+                samples[name][1].extend(host)
+        for name, fn in cases.items():
+            launches, tcn_bytes = count_calls(fn)
+            ev, host = samples[name]
+            q = statistics.quantiles(ev, n=10)
+            entry = {"event_ms_median": round(statistics.median(ev), 4), "event_ms_p10": round(q[0], 4),
+                     "event_ms_p90": round(q[-1], 4), "host_ms_median": round(statistics.median(host), 4), "launches": launches}
+            if name.startswith("stream"):
+                entry["tcn_weight_bytes_read"] = tcn_bytes
+                result["stream"][name[len("stream_"):]] = entry
+            else:
+                result["offline"][name[len("offline_"):]] = entry
+    tcn_params = sum(p.numel() for p in model.temporal.parameters())
+    head = [model.fusion, model.regressor, model.bn]
+    result["tcn_parameter_bytes"] = 4 * tcn_params
+    result["head_weight_bytes"] = 4 * sum(p.numel() for mod in head for p in mod.parameters())
+    one, off = result["stream"]["S1_c1"], result["offline"]["S1"]
+    result["offline_over_stream_S1_c1"] = round(off["event_ms_median"] / one["event_ms_median"], 2)
+    result["stream_no_slower_than_offline_S1_c1"] = one["event_ms_median"] <= off["event_ms_median"]
+    line = json.dumps(result)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write(json.dumps(result, indent=1) + "\n")
+    if not result["stream_no_slower_than_offline_S1_c1"]:
+        print("DEFECT: streaming at S = 1, c = 1 is slower than re-running the offline forward over 121 frames", file=sys.stderr)
+
+
+if __name__ == "__main__":
+    main()
