@@ -4,7 +4,9 @@
 video), accumulates the frame-level and the three video-level confusion count matrices with ``cer_eval_accumulate`` and
 turns them into the reference's score dictionary (trainer.py:525-605 / metrics.py:148-193: macro / weighted F1 with
 sklearn's "classes present in targets or predictions" convention, accuracy, row-normalised confusion matrix) after ONE
-[4, C, C] device-to-host copy per evaluation and ignore-class setting.
+[4, C, C] device-to-host copy per evaluation and ignore-class setting.  ``DeviceRegressionAccumulator`` does the same for the
+regression task from per-video moment rows.  Both answer to the three calls ``Trainer.inference`` makes:
+``add(values, labels, video_offsets=None, keys=None)``, ``merge_ranks(group=None)`` and ``compute()``.
 """
 import numpy as np
 import torch
@@ -115,31 +117,32 @@ class DeviceEvalAccumulator:
         self.keep = keep_video_predictions
         self.video_predictions = []
 
-    def add(self, logits, labels, video_offsets=None):
-        """logits [R, C] float32 GPU, labels [R] (float or long) GPU; ``video_offsets`` = row offsets [V+1] when several
+    def add(self, values, labels, video_offsets=None, keys=None):
+        """values: logits [R, C] float32 GPU, labels [R] (float or long) GPU; ``video_offsets`` = row offsets [V+1] when several
         videos are concatenated (default: one video): a list, or a tensor read in one copy, that starts at 0, rises strictly
-        and ends at R.  The kernel reads rows ``video_offsets[v]:video_offsets[v+1]`` unchecked, so anything else is refused here."""
-        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.shape[1] == self.c):
+        and ends at R.  The kernel reads rows ``video_offsets[v]:video_offsets[v+1]`` unchecked, so anything else is refused here.
+        ``keys`` (the videos' names, which ``DeviceRegressionAccumulator.add`` keeps) are ignored: counts carry no names."""
+        if not (values.is_cuda and values.dtype == torch.float32 and values.dim() == 2 and values.shape[1] == self.c):
             raise ValueError("logits: expected a [R, n_classes] float32 GPU tensor")
         if not (isinstance(labels, torch.Tensor) and labels.is_cuda):
             raise ValueError("labels: expected a GPU tensor (one label per logits row)")
-        logits = logits.contiguous()
+        values = values.contiguous()
         labels = labels.reshape(-1).float().contiguous()
-        r = logits.shape[0]
+        r = values.shape[0]
         if labels.numel() != r:
             raise ValueError("one label per logits row")
         offsets = [0, r] if video_offsets is None else _offsets("DeviceEvalAccumulator.add: video_offsets", video_offsets, r)
-        off = torch.tensor(offsets, dtype=torch.int32, device=logits.device)
+        off = torch.tensor(offsets, dtype=torch.int32, device=values.device)
         v = off.numel() - 1
         lib = _lib.load()
         for ic, cm in self.cm.items():
-            vp = torch.empty((v, 3), dtype=torch.int32, device=logits.device) if self.keep else None
-            check(lib.cer_eval_accumulate(ptr(logits), ptr(labels), ptr(off), v, r, self.c, -1 if ic is None else int(ic),
+            vp = torch.empty((v, 3), dtype=torch.int32, device=values.device) if self.keep else None
+            check(lib.cer_eval_accumulate(ptr(values), ptr(labels), ptr(off), v, r, self.c, -1 if ic is None else int(ic),
                                           ptr(cm[0]), ptr(cm[1:]), ptr(vp), ptr(self.bad), current_stream()), "cer_eval_accumulate")
             if self.keep:
                 self.video_predictions.append((ic, vp))
 
-    def all_reduce(self, group=None):
+    def merge_ranks(self, group=None):
         """Sum the counts of every rank (sharded evaluation): every ignore-class's [4, C, C] counts and the ``bad`` counter go
         in ONE int64 buffer through ONE ``all_reduce(SUM)``.  Afterwards every rank holds the global counts, so ``compute``
         gives the same scores everywhere -- and raises on every rank if any rank saw a bad label."""
@@ -189,19 +192,19 @@ class DeviceRegressionAccumulator:
         self.device = device
         self.rows, self.keys = [], []        # [V, 8] float64 tensors; one (loader position, trial) per row
 
-    def add(self, outputs, labels, video_offsets=None, keys=None):
-        """outputs [R, 1] or [R] float32 GPU, labels [R] or [R, 1] GPU; ``video_offsets`` as ``DeviceEvalAccumulator.add``
+    def add(self, values, labels, video_offsets=None, keys=None):
+        """values: outputs [R, 1] or [R] float32 GPU, labels [R] or [R, 1] GPU; ``video_offsets`` as ``DeviceEvalAccumulator.add``
         takes them (default: one video).  ``keys``: one ``(loader position, trial)`` per video (default: the running video
         count for both).  Everything is checked here, before the launch: the kernel reads rows unchecked, and a video of fewer
         than two frames has no variance (the reference divides by ``len - 1``)."""
-        if not (isinstance(outputs, torch.Tensor) and outputs.is_cuda and outputs.dtype == torch.float32 and outputs.dim() in (1, 2)):
+        if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float32 and values.dim() in (1, 2)):
             raise ValueError("outputs: expected a [R, 1] or [R] float32 GPU tensor")
-        if outputs.dim() == 2 and outputs.shape[1] != 1:
-            raise ValueError(f"outputs: output_dim = {outputs.shape[1]}, but the regression scores cover ONE output column "
+        if values.dim() == 2 and values.shape[1] != 1:
+            raise ValueError(f"outputs: output_dim = {values.shape[1]}, but the regression scores cover ONE output column "
                              "(the reference scores column 0 only, base/logger.py:105-108)")
         if not (isinstance(labels, torch.Tensor) and labels.is_cuda):
             raise ValueError("labels: expected a GPU tensor (one label per output row)")
-        r = outputs.shape[0]
+        r = values.shape[0]
         if labels.numel() != r:
             raise ValueError("one label per output row")
         offsets = [0, r] if video_offsets is None else _offsets("DeviceRegressionAccumulator.add: video_offsets", video_offsets, r)
@@ -214,7 +217,7 @@ class DeviceRegressionAccumulator:
         if len(keys) != v:
             raise ValueError(f"DeviceRegressionAccumulator.add: {len(keys)} keys for {v} videos")
         from . import ops
-        self.rows.append(ops.regression_moments(outputs.reshape(-1).contiguous(), labels.reshape(-1).float().contiguous(), offsets))
+        self.rows.append(ops.regression_moments(values.reshape(-1).contiguous(), labels.reshape(-1).float().contiguous(), offsets))
         self.keys.extend((int(pos), trial) for pos, trial in keys)
 
     def _host_rows(self):
@@ -223,7 +226,7 @@ class DeviceRegressionAccumulator:
         rows = [r if isinstance(r, torch.Tensor) else torch.as_tensor(r) for r in self.rows]
         return (rows[0] if len(rows) == 1 else torch.cat(rows)).cpu().numpy().reshape(-1, 8)
 
-    def all_gather(self, group=None):
+    def merge_ranks(self, group=None):
         """Sharded evaluation: every rank receives every rank's moment rows with their loader positions; ``compute`` orders
         them by position, so every rank folds the same rows in the same order and reports identical scores."""
         import torch.distributed as dist

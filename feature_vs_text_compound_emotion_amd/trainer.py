@@ -16,6 +16,10 @@ Two ways in:
   section 8 f3): ``class MyTrainer(DeviceEvalMixin, reference_trainer.Trainer)`` keeps the reference's own fit loop, logging
   and checkpoints and replaces its two evaluation methods.
 
+What differs between the classification and the regression task -- criterion, label handling, output check, accumulator,
+per-video entry, scores -- is stated once, in ``_Classification`` / ``_Regression``; the step, the evaluation loop and
+``optimize`` read it from ``_task(...)``.
+
 Logging (dllogger), pickled outputs, PerfTracker reports and best-model files stay with the reference's trainer: they are
 its control plane, not this path.
 """
@@ -75,12 +79,98 @@ def _is_gpu(device):
     return torch.device(device).type == "cuda"
 
 
+def _inputs_and_labels(X, device):
+    """A loader item's tensors on ``device``, the labels (either of the reference's two label keys) taken out."""
+    inputs = {k: v.to(device) for k, v in X.items()}
+    labels = inputs.pop("continuous_label", None)
+    if labels is None:
+        labels = inputs.pop(EXPR, None)
+    return inputs, labels
+
+
+class _Classification:
+    """Class logits [B, L, n_cls] against class indices that arrive as [B, L, 1] floats; scored from confusion counts."""
+    name = CLASSIFICATION
+    criterion = staticmethod(cross_entropy_loss)
+    field, label_dtype = "logits", torch.int64       # a per-video entry: {"labels": int64 [n], "logits": float32 [n, n_cls]}
+
+    def labels(self, labels, batch_size, indices, nframes=None):
+        """The reference's "todo : fix this." label hack, in training (trainer.py:360-363) and in evaluation (:468-472)."""
+        if labels.numel() == batch_size:
+            n = len(indices[0]) if indices is not None else labels.shape[1]
+            return torch.zeros((batch_size, n, 1), dtype=torch.float32, device=labels.device)
+        return labels
+
+    def check(self, outputs, labels, n_cls):
+        bsz, nfms, d = labels.shape
+        assert d == 1, d
+        assert outputs.ndim == 3 and tuple(outputs.shape) == (bsz, nfms, n_cls), tuple(outputs.shape)
+
+    def loss(self, criterion, outputs, labels, n_cls):
+        self.check(outputs, labels, n_cls)
+        rows = labels.shape[0] * labels.shape[1]
+        return criterion(outputs.contiguous().view(rows, -1), labels.contiguous().view(rows).long())   # trainer.py:380-383
+
+    def rows(self, outputs):
+        return outputs.reshape(-1, outputs.shape[-1])
+
+    def accumulator(self, n_cls, ignore_classes, device):
+        from .eval_device import DeviceEvalAccumulator
+        return DeviceEvalAccumulator(n_cls, ignore_classes, device=device)
+
+    def score(self, per_video, ignore_classes):
+        return metrics.compute_perf(per_video, ignore_classes)
+
+    def master(self, perf, ignore_classes):
+        return perf[ignore_classes[0]][metrics.W_F1][metrics.FRAME_LEVEL]["master"]
+
+
+class _Regression:
+    """One output column in [-1, 1] against float labels of the same shape (base/trainer.py:262-313); scored with RMSE /
+    Pearson's r / Lin's CCC per trial and overall (base/logger.py:89-129,274-351) from per-video moments."""
+    name = REGRESSION
+    criterion = staticmethod(ccc_loss)
+    field, label_dtype = "outputs", torch.float32    # a per-video entry: {"labels": float32 [n], "outputs": float32 [n]}
+
+    def labels(self, labels, batch_size, indices, nframes=None):
+        if nframes is not None:                       # evaluation: one whole video per loader item
+            assert tuple(labels.shape) == (1, nframes, 1), tuple(labels.shape)
+        return labels.float()
+
+    def check(self, outputs, labels, n_cls):
+        if outputs.shape[-1] != 1:
+            raise ValueError(f"output_dim = {outputs.shape[-1]}: the regression scores cover ONE output column (the "
+                             "reference scores column 0 only, base/logger.py:105-108)")
+        assert tuple(outputs.shape) == tuple(labels.shape), (tuple(outputs.shape), tuple(labels.shape))
+
+    def loss(self, criterion, outputs, labels, n_cls):
+        assert outputs.ndim == 3 and tuple(outputs.shape) == tuple(labels.shape), (tuple(outputs.shape), tuple(labels.shape))
+        return criterion(labels.float(), outputs)    # base/trainer.py:278: float labels, [B, L, D], gold first
+
+    def rows(self, outputs):
+        return outputs.reshape(-1)
+
+    def accumulator(self, n_cls, ignore_classes, device):
+        from .eval_device import DeviceRegressionAccumulator
+        return DeviceRegressionAccumulator(device=device)
+
+    def score(self, per_video, ignore_classes):
+        return metrics.compute_regression_perf(per_video)
+
+    def master(self, perf, ignore_classes):
+        return perf[metrics.OVERALL][metrics.CCC]    # base/trainer.py:174-176
+
+
+_CLASSIFICATION, _REGRESSION = _Classification(), _Regression()
+
+
 def _task(task):
-    """None -> CLASSIFICATION; otherwise one of the reference's two task names (constants.py:17-20), any letter case."""
-    task = CLASSIFICATION if task is None else str(task).upper()
-    if task not in TASKS:
-        raise ValueError(f"task must be one of {TASKS}, got {task!r}")
-    return task
+    """The description of ``task``: None -> classification; otherwise one of the reference's two task names
+    (constants.py:17-20), any letter case."""
+    name = CLASSIFICATION if task is None else str(task).upper()
+    if name not in TASKS:
+        raise ValueError(f"task must be one of {TASKS}, got {name!r}")
+    return _REGRESSION if name == REGRESSION else _CLASSIFICATION
 
 
 class DeviceEvalMixin:
@@ -133,10 +223,16 @@ class DeviceEvalMixin:
         windows = windowing(np.arange(sizes[0][1]), self._arg("window_length"), self._arg("hop_length"))
         return [[{m: _take(m, t, wd) for m, t in data.items()}, wd] for wd in windows]
 
+    def _windows_per_forward(self, wlen):
+        """How many ``wlen``-frame windows one forward may carry: ``eval_frame_budget`` (default: the training footprint,
+        ``train_batch_size x window_length``) in whole windows, at least one."""
+        budget = self.eval_frame_budget or max(1, int(self._arg("train_batch_size", 1))) * int(self._arg("window_length"))
+        return max(1, budget // max(wlen, 1))
+
     def inference_forward_windows(self, data, aggregate=None):
         """Forward a video longer than the model's window (trainer.py:832-892).  Device path: the windows go through the
         model in groups of at most ``eval_frame_budget`` frames (eval mode: clips are independent), then ONE kernel
-        scatter-adds them in window order and divides by the overlap counts (``eval_device.stitch_windows``).  Host path:
+        scatter-adds them in window order and divides by the overlap counts -- a ``_VideoWindowBatch`` of one video.  Host path:
         the reference's own sequence.  A batch of several videos (bsz > 1; the reference asserts bsz == 1 in ``inference``
         but not here) always takes the host path, whose indexed adds carry the batch dimension."""
         total = _num_frames(*next(iter(data.items())))
@@ -146,19 +242,9 @@ class DeviceEvalMixin:
         aggregate = self._aggregate(aggregate)
         bsz = next(iter(data.values())).shape[0]
         if aggregate == "device" and bsz == 1:
-            from .eval_device import stitch_windows
-            wlen = len(chunks[0][1])
-            budget = self.eval_frame_budget or max(1, int(self._arg("train_batch_size", 1))) * int(self._arg("window_length"))
-            group = max(1, budget // max(wlen, 1))
-            outs = []
-            for g0 in range(0, len(chunks), group):
-                part = chunks[g0:g0 + group]
-                batch = {m: torch.cat([c[m] for c, _ in part], dim=0).contiguous() for m in part[0][0]}
-                out = self.model(batch)                               # [n_windows_in_group, window_length, n_cls]
-                assert out.ndim == 3, out.ndim
-                outs.append(out.float())
-            out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
-            return stitch_windows(out, [int(wd[0]) for _, wd in chunks], total).unsqueeze(0)
+            video = _VideoWindowBatch(self.model, self._windows_per_forward(len(chunks[0][1])))
+            video.add(None, chunks, total)
+            return video.flush()[0].unsqueeze(0)
         results = []
         for chunk, wd in chunks:
             out = self.model({m: t.contiguous() for m, t in chunk.items()})
@@ -188,14 +274,14 @@ class DeviceEvalMixin:
 
     @torch.no_grad()
     def inference(self, dataloader, keep_logits=None, aggregate=None):
-        """Trainer.inference (trainer.py:436-523): returns ``(current_perf, per_video_frame_logits)``.  Device path: each
-        video is folded into device-side confusion counts (``DeviceEvalAccumulator``) and the scores come from one small
-        copy at the end; the per-video ``{labels, logits}`` dictionary the reference returns is filled when
-        ``keep_logits`` (default ``self.eval_keep_logits`` = True, as the reference; False skips the per-video copies).
-        ``eval_video_batch`` / ``eval_shard``: see the class docstring; the returned dictionary has the same keys in the
-        same (loader) order either way."""
-        if _task(self._arg("task")) == REGRESSION:
-            return self._inference_regression(dataloader, keep_logits, aggregate)
+        """Trainer.inference (trainer.py:436-523): returns ``(current_perf, per_video)``.  Device path: each video is folded
+        into the task's device-side accumulator (confusion counts, or one row of moments per video) and the scores come from
+        one small copy at the end; the per-video ``{labels, logits}`` (regression: ``{labels, outputs}``) dictionary the
+        reference returns is filled when ``keep_logits`` (default ``self.eval_keep_logits`` = True, as the reference; False
+        skips the per-video copies).  ``eval_video_batch`` / ``eval_shard``: see the class docstring; the returned dictionary
+        has the same keys in the same (loader) order either way.  Regression scores (base/trainer.py:262-313):
+        ``{trial: {"rmse", "pcc", "ccc"}, ..., "overall": {...}}``."""
+        task = _task(self._arg("task"))
         aggregate = self._aggregate(aggregate)
         keep_logits = self.eval_keep_logits if keep_logits is None else keep_logits
         video_batch = int(self.eval_video_batch or 1)
@@ -203,11 +289,9 @@ class DeviceEvalMixin:
             raise ValueError(f"eval_video_batch must be >= 1, got {self.eval_video_batch!r}")
         self.model.eval()
         rank, world = self._eval_shard_rank_world()
-        entries = []                                      # (loader position, trial, {labels, logits})
-        acc = None
-        if aggregate == "device":
-            from .eval_device import DeviceEvalAccumulator
-            acc = DeviceEvalAccumulator(self.number_classes, self.ignore_classes, device=self.device)
+        acc = task.accumulator(self.number_classes, self.ignore_classes, self.device) if aggregate == "device" else None
+        record = keep_logits or acc is None
+        entries = []                                      # (loader position, trial, {labels, logits / outputs})
         amp = bool(self._arg("amp", False)) and _is_gpu(self.device)
         wlen = int(self._arg("window_length"))
 
@@ -217,34 +301,35 @@ class DeviceEvalMixin:
 
         batched = None
         if acc is not None and video_batch > 1 and self._arg("model_name") == "LFAN":
-            budget = self.eval_frame_budget or max(1, int(self._arg("train_batch_size", 1))) * wlen
-            batched = _VideoWindowBatch(forward, max(1, budget // wlen))
+            batched = _VideoWindowBatch(forward, self._windows_per_forward(wlen))
 
-        def fold(logits, labels, offsets, keys):
-            acc.add(logits, labels, video_offsets=offsets)
-            if keep_logits:
-                lg, lb = logits.cpu().numpy(), labels.long().cpu().numpy()
+        def fold(values, labels, offsets, keys):
+            """Rows of one or several videos (``task.rows``) with one label per row."""
+            if acc is not None:
+                acc.add(values, labels, video_offsets=offsets, keys=keys)
+            if record:
+                v, lb = values.cpu().numpy(), labels.to(task.label_dtype).cpu().numpy()
                 for (pos, trial), a, b in zip(keys, offsets, offsets[1:]):
-                    entries.append((pos, trial, {"labels": lb[a:b], "logits": lg[a:b]}))
+                    entries.append((pos, trial, {"labels": lb[a:b], task.field: v[a:b]}))
+
+        def flush():
+            stitched, offsets, videos = batched.flush()
+            fold(task.rows(stitched), torch.cat([lb for _, lb in videos]), offsets, [key for key, _ in videos])
 
         for pos, (X, trials, lengths, indices) in enumerate(dataloader):
             if pos % world != rank:
                 continue
-            inputs = {k: v.to(self.device) for k, v in X.items()}
-            labels = inputs.pop("continuous_label", None)
-            if labels is None:
-                labels = inputs.pop(EXPR, None)
+            inputs, labels = _inputs_and_labels(X, self.device)
             nframes = 0
             for m, t in inputs.items():
                 assert t.shape[0] == 1, f"{t.shape[0]} | {m}"
                 nframes = _num_frames(m, t)
-            if labels.numel() == self.train_batch_size:     # the reference's "todo : fix this." label hack (:468-472)
-                labels = torch.zeros((self.train_batch_size, len(indices[0]), 1), dtype=torch.float32, device=self.device)
+            labels = task.labels(labels, self.train_batch_size, indices, nframes)
             if batched is not None and nframes >= wlen:
                 assert tuple(labels.shape) == (1, nframes, 1), tuple(labels.shape)
-                batched.add((pos, trials[0]), self.window_input(inputs), labels)
+                batched.add(((pos, trials[0]), labels.reshape(-1)), self.window_input(inputs), nframes)
                 if len(batched) >= video_batch:
-                    fold(*batched.flush())
+                    flush()
                 continue
             with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
                 if nframes > wlen and self._arg("model_name") == "LFAN":
@@ -252,123 +337,29 @@ class DeviceEvalMixin:
                 else:
                     outputs = self.model(inputs)
             outputs = outputs.detach().float()
-            bsz, nfms, d = labels.shape
-            assert d == 1 and tuple(outputs.shape) == (bsz, nfms, self.number_classes), tuple(outputs.shape)
-            if acc is not None:
-                acc.add(outputs.contiguous().view(bsz * nfms, -1), labels.contiguous().view(bsz * nfms))
-            if keep_logits or acc is None:
-                entries.append((pos, trials[0], {"labels": labels.contiguous().view(bsz * nfms).long().cpu().numpy().flatten(),
-                                                 "logits": outputs.contiguous().view(bsz * nfms, -1).cpu().numpy()}))
+            task.check(outputs, labels, self.number_classes)
+            fold(task.rows(outputs), labels.reshape(-1), [0, labels.numel()], [(pos, trials[0])])
         if batched is not None and len(batched):
-            fold(*batched.flush())
+            flush()
         if world > 1:                                   # every rank takes part, with or without videos of its own
             import torch.distributed as dist
             if acc is not None:
-                acc.all_reduce()
-            if keep_logits or acc is None:
+                acc.merge_ranks()
+            if record:
                 parts = [None] * world
                 dist.all_gather_object(parts, entries)
                 entries = [e for part in parts for e in part]
         per_video = {}
         for _, trial, entry in sorted(entries, key=lambda e: e[0]):   # loader order; a repeated trial id: the last one wins
             per_video[trial] = entry
-        if acc is not None:
-            return acc.compute(), per_video
-        return metrics.compute_perf(per_video, self.ignore_classes), per_video
-
-
-    def _inference_regression(self, dataloader, keep_logits=None, aggregate=None):
-        """``inference`` for ``task`` = "REGRESSION" (the reference: base/trainer.py:262-313 with base/logger.py:89-129,274-351).
-        Returns ``(scores, {trial: {"labels", "outputs"}})`` with ``scores = {trial: {"rmse", "pcc", "ccc"}, ..., "overall":
-        {...}}``.  Device path: every video leaves one row of moments on the card and the scores come from one small copy at
-        the end; the per-video arrays are copied only when ``keep_logits``.  Windows, ``eval_video_batch`` and ``eval_shard``
-        work as in the classification path; the stitch kernel averages the overlapping windows' outputs."""
-        aggregate = self._aggregate(aggregate)
-        keep = self.eval_keep_logits if keep_logits is None else keep_logits
-        video_batch = int(self.eval_video_batch or 1)
-        if video_batch < 1:
-            raise ValueError(f"eval_video_batch must be >= 1, got {self.eval_video_batch!r}")
-        self.model.eval()
-        rank, world = self._eval_shard_rank_world()
-        entries = []                                      # (loader position, trial, {labels, outputs})
-        acc = None
-        if aggregate == "device":
-            from .eval_device import DeviceRegressionAccumulator
-            acc = DeviceRegressionAccumulator(device=self.device)
-        amp = bool(self._arg("amp", False)) and _is_gpu(self.device)
-        wlen = int(self._arg("window_length"))
-
-        def forward(batch):
-            with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
-                return self.model(batch)
-
-        batched = None
-        if acc is not None and video_batch > 1 and self._arg("model_name") == "LFAN":
-            budget = self.eval_frame_budget or max(1, int(self._arg("train_batch_size", 1))) * wlen
-            batched = _VideoWindowBatch(forward, max(1, budget // wlen))
-
-        def fold(outputs, labels, offsets, keys):
-            acc.add(outputs, labels, video_offsets=offsets, keys=keys)
-            if keep:
-                og, lb = outputs.reshape(-1).cpu().numpy(), labels.reshape(-1).float().cpu().numpy()
-                for (pos, trial), a, b in zip(keys, offsets, offsets[1:]):
-                    entries.append((pos, trial, {"labels": lb[a:b], "outputs": og[a:b]}))
-
-        for pos, (X, trials, lengths, indices) in enumerate(dataloader):
-            if pos % world != rank:
-                continue
-            inputs = {k: v.to(self.device) for k, v in X.items()}
-            labels = inputs.pop("continuous_label", None)
-            if labels is None:
-                labels = inputs.pop(EXPR, None)
-            nframes = 0
-            for m, t in inputs.items():
-                assert t.shape[0] == 1, f"{t.shape[0]} | {m}"
-                nframes = _num_frames(m, t)
-            assert tuple(labels.shape) == (1, nframes, 1), tuple(labels.shape)
-            labels = labels.float()
-            if batched is not None and nframes >= wlen:
-                batched.add((pos, trials[0]), self.window_input(inputs), labels)
-                if len(batched) >= video_batch:
-                    fold(*batched.flush())
-                continue
-            with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
-                if nframes > wlen and self._arg("model_name") == "LFAN":
-                    outputs = self.inference_forward_windows(inputs, aggregate)
-                else:
-                    outputs = self.model(inputs)
-            outputs = outputs.detach().float()
-            if outputs.shape[-1] != 1:
-                raise ValueError(f"output_dim = {outputs.shape[-1]}: the regression scores cover ONE output column (the "
-                                 "reference scores column 0 only, base/logger.py:105-108)")
-            assert tuple(outputs.shape) == tuple(labels.shape), (tuple(outputs.shape), tuple(labels.shape))
-            if acc is not None:
-                fold(outputs.reshape(-1), labels.reshape(-1), [0, nframes], [(pos, trials[0])])
-            else:
-                entries.append((pos, trials[0], {"labels": labels.reshape(-1).cpu().numpy(),
-                                                 "outputs": outputs.reshape(-1).cpu().numpy()}))
-        if batched is not None and len(batched):
-            fold(*batched.flush())
-        if world > 1:                                   # every rank takes part, with or without videos of its own
-            import torch.distributed as dist
-            if acc is not None:
-                acc.all_gather()
-            if keep or acc is None:
-                parts = [None] * world
-                dist.all_gather_object(parts, entries)
-                entries = [e for part in parts for e in part]
-        per_video = {}
-        for _, trial, entry in sorted(entries, key=lambda e: e[0]):   # loader order; a repeated trial id: the last one wins
-            per_video[trial] = entry
-        if acc is not None:
-            return acc.compute(), per_video
-        return metrics.compute_regression_perf(per_video), per_video
+        return (acc.compute() if acc is not None else task.score(per_video, self.ignore_classes)), per_video
 
 
 class _VideoWindowBatch:
-    """The videos of one ``eval_video_batch`` on the batched LFAN path.  Their windows go through ``forward`` in groups of
-    ``group`` windows as soon as a group is full (a group may span videos; at most one group of inputs is held beyond the
-    current video's windows), only the window outputs are kept, and ``flush`` stitches every video with ONE launch."""
+    """The videos of one ``eval_video_batch`` on the batched LFAN path (or the one video of ``inference_forward_windows``).
+    Their windows go through ``forward`` in groups of ``group`` windows as soon as a group is full (a group may span videos;
+    at most one group of inputs is held beyond the current video's windows), only the window outputs are kept, and ``flush``
+    stitches every video with ONE launch."""
 
     def __init__(self, forward, group):
         self.forward, self.group = forward, group
@@ -377,22 +368,22 @@ class _VideoWindowBatch:
     def _reset(self):
         self.pending, self.outs = [], []             # window inputs not forwarded yet; [g, Lw, C] float32 outputs
         self.starts, self.win_off, self.frame_off = [], [0], [0]
-        self.labels, self.keys = [], []
+        self.videos = []
 
     def __len__(self):
-        return len(self.keys)
+        return len(self.videos)
 
-    def add(self, key, windows, labels):
-        """``windows``: ``window_input``'s [(inputs, frame indices)] of one video; ``labels`` [1, n, 1] on the device."""
+    def add(self, video, windows, nframes):
+        """``windows``: ``window_input``'s [(inputs, frame indices)] of one ``nframes``-frame video; ``video``: whatever the
+        caller wants back from ``flush`` for it."""
         for chunk, wd in windows:
             self.pending.append(chunk)
             self.starts.append(int(wd[0]))
             if len(self.pending) == self.group:
                 self._run()
         self.win_off.append(len(self.starts))
-        self.frame_off.append(self.frame_off[-1] + labels.numel())
-        self.labels.append(labels.reshape(-1))
-        self.keys.append(key)
+        self.frame_off.append(self.frame_off[-1] + nframes)
+        self.videos.append(video)
 
     def _run(self):
         part, self.pending = self.pending, []
@@ -401,13 +392,12 @@ class _VideoWindowBatch:
         self.outs.append(out.detach().float())
 
     def flush(self):
-        """-> (stitched logits [R, C], labels [R], frame offsets [V+1], keys [V]); the batch is empty afterwards."""
+        """-> (stitched outputs [R, C], frame offsets [V+1], the V ``video`` items); the batch is empty afterwards."""
         from .eval_device import stitch_windows_multi
         if self.pending:
             self._run()
         out = self.outs[0] if len(self.outs) == 1 else torch.cat(self.outs, dim=0)
-        logits = stitch_windows_multi(out, self.starts, self.win_off, self.frame_off)
-        res = (logits, torch.cat(self.labels), list(self.frame_off), list(self.keys))
+        res = (stitch_windows_multi(out, self.starts, self.win_off, self.frame_off), list(self.frame_off), list(self.videos))
         self._reset()
         return res
 
@@ -505,13 +495,13 @@ class Trainer(DeviceEvalMixin):
         self.optimizer, self.scheduler = optimizer, None
         self.scaler = None                               # the --amp GradScaler (trainer.py:341), one per train_one_epoch
         self._default_criterion = criterion is None      # then the criterion follows the task: cross entropy / CCC loss
-        self.criterion = criterion if criterion is not None else (ccc_loss if _task(task) == REGRESSION else cross_entropy_loss)
+        self.criterion = criterion if criterion is not None else _task(task).criterion
         self.model_name, self.train_batch_size = model_name, train_batch_size
         self.number_classes = number_classes if number_classes is not None else 7
         self.ddp, self.ignore_classes = data_parallel, tuple(ignore_classes)
         # trainer.py:436-523,832 read the window rule and model name from the argparse namespace
         self.args = SimpleNamespace(window_length=window_length, hop_length=hop_length, model_name=model_name, amp=False,
-                                    task=_task(task))
+                                    task=_task(task).name)
         self.epoch, self.counter, self.seed = 0, 0, 0
         self.dataloaders = None
         self.fit_finished = False
@@ -522,7 +512,7 @@ class Trainer(DeviceEvalMixin):
     # the short form's attribute names stay readable
     window_length = property(lambda self: self.args.window_length)
     hop_length = property(lambda self: self.args.hop_length)
-    task = property(lambda self: _task(self.args.task))
+    task = property(lambda self: _task(self.args.task).name)
 
     # ------------------------------------------------------------------ the calls experiment.py:178-182 makes
     def set_args(self, args):
@@ -536,7 +526,7 @@ class Trainer(DeviceEvalMixin):
         if getattr(args, "model_name", None):
             self.model_name = args.model_name
         if self._default_criterion:
-            self.criterion = ccc_loss if self.task == REGRESSION else cross_entropy_loss
+            self.criterion = _task(args.task).criterion
 
     def post_set_args(self, class_id=None):
         """trainer.py:95-105 loads ``<folds_dir>/split-<fold>/class_id.yaml``; the file belongs to the dataset folds, which
@@ -586,11 +576,7 @@ class Trainer(DeviceEvalMixin):
 
     # ------------------------------------------------------------------ training
     def _split(self, X):
-        inputs = {k: v.to(self.device) for k, v in X.items()}
-        labels = inputs.pop("continuous_label", None)
-        if labels is None:
-            labels = inputs.pop(EXPR, None)
-        return inputs, labels
+        return _inputs_and_labels(X, self.device)
 
     def _train_amp(self):
         """``--amp`` on a GPU: the step runs the forward and the loss under fp16 autocast, as ``inference`` does, with loss
@@ -609,10 +595,9 @@ class Trainer(DeviceEvalMixin):
         """One iteration of trainer.py:345-391.  Returns the (detached) loss tensor.  With ``args.amp`` (GPU): autocast
         forward and loss, then ``scaler.scale(loss).backward()``, the gradient all-reduce, ``scaler.step``, ``scaler.update``
         -- a step with a non-finite gradient is skipped and halves the scale, as the reference's GradScaler does."""
+        task = _task(self.args.task)
         inputs, labels = self._split(X)
-        if self.task != REGRESSION and labels.numel() == self.train_batch_size:  # the reference's "todo : fix this." label hack (:360-363)
-            n = len(indices[0]) if indices is not None else labels.shape[1]
-            labels = torch.zeros((self.train_batch_size, n, 1), dtype=torch.float32, device=self.device)
+        labels = task.labels(labels, self.train_batch_size, indices)
         if self.ddp is not None:
             self.ddp.zero_grad()
         else:
@@ -620,14 +605,7 @@ class Trainer(DeviceEvalMixin):
         amp = self._train_amp()
         with torch.autocast("cuda", dtype=torch.float16) if amp else contextlib.nullcontext():
             outputs = self.model(inputs)
-            if self.task == REGRESSION:                  # base/trainer.py:278: float labels, [B, L, D], gold first
-                assert outputs.ndim == 3 and tuple(outputs.shape) == tuple(labels.shape), (tuple(outputs.shape), tuple(labels.shape))
-                loss = self.criterion(labels.float(), outputs)
-            else:
-                bsz, nfms, d = labels.shape
-                assert d == 1, d
-                assert outputs.ndim == 3 and tuple(outputs.shape) == (bsz, nfms, self.number_classes), tuple(outputs.shape)
-                loss = self.criterion(outputs.contiguous().view(bsz * nfms, -1), labels.contiguous().view(bsz * nfms).long())  # trainer.py:380-383
+            loss = task.loss(self.criterion, outputs, labels, self.number_classes)
         if not amp:
             loss.backward()
             if self.ddp is not None:
@@ -668,9 +646,7 @@ class Trainer(DeviceEvalMixin):
         history = {"valid": [], "loss": []}
 
         def master(perf):
-            if self.task == REGRESSION:
-                return perf[metrics.OVERALL][metrics.CCC]
-            return perf[self.ignore_classes[0]][metrics.W_F1][metrics.FRAME_LEVEL]["master"]
+            return _task(self.args.task).master(perf, self.ignore_classes)
 
         def evaluate(loader, **kwargs):
             if self.eval_shard and self.ddp is not None:   # one set of BatchNorm statistics: every shard scores the same model

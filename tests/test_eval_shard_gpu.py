@@ -1,7 +1,8 @@
 """Sharded evaluation (``DeviceEvalMixin.eval_shard``) with the HIP LFAN: two freshly spawned gloo ranks on the one GPU, each
 handed the full loader.  Rank r evaluates the videos at loader positions p % 2 == r; the device confusion counts are summed
 with one all-reduce, the per-video logits gathered back into loader order -- so both ranks return the single-process
-result.  All scenarios run in one spawn (module fixture); each test checks one of them."""
+result.  The regression task (one tanh output, moment rows gathered instead of counts summed) runs through the same loop.
+All scenarios run in one spawn (module fixture); each test checks one of them."""
 import datetime
 import os
 import socket
@@ -27,31 +28,35 @@ def _free_port():
     return p
 
 
-def _lfan():
+def _lfan(n_cls=7, task="CLASSIFICATION"):
     from feature_vs_text_compound_emotion_amd import synth
     from feature_vs_text_compound_emotion_amd.lfan import LFAN
-    sd = synth.lfan_state_dict(MODS, n_cls=7, seed=9)
-    model = LFAN(backbone_settings={}, output_dim=7, task="CLASSIFICATION", modality=MODS, example_length=WINDOW,
+    sd = synth.lfan_state_dict(MODS, n_cls=n_cls, seed=9)
+    model = LFAN(backbone_settings={}, output_dim=n_cls, task=task, modality=MODS, example_length=WINDOW,
                  kernel_size=5, tcn_channel=synth.TCN_CHANNELS, root_dir="", device="cuda")
     model.init(load_backbone=False)
     model.load_state_dict(sd, strict=True)
     return model.cuda().eval()
 
 
-def _loader(videos, seed=5):
+def _loader(videos, seed=5, regression=False):
+    """``regression``: the same frame counts with labels uniform in (-1, 1) under the regression label key."""
     from feature_vs_text_compound_emotion_amd import synth
     g = torch.Generator().manual_seed(seed)
     out = []
     for v, (n, label) in enumerate(videos):
         X = {m: torch.randn(1, 1, n, synth.EMBEDDING_DIM[m], generator=g) for m in MODS}
-        X["EXPR_continuous_label"] = torch.full((1, n, 1), float(label))
+        if regression:
+            X["continuous_label"] = torch.rand(1, n, 1, generator=g) * 2.0 - 1.0
+        else:
+            X["EXPR_continuous_label"] = torch.full((1, n, 1), float(label))
         out.append((X, [f"clip{v}"], [n], [np.arange(n)]))
     return out
 
 
-def _run(model, loader, shard, video_batch=1, aggregate=None):
+def _run(model, loader, shard, video_batch=1, aggregate=None, task=None):
     from feature_vs_text_compound_emotion_amd.trainer import Trainer
-    tr = Trainer(model, device="cuda", window_length=WINDOW, hop_length=HOP, number_classes=7)
+    tr = Trainer(model, device="cuda", window_length=WINDOW, hop_length=HOP, number_classes=7, task=task)
     tr.eval_shard, tr.eval_video_batch, tr.eval_frame_budget = shard, video_batch, 3 * WINDOW
     try:
         return tr.inference(loader, aggregate=aggregate)
@@ -82,6 +87,15 @@ def _worker(rank, world, port, out):
             "shard_one_batched": _run(model, one, True, video_batch=4),
             "shard_bad": _run(model, bad, True),
         }
+        model = _lfan(n_cls=1, task="REGRESSION")
+        full, one = _loader(VIDEOS, regression=True), _loader(VIDEOS[2:3], regression=True)
+        res.update({
+            "reg_single": _run(model, full, False, task="REGRESSION"),
+            "reg_single_one": _run(model, one, False, task="REGRESSION"),
+            "reg_shard": _run(model, full, True, task="REGRESSION"),
+            "reg_shard_batched": _run(model, full, True, video_batch=4, task="REGRESSION"),
+            "reg_shard_one": _run(model, one, True, task="REGRESSION"),       # rank 1 has no video
+        })
         out[rank] = res
         dist.barrier()
     finally:
@@ -109,15 +123,15 @@ def _same(a, b):
         assert np.array_equal(np.asarray(a), np.asarray(b)), (a, b)
 
 
-def _same_videos(a, b, tol=0.0):
+def _same_videos(a, b, tol=0.0, field="logits"):
     assert list(a) == list(b)
     for k in a:
         assert np.array_equal(a[k]["labels"], b[k]["labels"])
-        assert a[k]["logits"].shape == b[k]["logits"].shape
+        assert a[k][field].shape == b[k][field].shape
         if tol == 0.0:
-            assert np.array_equal(a[k]["logits"], b[k]["logits"]), k
+            assert np.array_equal(a[k][field], b[k][field]), k
         else:
-            assert np.abs(a[k]["logits"] - b[k]["logits"]).max() < tol, k
+            assert np.abs(a[k][field] - b[k][field]).max() < tol, k
 
 
 def _margin(per_video):
@@ -164,3 +178,42 @@ def test_a_bad_label_on_one_rank_raises_on_every_rank(ranks):
     for r in range(WORLD):
         res = ranks[r]["shard_bad"]
         assert isinstance(res, tuple) and res[0] == "AssertionError" and "labels outside" in res[1], (r, res)
+
+
+def _regression_scores_close(a, b, tol):
+    """``tol`` = 0: equal, the (possibly NaN) p-value included."""
+    assert list(a) == list(b)
+    for t in a:
+        if tol == 0.0:
+            assert a[t]["rmse"] == b[t]["rmse"] and a[t]["ccc"] == b[t]["ccc"] and a[t]["pcc"][0] == b[t]["pcc"][0], t
+            assert np.array_equal(a[t]["pcc"][1], b[t]["pcc"][1], equal_nan=True), t
+        else:
+            assert abs(a[t]["rmse"] - b[t]["rmse"]) <= tol and abs(a[t]["ccc"] - b[t]["ccc"]) <= tol, t
+            assert abs(a[t]["pcc"][0] - b[t]["pcc"][0]) <= tol, t
+
+
+def test_sharded_regression_evaluation_equals_the_single_process_run_exactly(ranks):
+    for single, shard in (("reg_single", "reg_shard"), ("reg_single_one", "reg_shard_one")):
+        perf1, pv1 = ranks[0][single]
+        n = len(VIDEOS) if single == "reg_single" else 1
+        assert list(pv1) == [f"clip{v}" for v in range(n)] and list(perf1) == list(pv1) + ["overall"]
+        for r in range(WORLD):
+            perf, pv = ranks[r][shard]
+            _regression_scores_close(perf, perf1, 0.0)
+            _same_videos(pv, pv1, field="outputs")
+            assert all(e["labels"].dtype == np.float32 and e["outputs"].shape == e["labels"].shape for e in pv.values())
+
+
+def test_sharded_batched_regression_evaluation_agrees_with_its_host_mirror_and_the_single_process_run(ranks):
+    """Windows of several videos in shared forwards: the scores must reproduce the numpy mirror on the run's OWN outputs to
+    1e-10, while the outputs themselves (and rmse, 1-Lipschitz in them) may move by the 1e-5 that test_regression_gpu.py
+    grants batched forwards."""
+    from feature_vs_text_compound_emotion_amd import metrics
+    perf1, pv1 = ranks[0]["reg_single"]
+    for r in range(WORLD):
+        perf, pv = ranks[r]["reg_shard_batched"]
+        _regression_scores_close(perf, metrics.compute_regression_perf(pv), 1e-10)
+        _same_videos(pv, pv1, tol=1e-5, field="outputs")
+        assert list(perf) == list(perf1)
+        for t in perf1:
+            assert abs(perf[t]["rmse"] - perf1[t]["rmse"]) <= 1e-5, t

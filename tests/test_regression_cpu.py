@@ -108,7 +108,7 @@ def _worker(rank, world, port, out):
                             timeout=datetime.timedelta(seconds=120))
     try:
         acc = _filled([p for p in range(len(rr.VIDEO_FRAMES)) if p % world == rank])
-        acc.all_gather()
+        acc.merge_ranks()
         out[rank] = acc.compute()
         dist.barrier()
     finally:
