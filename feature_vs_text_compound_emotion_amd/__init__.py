@@ -9,7 +9,7 @@ __version__ = "0.1.0"
 
 def __getattr__(name):
     # the streaming interface, imported on first use (it pulls in torch and the whole host package)
-    if name in ("TCNStream", "LFANStream", "stream_forward"):
+    if name in ("TCNStream", "LFANStream", "CANStream", "stream_forward"):
         from . import streaming
         return getattr(streaming, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

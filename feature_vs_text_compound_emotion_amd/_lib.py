@@ -41,6 +41,12 @@ class TcnStreamDesc(Structure):
                                        "out_R", "out_head")] + [("slope", c_float)]
 
 
+class TcnStreamRowsDesc(Structure):
+    """cer_tcn_stream_rows_desc (see include/cer_hip.h)."""
+    _fields_ = [(n, c_int32) for n in ("S", "M", "max_count", "Cin", "Cout", "k", "dil", "R", "res_C", "res_R",
+                                       "out_R")] + [("slope", c_float)]
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "cer_last_error": (c_char_p, []),
@@ -130,6 +136,8 @@ _SIGNATURES = {
     "cer_regression_moments": (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     "cer_tcn_stream_conv": (c_int, [POINTER(TcnStreamDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cer_tcn_stream_append": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "cer_tcn_stream_conv_rows": (c_int, [POINTER(TcnStreamRowsDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cer_tcn_stream_append_rows": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "cer_add_inplace": (c_int, [_P, _P, c_size_t, _P]),
     "cer_l2norm_rows": (c_int, [_P, _P, c_int, c_int, _P]),
     "cer_l2norm_rows_bwd": (c_int, [_P, _P, _P, c_int, c_int, _P]),

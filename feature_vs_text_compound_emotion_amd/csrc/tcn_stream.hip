@@ -1,9 +1,10 @@
 // tcn_stream.hip -- frame-at-a-time causal TCN: the conv of a TemporalBlock over c new frames of S streams, its taps gathered
 // from a ring of past frames (reference models/temporal_convolutional_model.py:21-56, run incrementally).
 //
-// State of one ring: [S][R][C] fp32, channels-last, R a power of two; the host owns the write position `head` (all streams
-// advance together).  Row (s, i), i < c, is the frame written at slot (head + i) & (R - 1); tap j of a k-tap, dilation-d conv
-// reads slot (head + i - (k - 1 - j) d) & (R - 1).  A reset stream's ring is all zeros, which is the causal left zero-pad.
+// State of one ring: [S][R][C] fp32, channels-last, R a power of two; the host owns the write positions.  In lockstep (all
+// streams advance together) that is one `head`: row (s, i), i < c, is the frame written at slot (head + i) & (R - 1); tap j of
+// a k-tap, dilation-d conv reads slot (head + i - (k - 1 - j) d) & (R - 1).  A reset stream's ring is all zeros, which is the
+// causal left zero-pad.
 //
 // The work is M = S * c rows (1 .. a few hundred) against k * Cin * Cout weights: bound by the weight read.  One block owns
 // CO_T = 4 output channels x ROW_T = 8 rows; its 256 threads split K = k * Cin between them in float4 chunks (thread t takes
@@ -15,6 +16,13 @@
 // an output value is the same bits whatever S, c, head, the wrap count or the neighbouring rows of its block.  There is no
 // split over blocks along K, no atomics and no path picked by the row count.  Rows beyond M are clamped to row M - 1 for the
 // loads (in bounds, never stored).
+//
+// Two ways to find the M rows, one arithmetic.  Lockstep (cer_tcn_stream_conv): M = S * c, row m is frame m % c of stream
+// m / c at position head + m % c.  Row table (cer_tcn_stream_conv_rows): row m is the frame of stream row_stream[m] at
+// position row_pos[m] (unwrapped, modulo 2^30), read from device memory; every ring of a launch masks the same position with
+// its own R - 1, so one table serves all levels of a net and streams advance independently.  The table is data the host
+// code cannot see at launch: the stream index is clamped into [0, S) and every slot is masked, so any content stays inside the
+// rings.  Only ts_rows' filling and the epilogue's addresses differ; ts_dot / ts_fold do not know which way a row was found.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -95,26 +103,50 @@ __device__ __forceinline__ float ts_fold(float (&acc)[TS_CO][TS_ROWS], float *ld
 struct ts_args {
     const float *ring, *w, *bias;          // conv input ring [S][R][Cin], packed filter, bias [Cout]
     const float *res_ring, *res_w, *res_bias;   // phase B: residual ring [S][res_R][res_C]; res_w NULL = identity
-    float *out_ring, *out_dense;           // [S][out_R][Cout] and / or [S * c][Cout]
-    int S, c, Cin, Cout, k, dil, R, head;
-    int res_C, res_R, res_head, out_R, out_head;
+    float *out_ring, *out_dense;           // [S][out_R][Cout] and / or [M][Cout]
+    int M, Cin, Cout, k, dil, R;
+    int res_C, res_R, out_R;
     float slope;
+};
+
+// Where row m sits: its stream and its (unwrapped) position in the tap ring, the residual ring and the written ring.
+struct ts_where {
+    int s, pos, res_pos, out_pos;
+};
+
+// All streams advance together: row m is frame m % c of stream m / c, the rings' heads come from the host.
+struct ts_lockstep {
+    int c, head, res_head, out_head;
+    __device__ __forceinline__ ts_where operator()(int m) const {
+        const int s = m / c, i = m - s * c;
+        return {s, head + i, res_head + i, out_head + i};
+    }
+};
+
+// Each row names its stream and position; one position serves every ring.  The stream is clamped: a wrong table gives wrong
+// numbers, never an address outside a ring.
+struct ts_table {
+    const int *row_stream, *row_pos;
+    int S;
+    __device__ __forceinline__ ts_where operator()(int m) const {
+        const int s = min(max(row_stream[m], 0), S - 1), pos = row_pos[m];
+        return {s, pos, pos, pos};
+    }
 };
 
 __device__ __forceinline__ float ts_leaky(float v, float slope) { return v >= 0.f ? v : v * slope; }
 
-template <bool VEC, bool RES_VEC>
-__global__ __launch_bounds__(TS_THREADS) void tcn_stream_conv_kernel(ts_args p) {
-    __shared__ float lds[TS_WAVES * TS_CO * TS_ROWS];
-    const int M = p.S * p.c, co0 = blockIdx.x * TS_CO, m0 = blockIdx.y * TS_ROWS;
+template <bool VEC, bool RES_VEC, class Where>
+__device__ __forceinline__ void ts_block(const ts_args &p, const Where &where, float *lds) {
+    const int M = p.M, co0 = blockIdx.x * TS_CO, m0 = blockIdx.y * TS_ROWS;
     ts_rows rw, rr;
 #pragma unroll
     for (int r = 0; r < TS_ROWS; ++r) {
-        const int m = min(m0 + r, M - 1), s = m / p.c, i = m - s * p.c;
-        rw.base[r] = (size_t)s * p.R;
-        rw.pos[r] = p.head + i;
-        rr.base[r] = (size_t)s * p.res_R;
-        rr.pos[r] = p.res_head + i;
+        const ts_where at = where(min(m0 + r, M - 1));
+        rw.base[r] = (size_t)at.s * p.R;
+        rw.pos[r] = at.pos;
+        rr.base[r] = (size_t)at.s * p.res_R;
+        rr.pos[r] = at.res_pos;
     }
     float acc[TS_CO][TS_ROWS];
 #pragma unroll
@@ -135,18 +167,30 @@ __global__ __launch_bounds__(TS_THREADS) void tcn_stream_conv_kernel(ts_args p) 
     if (threadIdx.x >= TS_CO * TS_ROWS) return;
     const int a = threadIdx.x % TS_CO, r = threadIdx.x / TS_CO, co = co0 + a, m = m0 + r;
     if (co >= p.Cout || m >= M) return;
-    const int s = m / p.c, i = m - s * p.c;
+    const ts_where at = where(m);
     float v = ts_leaky(conv + p.bias[co], p.slope);
     if (p.res_ring) {
         float res;
         if (p.res_w)
             res = proj + p.res_bias[co];
         else
-            res = p.res_ring[((size_t)s * p.res_R + (size_t)((p.res_head + i) & (p.res_R - 1))) * p.Cout + co];
+            res = p.res_ring[((size_t)at.s * p.res_R + (size_t)(at.res_pos & (p.res_R - 1))) * p.Cout + co];
         v = ts_leaky(v + res, p.slope);
     }
-    if (p.out_ring) p.out_ring[((size_t)s * p.out_R + (size_t)((p.out_head + i) & (p.out_R - 1))) * p.Cout + co] = v;
+    if (p.out_ring) p.out_ring[((size_t)at.s * p.out_R + (size_t)(at.out_pos & (p.out_R - 1))) * p.Cout + co] = v;
     if (p.out_dense) p.out_dense[(size_t)m * p.Cout + co] = v;
+}
+
+template <bool VEC, bool RES_VEC>
+__global__ __launch_bounds__(TS_THREADS) void tcn_stream_conv_kernel(ts_args p, ts_lockstep where) {
+    __shared__ float lds[TS_WAVES * TS_CO * TS_ROWS];
+    ts_block<VEC, RES_VEC>(p, where, lds);
+}
+
+template <bool VEC, bool RES_VEC>
+__global__ __launch_bounds__(TS_THREADS) void tcn_stream_conv_rows_kernel(ts_args p, ts_table where) {
+    __shared__ float lds[TS_WAVES * TS_CO * TS_ROWS];
+    ts_block<VEC, RES_VEC>(p, where, lds);
 }
 
 __global__ void tcn_stream_append_kernel(const float *__restrict__ rows, float *__restrict__ ring, int c, int C, int R, int head,
@@ -160,7 +204,19 @@ __global__ void tcn_stream_append_kernel(const float *__restrict__ rows, float *
     ring[(s * R + (size_t)((head + i) & (R - 1))) * C + ch] = rows[idx];
 }
 
+__global__ void tcn_stream_append_rows_kernel(const float *__restrict__ rows, float *__restrict__ ring,
+                                              const int *__restrict__ row_stream, const int *__restrict__ row_pos, int S, int C,
+                                              int R, size_t n) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const size_t m = idx / C;
+    const int ch = (int)(idx - m * C);
+    const size_t s = (size_t)min(max(row_stream[m], 0), S - 1);
+    ring[(s * R + (size_t)(row_pos[m] & (R - 1))) * C + ch] = rows[idx];
+}
+
 static bool ts_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+static bool ts_ring_len(int v) { return ts_pow2(v) && v <= (1 << 30); }   // row positions are kept modulo 2^30
 static bool ts_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace cer
@@ -198,16 +254,16 @@ extern "C" int cer_tcn_stream_conv(const cer_tcn_stream_desc *d, const float *ri
     p.ring = ring; p.w = w; p.bias = bias;
     p.res_ring = res_ring; p.res_w = res_w; p.res_bias = res_bias;
     p.out_ring = out_ring; p.out_dense = out_dense;
-    p.S = d->S; p.c = d->c; p.Cin = d->Cin; p.Cout = d->Cout; p.k = d->k; p.dil = d->dil; p.R = d->R; p.head = d->head;
-    p.res_C = res_ring ? d->res_C : 1; p.res_R = res_ring ? d->res_R : 1; p.res_head = res_ring ? d->res_head : 0;
-    p.out_R = out_ring ? d->out_R : 1; p.out_head = out_ring ? d->out_head : 0;
+    p.M = (int)M; p.Cin = d->Cin; p.Cout = d->Cout; p.k = d->k; p.dil = d->dil; p.R = d->R;
+    p.res_C = res_ring ? d->res_C : 1; p.res_R = res_ring ? d->res_R : 1; p.out_R = out_ring ? d->out_R : 1;
     p.slope = d->slope;
+    const ts_lockstep where = {d->c, d->head, res_ring ? d->res_head : 0, out_ring ? d->out_head : 0};
     const bool vec = d->Cin % 4 == 0 && ts_al16(ring), rvec = res_w && d->res_C % 4 == 0 && ts_al16(res_ring);
     const dim3 grid((d->Cout + TS_CO - 1) / TS_CO, (unsigned)ytiles), block(TS_THREADS);
-    if (vec && rvec) CER_LAUNCH((tcn_stream_conv_kernel<true, true>), grid, block, 0, ST, p);
-    else if (vec) CER_LAUNCH((tcn_stream_conv_kernel<true, false>), grid, block, 0, ST, p);
-    else if (rvec) CER_LAUNCH((tcn_stream_conv_kernel<false, true>), grid, block, 0, ST, p);
-    else CER_LAUNCH((tcn_stream_conv_kernel<false, false>), grid, block, 0, ST, p);
+    if (vec && rvec) CER_LAUNCH((tcn_stream_conv_kernel<true, true>), grid, block, 0, ST, p, where);
+    else if (vec) CER_LAUNCH((tcn_stream_conv_kernel<true, false>), grid, block, 0, ST, p, where);
+    else if (rvec) CER_LAUNCH((tcn_stream_conv_kernel<false, true>), grid, block, 0, ST, p, where);
+    else CER_LAUNCH((tcn_stream_conv_kernel<false, false>), grid, block, 0, ST, p, where);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }
@@ -221,6 +277,68 @@ extern "C" int cer_tcn_stream_append(const float *rows, float *ring, int S, int 
     const size_t n = (size_t)S * c * C;
     if (n > (size_t)0x7fffffff * 256) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append: too many elements");
     CER_LAUNCH(tcn_stream_append_kernel, dim3(cer_blocks(n, 256)), dim3(256), 0, ST, rows, ring, c, C, R, head, n);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_tcn_stream_conv_rows(const cer_tcn_stream_rows_desc *d, const int32_t *row_stream, const int32_t *row_pos,
+                                        const float *ring, const float *w, const float *bias, const float *res_ring,
+                                        const float *res_w, const float *res_bias, float *out_ring, float *out_dense,
+                                        void *stream) {
+    if (!d || !row_stream || !row_pos || !ring || !w || !bias || (!out_ring && !out_dense))
+        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: null pointer");
+    if ((res_w && (!res_ring || !res_bias)) || (!res_w && res_bias))
+        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: res_w and res_bias come together, with res_ring");
+    if (d->S < 1 || d->M < 1 || d->max_count < 1 || d->Cin < 1 || d->Cout < 1 || d->k < 1 || d->dil < 1)
+        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: S, M, max_count, Cin, Cout, k and dil must be >= 1");
+    if (!ts_ring_len(d->R) || (out_ring && !ts_ring_len(d->out_R)) || (res_ring && !ts_ring_len(d->res_R)))
+        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: ring length R = %d (out %d, res %d) is not a power of "
+                             "two up to 2^30", d->R, d->out_R, d->res_R);
+    if ((long long)(d->k - 1) * d->dil + d->max_count > d->R || (out_ring && d->max_count > d->out_R) ||
+        (res_ring && d->max_count > d->res_R))
+        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: max_count = %d new frames of a stream plus "
+                             "(k - 1) * dil = %lld of history exceed R = %d (out %d, res %d)", d->max_count,
+                             (long long)(d->k - 1) * d->dil, d->R, d->out_R, d->res_R);
+    if (res_ring && (res_w ? d->res_C < 1 : d->res_C != d->Cout))
+        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: residual ring of %d channels for Cout = %d without a "
+                             "projection", d->res_C, d->Cout);
+    if (!ts_al16(w) || (res_w && !ts_al16(res_w)))
+        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: packed weights must be 16-byte aligned");
+    const long long ytiles = ((long long)d->M + TS_ROWS - 1) / TS_ROWS;
+    if (ytiles > 65535) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: M = %d rows exceed the grid", d->M);
+    ts_args p;
+    p.ring = ring; p.w = w; p.bias = bias;
+    p.res_ring = res_ring; p.res_w = res_w; p.res_bias = res_bias;
+    p.out_ring = out_ring; p.out_dense = out_dense;
+    p.M = d->M; p.Cin = d->Cin; p.Cout = d->Cout; p.k = d->k; p.dil = d->dil; p.R = d->R;
+    p.res_C = res_ring ? d->res_C : 1; p.res_R = res_ring ? d->res_R : 1; p.out_R = out_ring ? d->out_R : 1;
+    p.slope = d->slope;
+    const ts_table where = {row_stream, row_pos, d->S};
+    const bool vec = d->Cin % 4 == 0 && ts_al16(ring), rvec = res_w && d->res_C % 4 == 0 && ts_al16(res_ring);
+    const dim3 grid((d->Cout + TS_CO - 1) / TS_CO, (unsigned)ytiles), block(TS_THREADS);
+    if (vec && rvec) CER_LAUNCH((tcn_stream_conv_rows_kernel<true, true>), grid, block, 0, ST, p, where);
+    else if (vec) CER_LAUNCH((tcn_stream_conv_rows_kernel<true, false>), grid, block, 0, ST, p, where);
+    else if (rvec) CER_LAUNCH((tcn_stream_conv_rows_kernel<false, true>), grid, block, 0, ST, p, where);
+    else CER_LAUNCH((tcn_stream_conv_rows_kernel<false, false>), grid, block, 0, ST, p, where);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_tcn_stream_append_rows(const float *rows, float *ring, const int32_t *row_stream, const int32_t *row_pos,
+                                          int S, int M, int max_count, int C, int R, void *stream) {
+    if (!rows || !ring || !row_stream || !row_pos)
+        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append_rows: null pointer");
+    if (S < 1 || M < 1 || max_count < 1 || C < 1)
+        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append_rows: S, M, max_count and C must be >= 1");
+    if (!ts_ring_len(R))
+        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append_rows: ring length R = %d is not a power of two up to 2^30", R);
+    if (max_count > R)
+        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append_rows: max_count = %d new frames of a stream exceed R = %d",
+                             max_count, R);
+    const size_t n = (size_t)M * C;
+    if (n > (size_t)0x7fffffff * 256) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append_rows: too many elements");
+    CER_LAUNCH(tcn_stream_append_rows_kernel, dim3(cer_blocks(n, 256)), dim3(256), 0, ST, rows, ring, row_stream, row_pos, S, C, R,
+               n);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }

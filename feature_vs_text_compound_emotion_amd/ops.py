@@ -1690,3 +1690,92 @@ def tcn_stream_conv(ring, head, c, w_packed, bias, k, dil, *, res_ring=None, res
           "cer_tcn_stream_conv")
     if STREAM_TRACE is not None:
         STREAM_TRACE.append(("conv", wbytes))
+
+
+ROW_POS_MOD = 1 << 30   # row positions travel modulo 2^30: every ring length divides it, so each launch's mask sees the same slot
+
+
+def stream_row_table(positions, counts, device):
+    """The row table of one ragged push: stream s brings ``counts[s]`` frames, the first at position ``positions[s]`` (frames
+    that stream has been pushed so far).  Returns (row_stream, row_pos), int32 [M] each on ``device``: rows stream-major in
+    ascending stream order, a stream's frames in time order, positions modulo 2^30; a stream with count 0 has no row.
+    Built from Python ints and uploaded in one fresh tensor per call (no staging buffer an unfinished copy could still read)."""
+    positions, counts = [int(p) for p in positions], [int(c) for c in counts]
+    if len(positions) != len(counts):
+        raise ValueError(f"stream_row_table: {len(positions)} positions for {len(counts)} counts")
+    for s, (p, c) in enumerate(zip(positions, counts)):
+        if c < 0 or p < 0:
+            raise ValueError(f"stream_row_table: stream {s} has count {c} at position {p}: both must be >= 0")
+    streams = [s for s, c in enumerate(counts) for _ in range(c)]
+    pos = [(p + i) % ROW_POS_MOD for p, c in zip(positions, counts) for i in range(c)]
+    table = torch.tensor([streams, pos], dtype=torch.int32, device=device).view(2, len(streams))
+    return table[0], table[1]
+
+
+def _row_table(row_stream, row_pos, ring):
+    """Both tables int32, contiguous, one-dimensional, on the ring's device and of one length M >= 1.  Returns M."""
+    for t, n in ((row_stream, "row_stream"), (row_pos, "row_pos")):
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == ring.device and t.dtype == torch.int32 and t.is_contiguous()
+                and t.dim() == 1):
+            raise ValueError(f"{n}: expected a contiguous int32 vector on the GPU of the ring ({ring.device}), got "
+                             f"{(t.dtype, t.device, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
+    if row_stream.shape[0] != row_pos.shape[0] or row_stream.shape[0] < 1:
+        raise ValueError(f"row_stream / row_pos: expected one length M >= 1, got {row_stream.shape[0]} and {row_pos.shape[0]}")
+    return row_stream.shape[0]
+
+
+def tcn_stream_append_rows(rows, ring, row_stream, row_pos, max_count):
+    """ring[row_stream[m], row_pos[m] % R, :] = rows[m, :]: ``rows`` [M, C] dense, ``ring`` [S, R, C], the tables of
+    ``stream_row_table``; ``max_count``: the most rows any one stream has in them."""
+    s, r, ch = _ring(ring, "ring")
+    m = _row_table(row_stream, row_pos, ring)
+    _dev_f32(rows, "rows")
+    if rows.dim() != 2 or rows.shape[0] != m or rows.shape[1] != ch:
+        raise ValueError(f"rows: expected [{m}, {ch}], got {tuple(rows.shape)}")
+    check(_lib.load().cer_tcn_stream_append_rows(ptr(rows), ptr(ring), ptr(row_stream), ptr(row_pos), s, m, int(max_count), ch, r,
+                                                 current_stream()), "cer_tcn_stream_append_rows")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("append_rows", 0))
+
+
+def tcn_stream_conv_rows(ring, row_stream, row_pos, max_count, w_packed, bias, k, dil, *, res_ring=None, res_w=None,
+                         res_bias=None, out_ring=None, out_dense=None, slope=LEAKY_SLOPE):
+    """``tcn_stream_conv`` over the M rows of a row table instead of the c newest frames of every stream: row m is the frame
+    of stream ``row_stream[m]`` at position ``row_pos[m]`` in ``ring``, ``res_ring`` and ``out_ring`` alike (each masks the
+    position with its own length); ``out_dense`` is [M, Cout].  A stream's rows are consecutive positions, at most
+    ``max_count`` of them.  The same bits as the lockstep launch gives the same frames."""
+    s, r, cin = _ring(ring, "ring")
+    m = _row_table(row_stream, row_pos, ring)
+    _dev_f32(bias, "bias")
+    cout = bias.shape[0]
+    c4 = lambda n: -(-n // 4) * 4   # noqa: E731
+    _dev_f32(w_packed, "w_packed", shape=(c4(cout), k, c4(cin)))
+    d = _lib.TcnStreamRowsDesc(S=s, M=m, max_count=int(max_count), Cin=cin, Cout=cout, k=int(k), dil=int(dil), R=r,
+                               slope=float(slope))
+    wbytes = w_packed.numel() * 4
+    if res_ring is not None:
+        rs, d.res_R, d.res_C = _ring(res_ring, "res_ring")
+        if rs != s:
+            raise ValueError(f"res_ring: expected {s} streams, got {rs}")
+        if res_w is not None:
+            _dev_f32(res_w, "res_w", shape=(c4(cout), 1, c4(d.res_C)))
+            _dev_f32(res_bias, "res_bias", shape=(cout,))
+            if res_bias is None:
+                raise ValueError("res_bias: the projection needs its bias")
+            wbytes += res_w.numel() * 4
+        elif d.res_C != cout:
+            raise ValueError(f"res_ring: {d.res_C} channels for Cout = {cout} and no projection")
+    elif res_w is not None or res_bias is not None:
+        raise ValueError("res_w / res_bias without res_ring")
+    if out_ring is None and out_dense is None:
+        raise ValueError("tcn_stream_conv_rows: no output")
+    if out_ring is not None:
+        os_, d.out_R, _ = _ring(out_ring, "out_ring", cout)
+        if os_ != s:
+            raise ValueError(f"out_ring: expected {s} streams, got {os_}")
+    _dev_f32(out_dense, "out_dense", shape=(m, cout))
+    check(_lib.load().cer_tcn_stream_conv_rows(ctypes.byref(d), ptr(row_stream), ptr(row_pos), ptr(ring), ptr(w_packed), ptr(bias),
+                                               ptr(res_ring), ptr(res_w), ptr(res_bias), ptr(out_ring), ptr(out_dense),
+                                               current_stream()), "cer_tcn_stream_conv_rows")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("conv_rows", wbytes))

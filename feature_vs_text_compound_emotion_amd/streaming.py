@@ -1,13 +1,18 @@
-"""Streaming inference: the causal TCN run a few frames at a time over device-side rings of past frames, and LFAN on top.
+"""Streaming inference: the causal TCN run a few frames at a time over device-side rings of past frames, and LFAN or CAN on
+top.
 
 Everything in LFAN is causal or per frame (the TCN pads left only, eval BatchNorm1d is a per-row affine, the cross-modal
 attention mixes modalities and not time, LayerNorm and the regressor are per row), so frame t's output is a function of frames
-<= t: pushing the frames of a sequence in any chunking returns what the whole-sequence forward returns.
+<= t: pushing the frames of a sequence in any chunking returns what the whole-sequence forward returns.  The same holds for CAN
+(the same TCN front; AttentionFusion, fc1, eval bn1 and fc2 work row by row).  JMT / MT attend over time and cannot stream.
 
 State of one ``TemporalBlock`` for S streams (csrc/tcn_stream.hip): ``xring`` [S, R, Cin] holds its past inputs and ``hring``
-[S, R, Cout] its past first-conv activations, fp32 channels-last, R the power of two >= (k - 1) d + max_new.  The streams advance
-together, so one host integer (frames pushed so far) gives every ring's write position; a reset stream's rings are zero, which
-is the reference's left zero-pad.  Per push of c <= max_new frames a block costs two launches:
+[S, R, Cout] its past first-conv activations, fp32 channels-last, R the power of two >= (k - 1) d + max_new.  Each stream
+advances on its own: the host keeps one integer per stream (frames pushed so far), which gives that stream's write position in
+every ring; a reset stream's rings are zero, which is the reference's left zero-pad.  While all streams stand at one position a
+dense push runs the lockstep launches (one ``head`` per ring); otherwise, and for every ragged push, the host uploads a row
+table (stream and position of each new row) that all launches of the push share.  The bits are the same either way.  Per push
+of up to max_new frames per stream a block costs two launches:
 
   phase A   hring[new] = leaky(conv(xring) + b1)
   phase B   next block's xring[new] (or the dense output) = leaky(leaky(conv(hring) + b2) + res(xring[new]))
@@ -17,6 +22,7 @@ An output value depends on its own stream's history only: not on S, c, the ring 
 import torch
 
 from . import ops
+from .fusion_heads import BN_EPS as CAN_BN_EPS, BN_MOMENTUM as CAN_BN_MOMENTUM, CAN
 from .lfan import BN_EPS, BN_MOMENTUM, LFAN, LN_EPS, REGRESSION, _packed
 from .temporal_convnet import TemporalConvNet
 
@@ -39,16 +45,53 @@ def block_push(pack, xring, hring, pos, c, out_ring=None, out_pos=0, out_dense=N
                         out_head=out_pos & (out_ring.shape[1] - 1) if out_ring is not None else 0, out_dense=out_dense, slope=slope)
 
 
-def _check_rows(x, name, streams, channels):
+def block_push_rows(pack, xring, hring, row_stream, row_pos, max_count, out_ring=None, out_dense=None, slope=ops.LEAKY_SLOPE):
+    """``block_push`` over the rows of a row table (``ops.stream_row_table``) already written to ``xring``: the same two
+    launches, each stream at its own position."""
+    ops.tcn_stream_conv_rows(xring, row_stream, row_pos, max_count, pack["w1"], pack["b1"], pack["k"], pack["dil"], out_ring=hring,
+                             slope=slope)
+    ops.tcn_stream_conv_rows(hring, row_stream, row_pos, max_count, pack["w2"], pack["b2"], pack["k"], pack["dil"], res_ring=xring,
+                             res_w=pack["dsw"], res_bias=pack["dsb"], out_ring=out_ring, out_dense=out_dense, slope=slope)
+
+
+def _check_tensor(x, name):
     if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32):
         raise ValueError(f"{name}: expected a float32 tensor on the GPU, got "
                          f"{(x.dtype, x.device) if torch.is_tensor(x) else type(x)}")
+
+
+def _check_rows(x, name, streams, channels):
+    _check_tensor(x, name)
     if x.dim() != 3 or x.shape[0] != streams or x.shape[2] != channels or x.shape[1] < 1:
         raise ValueError(f"{name}: expected [{streams} streams, c >= 1 new frames, {channels}], got {tuple(x.shape)}")
 
 
+def _check_counts(counts, streams, max_new):
+    """``counts``: how many new frames each of ``streams`` streams brings, 0 .. ``max_new`` each.  Returns them as ints."""
+    try:
+        counts = [int(c) for c in counts]
+    except TypeError:
+        raise ValueError(f"counts: expected a sequence of {streams} ints, got {type(counts).__name__}") from None
+    if len(counts) != streams:
+        raise ValueError(f"counts: expected one count per stream ({streams}), got {len(counts)}")
+    for s, c in enumerate(counts):
+        if not 0 <= c <= max_new:
+            raise ValueError(f"counts: stream {s} brings {c} frames, outside 0 .. max_new = {max_new}")
+    return counts
+
+
+def _check_packed(x, name, rows, tail):
+    """x [M, *tail] with M = ``rows``, the sum of the counts."""
+    _check_tensor(x, name)
+    if tuple(x.shape[1:]) != tuple(tail) or x.dim() != 1 + len(tail):
+        raise ValueError(f"{name}: expected [M, {', '.join(str(t) for t in tail)}], got {tuple(x.shape)}")
+    if x.shape[0] != rows:
+        raise ValueError(f"{name}: {x.shape[0]} rows for counts that sum to {rows}")
+
+
 class TCNStream:
-    """``TemporalConvNet`` in eval mode, a few frames at a time, for ``streams`` parallel sequences."""
+    """``TemporalConvNet`` in eval mode, a few frames at a time, for ``streams`` parallel sequences.  Every stream has its
+    own write position: ``push_rows`` advances all of them by the same c frames, ``push_ragged`` each by its own count."""
 
     def __init__(self, net, streams, max_new=32):
         if not isinstance(net, TemporalConvNet):
@@ -65,7 +108,7 @@ class TCNStream:
         self.hrings = [alloc((streams, r, b.cout)) for b, r in zip(net.network, self.ring_frames)]
         self.cin, self.cout = net.network[0].cin, net.network[-1].cout
         self.frames_seen = [0] * streams
-        self._pos = 0          # frames pushed since construction: ring l writes at _pos & (R_l - 1)
+        self._pos = [0] * streams   # frames pushed per stream since construction: stream s writes ring l at _pos[s] & (R_l - 1)
         self._packs, self._key = None, None
 
     def _pack(self):
@@ -85,7 +128,8 @@ class TCNStream:
         return self._packs
 
     def reset(self, streams=None):
-        """Forget the past of ``streams`` (indices; None = all): their rings become the zero left-pad again."""
+        """Forget the past of ``streams`` (indices; None = all): their rings become the zero left-pad again.  Their write
+        positions stay where they are: a zeroed ring is an empty past at any position."""
         idx = list(range(self.streams)) if streams is None else [int(s) for s in streams]
         for s in idx:
             if not 0 <= s < self.streams:
@@ -98,50 +142,98 @@ class TCNStream:
         for s in idx:
             self.frames_seen[s] = 0
 
-    @torch.no_grad()
-    def push_rows(self, x):
-        """x [S, c, Cin]: the next c frames of every stream -> [S, c, Cout], the net's output at those frames."""
+    def _check_eval(self):
         if self.net.training:
             raise RuntimeError("TCNStream: the net is in train mode (dropout); call .eval() first")
+
+    def _lockstep(self, x, dense):
+        """x [S, n, Cin], n <= max_new, all streams at one position: the dense launches."""
+        pos, n, last = self._pos[0], x.shape[1], len(self.xrings) - 1
+        ops.tcn_stream_append(x, self.xrings[0], pos & (self.ring_frames[0] - 1))
+        for lvl, pack in enumerate(self._pack()):
+            if lvl < last:
+                block_push(pack, self.xrings[lvl], self.hrings[lvl], pos, n, out_ring=self.xrings[lvl + 1], out_pos=pos)
+            else:
+                block_push(pack, self.xrings[lvl], self.hrings[lvl], pos, n, out_dense=dense)
+
+    def _ragged(self, x, counts, dense):
+        """x [M, Cin] packed stream-major, counts[s] <= max_new frames of stream s, M >= 1: one table upload, one append and
+        two launches per block, each stream at its own position."""
+        row_stream, row_pos = ops.stream_row_table(self._pos, counts, self.device)
+        most, last = max(counts), len(self.xrings) - 1
+        ops.tcn_stream_append_rows(x, self.xrings[0], row_stream, row_pos, most)
+        for lvl, pack in enumerate(self._pack()):
+            if lvl < last:
+                block_push_rows(pack, self.xrings[lvl], self.hrings[lvl], row_stream, row_pos, most, out_ring=self.xrings[lvl + 1])
+            else:
+                block_push_rows(pack, self.xrings[lvl], self.hrings[lvl], row_stream, row_pos, most, out_dense=dense)
+
+    def _advance(self, counts):
+        self._pos = [p + c for p, c in zip(self._pos, counts)]
+        self.frames_seen = [f + c for f, c in zip(self.frames_seen, counts)]
+
+    @torch.no_grad()
+    def push_rows(self, x):
+        """x [S, c, Cin]: the next c frames of every stream -> [S, c, Cout], the net's output at those frames.  While the
+        streams share one position this is the lockstep launches; after ragged pushes it goes through the row table, with
+        the same bits."""
+        self._check_eval()
         _check_rows(x, "x", self.streams, self.cin)
         x = x.contiguous()
-        packs, c, last = self._pack(), x.shape[1], len(self.xrings) - 1
+        c = x.shape[1]
         out = torch.empty((self.streams, c, self.cout), device=self.device, dtype=torch.float32)
         for c0 in range(0, c, self.max_new):
             n = min(self.max_new, c - c0)
             whole = n == c
-            ops.tcn_stream_append(x if whole else x[:, c0:c0 + n].contiguous(), self.xrings[0],
-                                  self._pos & (self.ring_frames[0] - 1))
+            chunk = x if whole else x[:, c0:c0 + n].contiguous()
             dense = out if whole else torch.empty((self.streams, n, self.cout), device=self.device, dtype=torch.float32)
-            for lvl, pack in enumerate(packs):
-                if lvl < last:
-                    block_push(pack, self.xrings[lvl], self.hrings[lvl], self._pos, n, out_ring=self.xrings[lvl + 1],
-                               out_pos=self._pos)
-                else:
-                    block_push(pack, self.xrings[lvl], self.hrings[lvl], self._pos, n,
-                               out_dense=dense.view(self.streams * n, self.cout))
+            if len(set(self._pos)) == 1:
+                self._lockstep(chunk, dense.view(self.streams * n, self.cout))
+            else:
+                self._ragged(chunk.view(self.streams * n, self.cin), [n] * self.streams, dense.view(self.streams * n, self.cout))
             if not whole:
                 out[:, c0:c0 + n] = dense
-            self._pos += n
-        self.frames_seen = [f + c for f in self.frames_seen]
+            self._advance([n] * self.streams)
+        return out
+
+    @torch.no_grad()
+    def push_ragged(self, x, counts):
+        """x [M, Cin]: ``counts[s]`` (0 .. max_new) new frames of stream s, packed stream-major in ascending stream order,
+        each stream's frames in time order, M = sum(counts) -> [M, Cout] in the same row order.  A stream that brings nothing
+        is left as it is; all-zero counts return an empty [0, Cout] without a launch."""
+        self._check_eval()
+        counts = _check_counts(counts, self.streams, self.max_new)
+        _check_packed(x, "x", sum(counts), (self.cin,))
+        out = torch.empty((x.shape[0], self.cout), device=self.device, dtype=torch.float32)
+        if x.shape[0]:
+            self._ragged(x.contiguous(), counts, out)
+            self._advance(counts)
         return out
 
 
-class LFANStream:
-    """An eval-mode ``LFAN`` on live streams: ``push`` the next c frames of ``streams`` sequences, get their logits.
-    The model's ``example_length`` plays no part."""
+class _ModelStream:
+    """What ``LFANStream`` and ``CANStream`` share: one ``TCNStream`` per modality behind the model's encoders, the key, shape
+    and count checks, and the four ways to push.  A subclass names the model class it runs, the order in which the TCN outputs
+    meet its head, and the head itself on rows."""
 
-    def __init__(self, model, streams, max_new=32):
-        if not isinstance(model, LFAN):
-            raise TypeError(f"LFANStream needs an LFAN (JMT / MT attend over time and are not causal), got {type(model).__name__}")
+    _model_class, _needs = None, ""
+
+    def __init__(self, model, streams, max_new=32, encoder_batch=8):
+        name = type(self).__name__
+        if encoder_batch is not None and encoder_batch < 1:
+            raise ValueError(f"encoder_batch = {encoder_batch}: a positive number of frames per encoder call, or None")
+        self.encoder_batch = encoder_batch
+        if not isinstance(model, self._model_class):
+            raise TypeError(f"{name} needs {self._needs} (JMT / MT attend over time and are not causal), got {type(model).__name__}")
         if model.training:
-            raise RuntimeError("LFANStream: the model is in train mode; batch statistics are undefined frame by frame -- call .eval()")
+            raise RuntimeError(f"{name}: the model is in train mode; batch statistics are undefined frame by frame -- call .eval()")
         self.model, self.streams, self.max_new = model, streams, max_new
-        self.tcn = {m: TCNStream(model.temporal[m], streams, max_new) for m in model.modality}
+        self.modalities = list(self._modalities(model))
+        self.tcn = {m: TCNStream(model.temporal[m], streams, max_new) for m in self.modalities}
 
     @property
     def frames_seen(self):
-        return self.tcn[self.model.modality[0]].frames_seen
+        return self.tcn[self.modalities[0]].frames_seen
 
     @property
     def ring_frames(self):
@@ -154,18 +246,17 @@ class LFANStream:
     def _check_keys(self, X):
         model = self.model
         if model.training:
-            raise RuntimeError("LFANStream: the model is in train mode; batch statistics are undefined frame by frame -- call .eval()")
+            raise RuntimeError(f"{type(self).__name__}: the model is in train mode; batch statistics are undefined frame by frame "
+                               "-- call .eval()")
         for m in X:
             if m not in model.temporal:
                 raise KeyError(m)
-        for m in model.modality:
+        for m in self.modalities:
             if m not in X:
                 raise KeyError(m)
 
     def _check_input(self, m, x):
-        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32):
-            raise ValueError(f"{m}: expected a float32 tensor on the GPU, got "
-                             f"{(x.dtype, x.device) if torch.is_tensor(x) else type(x)}")
+        _check_tensor(x, m)
         s = self.streams
         if m == "video":
             ok, c = x.dim() == 5 and x.shape[0] == s and x.shape[2] == 3, x.shape[1] if x.dim() == 5 else 0
@@ -174,37 +265,88 @@ class LFANStream:
             ok, c = x.dim() == 4 and x.shape[0] == s and x.shape[1] == 64 and x.shape[3] == 96, x.shape[2] if x.dim() == 4 else 0
             want = f"[{s}, 64, c, 96]"
         else:
-            e = self.model.embedding_dim[m]
+            e = self.tcn[m].cin
             ok, c = x.dim() == 4 and x.shape[0] == s and x.shape[1] == 1 and x.shape[3] == e, x.shape[2] if x.dim() == 4 else 0
             want = f"[{s}, 1, c, {e}]"
         if not ok or c < 1:
             raise ValueError(f"{m}: expected {want} for {s} streams, got {tuple(x.shape)}")
         return c
 
-    @torch.no_grad()
-    def push(self, X):
-        """X keyed like ``LFAN.forward``'s dict with c new frames in place of L (video [S,c,3,H,W], vggish [S,1,c,128],
-        bert [S,1,c,768], logmel [S,64,c,96]) -> logits [S, c, n_cls] (tanh-ed for REGRESSION).  X is left as it is."""
-        self._check_keys(X)
-        model, s = self.model, self.streams
-        cs = {m: self._check_input(m, X[m]) for m in X}
+    def _check_packed_input(self, m, x, rows):
+        if m == "video":
+            hw = tuple(x.shape[2:]) if torch.is_tensor(x) and x.dim() == 4 else ("H", "W")
+            _check_packed(x, m, rows, (3,) + hw)
+        elif m == "logmel":
+            _check_packed(x, m, rows, (64, 96))
+        else:
+            _check_packed(x, m, rows, (self.tcn[m].cin,))
+
+    @staticmethod
+    def _one_count(cs):
         if len(set(cs.values())) != 1:
             raise ValueError(f"the modalities bring different numbers of new frames: {cs}")
-        c = next(iter(cs.values()))
+        return next(iter(cs.values()))
+
+    def _in_groups(self, encoder, frames):
+        """``encoder`` over ``frames`` [N, ...] in calls of exactly ``encoder_batch`` frames, the last call filled up with zero
+        frames whose rows are dropped.  The conv kernels pick their tile variant, and with it the order of their K sums, from
+        the number of rows of a call; with every call the same size, a frame's embedding is the same bits however many frames
+        the push brought.  ``encoder_batch`` None: one call per push (fewer launches; the bits then depend on the push size)."""
+        g, n = self.encoder_batch, frames.shape[0]
+        if g is None:
+            return encoder(frames)
+        outs = []
+        for i in range(0, n, g):
+            part = frames[i:i + g]
+            if part.shape[0] < g:
+                full = frames.new_zeros((g,) + tuple(frames.shape[1:]))
+                full[:part.shape[0]] = part
+                part = full
+            outs.append(encoder(part.contiguous()))
+        return torch.cat(outs)[:n]
+
+    def _encode(self, X, packed):
+        """The encoders as the model's forward runs them, ``encoder_batch`` frames per call: X[m] -> rows
+        [M, embedding_dim[m]] (M = S c, stream-major)."""
+        model = self.model
         if "visual" in model.spatial:
             model.spatial["visual"].backbone.check_sync_release()
         feats = {}
-        for m in X:   # the encoders exactly as LFAN.forward runs them
+        for m in X:
             x = X[m]
             if m == "video":
                 vis = model.spatial["visual"]
                 vis.backbone.dropout_seed = model.dropout_seed
-                feats[m] = vis(x.reshape(-1, *x.shape[2:]), None).view(s, c, -1)
+                feats[m] = self._in_groups(lambda f: vis(f, None), x if packed else x.reshape(-1, *x.shape[2:]))
             elif m == "logmel":
-                feats[m] = model.spatial["audio"](x.permute(0, 2, 3, 1).contiguous().view(-1, 96, 64)).view(s, c, -1)
+                frames = x.permute(0, 2, 1) if packed else x.permute(0, 2, 3, 1)
+                feats[m] = self._in_groups(model.spatial["audio"], frames.contiguous().view(-1, 96, 64))
             else:
-                feats[m] = x.reshape(s, c, x.shape[-1])
-        return self._tail(feats, c)
+                feats[m] = x.reshape(-1, x.shape[-1])
+        return feats
+
+    def _run(self, feats, c=None, counts=None):
+        """feats[m] [M, E_m] rows -> logits: [S, c, n_cls] of a dense push, [M, n_cls] of a ragged one."""
+        order = self._order(feats)
+        if counts is None:
+            t = [self.tcn[m].push_rows(feats[m].detach().view(self.streams, c, -1)).view(self.streams * c, -1) for m in order]
+        else:
+            t = [self.tcn[m].push_ragged(feats[m].detach(), counts) for m in order]
+        logits = self._head(order, t)
+        out = logits if counts is not None else logits.view(self.streams, c, -1)
+        return ops.tanh_fwd(out) if self.model.task == REGRESSION else out
+
+    def _nothing(self):
+        """No stream brought a frame: no rows, no launch."""
+        return torch.empty((0, self._n_out()), device=self.tcn[self.modalities[0]].device, dtype=torch.float32)
+
+    @torch.no_grad()
+    def push(self, X):
+        """X keyed like the model's ``forward`` dict with c new frames in place of L (video [S,c,3,H,W], vggish [S,1,c,128],
+        bert [S,1,c,768], logmel [S,64,c,96]) -> logits [S, c, n_cls] (tanh-ed for REGRESSION).  X is left as it is."""
+        self._check_keys(X)
+        c = self._one_count({m: self._check_input(m, X[m]) for m in X})
+        return self._run(self._encode(X, packed=False), c=c)
 
     @torch.no_grad()
     def push_features(self, F):
@@ -212,15 +354,53 @@ class LFANStream:
         -> logits [S, c, n_cls].  Skips the encoders."""
         self._check_keys(F)
         for m in F:
-            _check_rows(F[m], m, self.streams, self.model.embedding_dim[m])
-        cs = {m: F[m].shape[1] for m in F}
-        if len(set(cs.values())) != 1:
-            raise ValueError(f"the modalities bring different numbers of new frames: {cs}")
-        return self._tail({m: F[m].contiguous() for m in F}, next(iter(cs.values())))
+            _check_rows(F[m], m, self.streams, self.tcn[m].cin)
+        c = self._one_count({m: F[m].shape[1] for m in F})
+        return self._run({m: F[m].contiguous().view(self.streams * c, -1) for m in F}, c=c)
 
-    def _tail(self, feats, c):
-        model, mods, rows = self.model, list(self.model.modality), self.streams * c
-        t = [self.tcn[m].push_rows(feats[m].detach()).view(rows, -1) for m in mods]
+    @torch.no_grad()
+    def push_ragged(self, X, counts):
+        """Stream s brings ``counts[s]`` (0 .. max_new) new frames.  X[m] holds the M = sum(counts) frames without the stream
+        axis, stream-major in ascending stream order, each stream's frames in time order: video [M,3,H,W], logmel [M,64,96],
+        any other modality [M, embedding_dim[m]] -> logits [M, n_cls] in the same row order (tanh-ed for REGRESSION)."""
+        self._check_keys(X)
+        counts = _check_counts(counts, self.streams, self.max_new)
+        for m in X:
+            self._check_packed_input(m, X[m], sum(counts))
+        if not sum(counts):
+            return self._nothing()
+        return self._run(self._encode(X, packed=True), counts=counts)
+
+    @torch.no_grad()
+    def push_features_ragged(self, F, counts):
+        """``push_ragged`` on per-modality embeddings F[m] [M, embedding_dim[m]]: skips the encoders."""
+        self._check_keys(F)
+        counts = _check_counts(counts, self.streams, self.max_new)
+        for m in F:
+            _check_packed(F[m], m, sum(counts), (self.tcn[m].cin,))
+        if not sum(counts):
+            return self._nothing()
+        return self._run({m: F[m].contiguous() for m in F}, counts=counts)
+
+
+class LFANStream(_ModelStream):
+    """An eval-mode ``LFAN`` on live streams: ``push`` the next c frames of ``streams`` sequences, get their logits;
+    ``push_ragged`` when the streams bring different numbers of frames.  The model's ``example_length`` plays no part."""
+
+    _model_class, _needs = LFAN, "an LFAN"
+
+    @staticmethod
+    def _modalities(model):
+        return model.modality
+
+    def _order(self, feats):
+        return self.modalities
+
+    def _n_out(self):
+        return self.model.regressor.weight.shape[0]
+
+    def _head(self, mods, t):
+        model, rows = self.model, t[0].shape[0]
         attn, norm1 = model.fusion.layers.self_attn, model.fusion.layers.norm1
         # the head of LFANHeadFunction.forward in eval mode, on the same row kernels; BatchNorm of the leader and the
         # LayerNorm write straight into their column slices of the regressor's input
@@ -235,19 +415,54 @@ class LFANStream:
         vals, _ = ops.lfan_attn_fwd(qkvs, attn.num_heads, attn.head_dim)
         o = ops.linear(vals, _packed(attn.o_proj.weight), bias=attn.o_proj.bias)
         ops.layernorm_fwd(o, norm1.weight, norm1.bias, eps=LN_EPS, out=z[:, enc0:], save=False)
-        logits = ops.linear(z, _packed(model.regressor.weight), bias=model.regressor.bias)
-        out = logits.view(self.streams, c, -1)
-        return ops.tanh_fwd(out) if model.task == REGRESSION else out
+        return ops.linear(z, _packed(model.regressor.weight), bias=model.regressor.bias)
+
+
+class CANStream(_ModelStream):
+    """An eval-mode ``CAN`` on live streams, with ``LFANStream``'s surface.  CAN is as causal as LFAN: the same TCN front, and
+    behind it ``AttentionFusion``, ``fc1``, eval ``bn1`` and ``fc2`` all work row by row.  As in ``CAN.forward``, the caller's
+    key order pairs the modalities with ``fuse.attn[i]``."""
+
+    _model_class, _needs = CAN, "a CAN"
+
+    @staticmethod
+    def _modalities(model):
+        return model.modalities
+
+    def _order(self, feats):
+        return list(feats)
+
+    def _n_out(self):
+        return self.model.fc2.weight.shape[0]
+
+    def _head(self, mods, t):
+        model, rows = self.model, t[0].shape[0]
+        fuse, bn1 = model.fuse, model.bn1
+        # CAN.forward's tail in eval mode on the same row kernels; the per-modality projections write straight into their
+        # column slices of the concatenation
+        width = fuse.attn[0].weight.shape[0]
+        cat = torch.empty((rows, width * len(mods)), device=t[0].device, dtype=torch.float32)
+        for i, m in enumerate(mods):
+            bn, lin = model.bn[m], fuse.attn[i]
+            y, _, _ = ops.bn_rows_fwd(t[i], bn.weight, bn.bias, bn.running_mean, bn.running_var, False, CAN_BN_EPS,
+                                      CAN_BN_MOMENTUM)
+            ops.linear(y, _packed(lin.weight), bias=lin.bias, out=cat[:, i * width:(i + 1) * width])
+        gate = ops.linear(cat, _packed(fuse.weights.weight), bias=fuse.weights.bias)
+        c, _ = ops.softmax_gate_fwd(gate, cat)
+        c = ops.linear(c, _packed(model.fc1.weight), bias=model.fc1.bias)
+        c, _, _ = ops.bn_rows_fwd(c, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, False, CAN_BN_EPS, CAN_BN_MOMENTUM)
+        return ops.linear(ops.leaky_relu(c), _packed(model.fc2.weight), bias=model.fc2.bias)
 
 
 _TIME_AXIS = {"video": 1}   # every other modality: axis 2
 
 
-def stream_forward(model, X, chunk=32):
-    """A whole clip or video of any length T through an eval-mode LFAN, causally, ``chunk`` frames at a time:
+def stream_forward(model, X, chunk=32, encoder_batch=8):
+    """A whole clip or video of any length T through an eval-mode LFAN or CAN, causally, ``chunk`` frames at a time:
     [B, T, n_cls], what ``model(X)`` returns when it is built with ``example_length = T``.  X is left as it is."""
     first = next(iter(X.values()))
-    stream = LFANStream(model, first.shape[0], max_new=chunk)
+    stream = (CANStream if isinstance(model, CAN) else LFANStream)(model, first.shape[0], max_new=chunk,
+                                                                   encoder_batch=encoder_batch)
     stream._check_keys(X)
     total = {m: x.shape[_TIME_AXIS.get(m, 2)] for m, x in X.items()}
     if len(set(total.values())) != 1:

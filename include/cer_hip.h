@@ -621,9 +621,12 @@ int cer_copy_cols(const float *x, int x_ld, float *y, int y_ld, int R, int C, vo
  * Streaming TCN: a TemporalBlock (reference models/temporal_convolutional_model.py:21-56) run on c new frames of S streams,
  * its causal taps read from rings of past frames.
  *
- * A ring is [S][R][C] fp32, channels-last, R a power of two.  All streams advance together: the host keeps the write
- * position `head` in [0, R) and passes it in; the device keeps no counters.  Row (s, i), i < c, is the frame at slot
- * (head + i) & (R - 1).  An all-zero ring is a stream with no past: exactly the reference's left zero padding.
+ * A ring is [S][R][C] fp32, channels-last, R a power of two.  The device keeps no counters: the host says where the
+ * rows of a launch sit, in one of two ways.  An all-zero ring is a stream with no past: exactly the reference's left zero
+ * padding.
+ *
+ * Lockstep (cer_tcn_stream_conv, cer_tcn_stream_append): all streams advance together: the host keeps the write
+ * position `head` in [0, R) and passes it in.  Row (s, i), i < c, is the frame at slot (head + i) & (R - 1).
  *
  * cer_tcn_stream_conv, for every row (s, i) and output channel o:
  *     z   = bias[o] + sum_{j < k, ci < Cin} w[o][j][ci] * ring[s][(head + i - (k - 1 - j) * dil) & (R - 1)][ci]
@@ -644,6 +647,25 @@ int cer_copy_cols(const float *x, int x_ld, float *y, int y_ld, int R, int C, vo
  *
  * Invalid descriptors (null pointers, R not a power of two, head outside [0, R), c too large for R) return
  * CER_ERR_INVALID_ARG before any launch.
+ *
+ * Row table (cer_tcn_stream_conv_rows, cer_tcn_stream_append_rows): streams advance independently.  The M rows of a
+ * launch are named by two int32 arrays of length M in device memory: row_stream[m] is the stream of row m and row_pos[m]
+ * that frame's position in its own stream, unwrapped, modulo 2^30.  cer_tcn_stream_conv_rows is cer_tcn_stream_conv with
+ * s = row_stream[m] and with row_pos[m] in place of head + i, res_head + i and out_head + i alike: tap j reads slot
+ * (row_pos[m] - (k - 1 - j) * dil) & (R - 1), the residual and the written slot are row_pos[m] & (res_R - 1) and
+ * row_pos[m] & (out_R - 1), and out_dense row m is row m.  Each launch masks row_pos with its own ring lengths, so one
+ * table serves every level of a net and there are no per-ring heads.  cer_tcn_stream_append_rows:
+ * ring[row_stream[m]][row_pos[m] & (R - 1)][:] = rows[m][:].
+ *   A stream's rows in one launch must be consecutive positions and must not exceed max_count.  max_count is the largest
+ *   number of rows any one stream has in the table; the host passes it because the entry point cannot read the table.
+ *   More rows of a stream than R - (k - 1) * dil would overwrite history that the launch still reads.
+ *   The sums, their order and the reduction trees are those of the lockstep entry points: a row's result is the same bits
+ *   through either.
+ *   The table's contents are never trusted with an address: row_stream[m] is clamped into [0, S) and every slot is masked
+ *   by its ring length, so a wrong table gives wrong numbers and never an access outside a ring.
+ *   Refused with CER_ERR_INVALID_ARG before any launch: a null table or pointer; M < 1; R, out_R or res_R not a power of
+ *   two or above 2^30; (k - 1) * dil + max_count > R; max_count > out_R or res_R; the residual-width and weight-alignment
+ *   rules of cer_tcn_stream_conv; ceil(M / 8) > 65535.
  * ---------------------------------------------------------------------- */
 typedef struct cer_tcn_stream_desc {
     int32_t S, c;              /* streams, new frames per stream */
@@ -658,6 +680,21 @@ int cer_tcn_stream_conv(const cer_tcn_stream_desc *d, const float *ring, const f
                         const float *res_ring, const float *res_w, const float *res_bias, float *out_ring, float *out_dense,
                         void *stream);
 int cer_tcn_stream_append(const float *rows, float *ring, int S, int c, int C, int R, int head, void *stream);
+
+typedef struct cer_tcn_stream_rows_desc {
+    int32_t S, M, max_count;   /* streams, rows in the table, the largest number of rows of one stream */
+    int32_t Cin, Cout, k, dil; /* the conv */
+    int32_t R;                 /* the ring the taps read */
+    int32_t res_C, res_R;      /* the residual ring (read when res_ring != NULL) */
+    int32_t out_R;             /* the ring written (when out_ring != NULL) */
+    float slope;
+} cer_tcn_stream_rows_desc;
+
+int cer_tcn_stream_conv_rows(const cer_tcn_stream_rows_desc *d, const int32_t *row_stream, const int32_t *row_pos,
+                             const float *ring, const float *w, const float *bias, const float *res_ring, const float *res_w,
+                             const float *res_bias, float *out_ring, float *out_dense, void *stream);
+int cer_tcn_stream_append_rows(const float *rows, float *ring, const int32_t *row_stream, const int32_t *row_pos, int S, int M,
+                               int max_count, int C, int R, void *stream);
 
 #ifdef __cplusplus
 }

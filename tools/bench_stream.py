@@ -6,7 +6,8 @@ offline model offers for a live stream: ``LFAN.forward`` over the last 121 frame
 
 Both run the same weights on pre-computed embeddings (the video modality enters as its 512-d embedding under the reference's
 ``cnn_res50`` key, same TCN as ``video``), so neither side runs an encoder.  Settings: S in {1, 32} streams, c in {1, 32} new
-frames per push.  Each figure is the median over ``rounds * reps`` calls of the time between two HIP events around ONE call,
+frames per push, and one ragged setting: S = 32 of which 5 streams bring one frame (``push_features_ragged``, one launch set)
+against the same 5 frames as 5 single-stream pushes, one ``LFANStream(model, 1)`` each.  Each figure is the median over ``rounds * reps`` calls of the time between two HIP events around ONE call,
 after warm-up, the two methods alternating round by round in the same process; the host-clock median (call + synchronise) is
 kept next to it.  Before timing, the streamed logits of the window's last frame are compared with the offline forward's.
 Launches are counted as C-ABI calls of one push / one forward (each is one kernel launch); weight bytes from the shapes.
@@ -85,7 +86,8 @@ def main():
     model = build_model(FIELD)
     dims = {m: model.embedding_dim[m] for m in MODS}
     g = torch.Generator(device="cuda").manual_seed(1)
-    result = {"modalities": MODS, "receptive_field": FIELD, "reps": a.reps, "rounds": a.rounds, "stream": {}, "offline": {}}
+    result = {"modalities": MODS, "receptive_field": FIELD, "reps": a.reps, "rounds": a.rounds, "stream": {}, "offline": {},
+              "ragged": {}}
 
     with torch.no_grad():
         # the two methods agree on the newest frame of a 121-frame window
@@ -102,6 +104,15 @@ def main():
                 stream = LFANStream(model, s, max_new=32)
                 feats = {m: torch.randn(s, c, d, device="cuda", generator=g) for m, d in dims.items()}
                 cases[f"stream_S{s}_c{c}"] = (lambda stream=stream, feats=feats: stream.push_features(feats))
+        # ragged: 5 of 32 streams have a new frame
+        some = [3, 7, 12, 20, 31]
+        counts = [1 if i in some else 0 for i in range(32)]
+        wide = LFANStream(model, 32, max_new=32)
+        rows = {m: torch.randn(len(some), d, device="cuda", generator=g) for m, d in dims.items()}
+        singles = [LFANStream(model, 1, max_new=32) for _ in some]
+        ones = [{m: v[i:i + 1].unsqueeze(1).contiguous() for m, v in rows.items()} for i in range(len(some))]
+        cases["ragged_S32_5x1"] = (lambda: wide.push_features_ragged(rows, counts))
+        cases["ragged_five_single_pushes"] = (lambda: [st.push_features(f) for st, f in zip(singles, ones)])
         samples = {name: ([], []) for name in cases}
         for fn in cases.values():
             for _ in range(a.warmup):
@@ -117,7 +128,10 @@ def main():
             q = statistics.quantiles(ev, n=10)
             entry = {"event_ms_median": round(statistics.median(ev), 4), "event_ms_p10": round(q[0], 4),
                      "event_ms_p90": round(q[-1], 4), "host_ms_median": round(statistics.median(host), 4), "launches": launches}
-            if name.startswith("stream"):
+            if name.startswith("ragged"):
+                entry["tcn_weight_bytes_read"] = tcn_bytes
+                result["ragged"][name[len("ragged_"):]] = entry
+            elif name.startswith("stream"):
                 entry["tcn_weight_bytes_read"] = tcn_bytes
                 result["stream"][name[len("stream_"):]] = entry
             else:
@@ -129,6 +143,8 @@ def main():
     one, off = result["stream"]["S1_c1"], result["offline"]["S1"]
     result["offline_over_stream_S1_c1"] = round(off["event_ms_median"] / one["event_ms_median"], 2)
     result["stream_no_slower_than_offline_S1_c1"] = one["event_ms_median"] <= off["event_ms_median"]
+    rag, five = result["ragged"]["S32_5x1"], result["ragged"]["five_single_pushes"]
+    result["five_single_pushes_over_ragged"] = round(five["event_ms_median"] / rag["event_ms_median"], 2)
     line = json.dumps(result)
     print(line)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
