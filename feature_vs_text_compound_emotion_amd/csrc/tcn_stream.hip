@@ -22,7 +22,11 @@
 // position row_pos[m] (unwrapped, modulo 2^30), read from device memory; every ring of a launch masks the same position with
 // its own R - 1, so one table serves all levels of a net and streams advance independently.  The table is data the host
 // code cannot see at launch: the stream index is clamped into [0, S) and every slot is masked, so any content stays inside the
-// rings.  Only ts_rows' filling and the epilogue's addresses differ; ts_dot / ts_fold do not know which way a row was found.
+// rings.  The two differ in a `Where` functor (row m -> stream and positions) and in nothing else: one kernel template and one
+// host path, ts_launch<Where>, with every shared check, the ts_args and the VEC / RES_VEC dispatch.  An entry point keeps what
+// is its own (lockstep: the S * c product and the heads' ranges; row table: the table pointers) and hands ts_launch its name.
+// The append kernels stay two (the lockstep one indexes rows in size_t, a functor over int rows would narrow it) behind one
+// set of host checks.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -181,14 +185,8 @@ __device__ __forceinline__ void ts_block(const ts_args &p, const Where &where, f
     if (p.out_dense) p.out_dense[(size_t)m * p.Cout + co] = v;
 }
 
-template <bool VEC, bool RES_VEC>
-__global__ __launch_bounds__(TS_THREADS) void tcn_stream_conv_kernel(ts_args p, ts_lockstep where) {
-    __shared__ float lds[TS_WAVES * TS_CO * TS_ROWS];
-    ts_block<VEC, RES_VEC>(p, where, lds);
-}
-
-template <bool VEC, bool RES_VEC>
-__global__ __launch_bounds__(TS_THREADS) void tcn_stream_conv_rows_kernel(ts_args p, ts_table where) {
+template <bool VEC, bool RES_VEC, class Where>
+__global__ __launch_bounds__(TS_THREADS) void tcn_stream_conv_kernel(ts_args p, Where where) {
     __shared__ float lds[TS_WAVES * TS_CO * TS_ROWS];
     ts_block<VEC, RES_VEC>(p, where, lds);
 }
@@ -215,128 +213,97 @@ __global__ void tcn_stream_append_rows_kernel(const float *__restrict__ rows, fl
     ring[(s * R + (size_t)(row_pos[m] & (R - 1))) * C + ch] = rows[idx];
 }
 
-static bool ts_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-static bool ts_ring_len(int v) { return ts_pow2(v) && v <= (1 << 30); }   // row positions are kept modulo 2^30
+// A power of two; 2^30 is the largest an int holds, and row positions are kept modulo 2^30.
+static bool ts_ring_len(int v) { return v > 0 && (v & (v - 1)) == 0; }
 static bool ts_al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+
+#define ST ((hipStream_t)stream)
+#define TS_REFUSE(...) return cer_set_error(CER_ERR_INVALID_ARG, __VA_ARGS__)
+
+// The one validated launch under both conv entries.  `d`: the dimensions in the row-table descriptor's terms (lockstep: M =
+// S * c, max_count = c); `p`: the eight pointers, the rest is filled in here; `entry` names the caller in every refusal.
+template <class Where>
+static int ts_launch(const char *entry, const cer_tcn_stream_rows_desc &d, ts_args p, const Where &where, void *stream) {
+    const long long hist = (long long)(d.k - 1) * d.dil, ytiles = ((long long)d.M + TS_ROWS - 1) / TS_ROWS;
+    if (!p.ring || !p.w || !p.bias || (!p.out_ring && !p.out_dense)) TS_REFUSE("%s: null pointer", entry);
+    if ((p.res_w && (!p.res_ring || !p.res_bias)) || (!p.res_w && p.res_bias))
+        TS_REFUSE("%s: res_w and res_bias come together, with res_ring", entry);
+    if (d.S < 1 || d.M < 1 || d.max_count < 1 || d.Cin < 1 || d.Cout < 1 || d.k < 1 || d.dil < 1)
+        TS_REFUSE("%s: streams, rows, new frames of a stream, Cin, Cout, k and dil must be >= 1", entry);
+    if (!ts_ring_len(d.R) || (p.out_ring && !ts_ring_len(d.out_R)) || (p.res_ring && !ts_ring_len(d.res_R)))
+        TS_REFUSE("%s: ring length R = %d (out %d, res %d) is not a power of two up to 2^30", entry, d.R, d.out_R, d.res_R);
+    if (hist + d.max_count > d.R || (p.out_ring && d.max_count > d.out_R) || (p.res_ring && d.max_count > d.res_R))
+        TS_REFUSE("%s: %d new frames of a stream plus (k - 1) * dil = %lld of history exceed R = %d (out %d, res %d)", entry,
+                  d.max_count, hist, d.R, d.out_R, d.res_R);
+    if (p.res_ring && (p.res_w ? d.res_C < 1 : d.res_C != d.Cout))
+        TS_REFUSE("%s: residual ring of %d channels for Cout = %d without a projection", entry, d.res_C, d.Cout);
+    if (!ts_al16(p.w) || (p.res_w && !ts_al16(p.res_w))) TS_REFUSE("%s: packed weights must be 16-byte aligned", entry);
+    if (ytiles > 65535) TS_REFUSE("%s: %d rows exceed the grid", entry, d.M);
+    p.M = d.M; p.Cin = d.Cin; p.Cout = d.Cout; p.k = d.k; p.dil = d.dil; p.R = d.R;
+    p.res_C = p.res_ring ? d.res_C : 1; p.res_R = p.res_ring ? d.res_R : 1; p.out_R = p.out_ring ? d.out_R : 1;
+    p.slope = d.slope;
+    const bool vec = d.Cin % 4 == 0 && ts_al16(p.ring), rvec = p.res_w && d.res_C % 4 == 0 && ts_al16(p.res_ring);
+    const dim3 grid((d.Cout + TS_CO - 1) / TS_CO, (unsigned)ytiles), block(TS_THREADS);
+    if (vec && rvec) CER_LAUNCH((tcn_stream_conv_kernel<true, true, Where>), grid, block, 0, ST, p, where);
+    else if (vec) CER_LAUNCH((tcn_stream_conv_kernel<true, false, Where>), grid, block, 0, ST, p, where);
+    else if (rvec) CER_LAUNCH((tcn_stream_conv_kernel<false, true, Where>), grid, block, 0, ST, p, where);
+    else CER_LAUNCH((tcn_stream_conv_kernel<false, false, Where>), grid, block, 0, ST, p, where);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+// What both append entries refuse: `count` new frames of a stream into a ring of R slots, n elements in all.
+static int ts_append_check(const char *entry, bool null, int S, int M, int count, int C, int R, size_t n) {
+    if (null) TS_REFUSE("%s: null pointer", entry);
+    if (S < 1 || M < 1 || count < 1 || C < 1) TS_REFUSE("%s: streams, rows, new frames of a stream and C must be >= 1", entry);
+    if (!ts_ring_len(R)) TS_REFUSE("%s: ring length R = %d is not a power of two up to 2^30", entry, R);
+    if (count > R) TS_REFUSE("%s: %d new frames of a stream exceed R = %d", entry, count, R);
+    if (n > (size_t)0x7fffffff * 256) TS_REFUSE("%s: too many elements", entry);
+    return CER_OK;
+}
 
 }  // namespace cer
 
 using namespace cer;
 
-#define ST ((hipStream_t)stream)
-
 extern "C" int cer_tcn_stream_conv(const cer_tcn_stream_desc *d, const float *ring, const float *w, const float *bias,
                                    const float *res_ring, const float *res_w, const float *res_bias, float *out_ring,
                                    float *out_dense, void *stream) {
-    if (!d || !ring || !w || !bias || (!out_ring && !out_dense))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv: null pointer");
-    if ((res_w && (!res_ring || !res_bias)) || (!res_w && res_bias))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv: res_w and res_bias come together, with res_ring");
-    if (d->S < 1 || d->c < 1 || d->Cin < 1 || d->Cout < 1 || d->k < 1 || d->dil < 1)
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv: S, c, Cin, Cout, k and dil must be >= 1");
-    if (!ts_pow2(d->R) || (out_ring && !ts_pow2(d->out_R)) || (res_ring && !ts_pow2(d->res_R)))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv: ring length R = %d (out %d, res %d) is not a power of two",
-                             d->R, d->out_R, d->res_R);
+    if (!d) TS_REFUSE("tcn_stream_conv: null pointer");
+    const long long M = (long long)d->S * d->c;   // bounded before it is narrowed; S < 1 or c < 1 is refused in ts_launch
+    if (M > 65535LL * TS_ROWS) TS_REFUSE("tcn_stream_conv: S * c = %lld rows exceed the grid", M);
     if (d->head < 0 || d->head >= d->R || (out_ring && (d->out_head < 0 || d->out_head >= d->out_R)) ||
         (res_ring && (d->res_head < 0 || d->res_head >= d->res_R)))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv: head outside [0, R)");
-    if ((long long)(d->k - 1) * d->dil + d->c > d->R || (out_ring && d->c > d->out_R) || (res_ring && d->c > d->res_R))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv: c = %d new frames plus (k - 1) * dil = %lld of history exceed "
-                             "R = %d", d->c, (long long)(d->k - 1) * d->dil, d->R);
-    if (res_ring && (res_w ? d->res_C < 1 : d->res_C != d->Cout))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv: residual ring of %d channels for Cout = %d without a "
-                             "projection", d->res_C, d->Cout);
-    if (!ts_al16(w) || (res_w && !ts_al16(res_w)))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv: packed weights must be 16-byte aligned");
-    const long long M = (long long)d->S * d->c, ytiles = (M + TS_ROWS - 1) / TS_ROWS;
-    if (ytiles > 65535) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv: S * c = %lld rows exceed the grid", M);
-    ts_args p;
-    p.ring = ring; p.w = w; p.bias = bias;
-    p.res_ring = res_ring; p.res_w = res_w; p.res_bias = res_bias;
-    p.out_ring = out_ring; p.out_dense = out_dense;
-    p.M = (int)M; p.Cin = d->Cin; p.Cout = d->Cout; p.k = d->k; p.dil = d->dil; p.R = d->R;
-    p.res_C = res_ring ? d->res_C : 1; p.res_R = res_ring ? d->res_R : 1; p.out_R = out_ring ? d->out_R : 1;
-    p.slope = d->slope;
+        TS_REFUSE("tcn_stream_conv: head outside [0, R)");
+    const cer_tcn_stream_rows_desc dims = {d->S, (int)M, d->c, d->Cin, d->Cout, d->k, d->dil, d->R, d->res_C, d->res_R,
+                                           d->out_R, d->slope};
     const ts_lockstep where = {d->c, d->head, res_ring ? d->res_head : 0, out_ring ? d->out_head : 0};
-    const bool vec = d->Cin % 4 == 0 && ts_al16(ring), rvec = res_w && d->res_C % 4 == 0 && ts_al16(res_ring);
-    const dim3 grid((d->Cout + TS_CO - 1) / TS_CO, (unsigned)ytiles), block(TS_THREADS);
-    if (vec && rvec) CER_LAUNCH((tcn_stream_conv_kernel<true, true>), grid, block, 0, ST, p, where);
-    else if (vec) CER_LAUNCH((tcn_stream_conv_kernel<true, false>), grid, block, 0, ST, p, where);
-    else if (rvec) CER_LAUNCH((tcn_stream_conv_kernel<false, true>), grid, block, 0, ST, p, where);
-    else CER_LAUNCH((tcn_stream_conv_kernel<false, false>), grid, block, 0, ST, p, where);
-    CER_HIP_CHECK(hipGetLastError());
-    return CER_OK;
-}
-
-extern "C" int cer_tcn_stream_append(const float *rows, float *ring, int S, int c, int C, int R, int head, void *stream) {
-    if (!rows || !ring) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append: null pointer");
-    if (S < 1 || c < 1 || C < 1) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append: S, c and C must be >= 1");
-    if (!ts_pow2(R)) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append: ring length R = %d is not a power of two", R);
-    if (head < 0 || head >= R) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append: head %d outside [0, %d)", head, R);
-    if (c > R) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append: c = %d new frames exceed R = %d", c, R);
-    const size_t n = (size_t)S * c * C;
-    if (n > (size_t)0x7fffffff * 256) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append: too many elements");
-    CER_LAUNCH(tcn_stream_append_kernel, dim3(cer_blocks(n, 256)), dim3(256), 0, ST, rows, ring, c, C, R, head, n);
-    CER_HIP_CHECK(hipGetLastError());
-    return CER_OK;
+    return ts_launch("tcn_stream_conv", dims, {ring, w, bias, res_ring, res_w, res_bias, out_ring, out_dense}, where, stream);
 }
 
 extern "C" int cer_tcn_stream_conv_rows(const cer_tcn_stream_rows_desc *d, const int32_t *row_stream, const int32_t *row_pos,
                                         const float *ring, const float *w, const float *bias, const float *res_ring,
                                         const float *res_w, const float *res_bias, float *out_ring, float *out_dense,
                                         void *stream) {
-    if (!d || !row_stream || !row_pos || !ring || !w || !bias || (!out_ring && !out_dense))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: null pointer");
-    if ((res_w && (!res_ring || !res_bias)) || (!res_w && res_bias))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: res_w and res_bias come together, with res_ring");
-    if (d->S < 1 || d->M < 1 || d->max_count < 1 || d->Cin < 1 || d->Cout < 1 || d->k < 1 || d->dil < 1)
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: S, M, max_count, Cin, Cout, k and dil must be >= 1");
-    if (!ts_ring_len(d->R) || (out_ring && !ts_ring_len(d->out_R)) || (res_ring && !ts_ring_len(d->res_R)))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: ring length R = %d (out %d, res %d) is not a power of "
-                             "two up to 2^30", d->R, d->out_R, d->res_R);
-    if ((long long)(d->k - 1) * d->dil + d->max_count > d->R || (out_ring && d->max_count > d->out_R) ||
-        (res_ring && d->max_count > d->res_R))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: max_count = %d new frames of a stream plus "
-                             "(k - 1) * dil = %lld of history exceed R = %d (out %d, res %d)", d->max_count,
-                             (long long)(d->k - 1) * d->dil, d->R, d->out_R, d->res_R);
-    if (res_ring && (res_w ? d->res_C < 1 : d->res_C != d->Cout))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: residual ring of %d channels for Cout = %d without a "
-                             "projection", d->res_C, d->Cout);
-    if (!ts_al16(w) || (res_w && !ts_al16(res_w)))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: packed weights must be 16-byte aligned");
-    const long long ytiles = ((long long)d->M + TS_ROWS - 1) / TS_ROWS;
-    if (ytiles > 65535) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_conv_rows: M = %d rows exceed the grid", d->M);
-    ts_args p;
-    p.ring = ring; p.w = w; p.bias = bias;
-    p.res_ring = res_ring; p.res_w = res_w; p.res_bias = res_bias;
-    p.out_ring = out_ring; p.out_dense = out_dense;
-    p.M = d->M; p.Cin = d->Cin; p.Cout = d->Cout; p.k = d->k; p.dil = d->dil; p.R = d->R;
-    p.res_C = res_ring ? d->res_C : 1; p.res_R = res_ring ? d->res_R : 1; p.out_R = out_ring ? d->out_R : 1;
-    p.slope = d->slope;
+    if (!d || !row_stream || !row_pos) TS_REFUSE("tcn_stream_conv_rows: null pointer");
     const ts_table where = {row_stream, row_pos, d->S};
-    const bool vec = d->Cin % 4 == 0 && ts_al16(ring), rvec = res_w && d->res_C % 4 == 0 && ts_al16(res_ring);
-    const dim3 grid((d->Cout + TS_CO - 1) / TS_CO, (unsigned)ytiles), block(TS_THREADS);
-    if (vec && rvec) CER_LAUNCH((tcn_stream_conv_rows_kernel<true, true>), grid, block, 0, ST, p, where);
-    else if (vec) CER_LAUNCH((tcn_stream_conv_rows_kernel<true, false>), grid, block, 0, ST, p, where);
-    else if (rvec) CER_LAUNCH((tcn_stream_conv_rows_kernel<false, true>), grid, block, 0, ST, p, where);
-    else CER_LAUNCH((tcn_stream_conv_rows_kernel<false, false>), grid, block, 0, ST, p, where);
+    return ts_launch("tcn_stream_conv_rows", *d, {ring, w, bias, res_ring, res_w, res_bias, out_ring, out_dense}, where, stream);
+}
+
+extern "C" int cer_tcn_stream_append(const float *rows, float *ring, int S, int c, int C, int R, int head, void *stream) {
+    const size_t n = (size_t)S * c * C;
+    if (int rc = ts_append_check("tcn_stream_append", !rows || !ring, S, c, c, C, R, n)) return rc;
+    if (head < 0 || head >= R) TS_REFUSE("tcn_stream_append: head %d outside [0, %d)", head, R);
+    CER_LAUNCH(tcn_stream_append_kernel, dim3(cer_blocks(n, 256)), dim3(256), 0, ST, rows, ring, c, C, R, head, n);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }
 
 extern "C" int cer_tcn_stream_append_rows(const float *rows, float *ring, const int32_t *row_stream, const int32_t *row_pos,
                                           int S, int M, int max_count, int C, int R, void *stream) {
-    if (!rows || !ring || !row_stream || !row_pos)
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append_rows: null pointer");
-    if (S < 1 || M < 1 || max_count < 1 || C < 1)
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append_rows: S, M, max_count and C must be >= 1");
-    if (!ts_ring_len(R))
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append_rows: ring length R = %d is not a power of two up to 2^30", R);
-    if (max_count > R)
-        return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append_rows: max_count = %d new frames of a stream exceed R = %d",
-                             max_count, R);
     const size_t n = (size_t)M * C;
-    if (n > (size_t)0x7fffffff * 256) return cer_set_error(CER_ERR_INVALID_ARG, "tcn_stream_append_rows: too many elements");
+    if (int rc = ts_append_check("tcn_stream_append_rows", !rows || !ring || !row_stream || !row_pos, S, M, max_count, C, R, n))
+        return rc;
     CER_LAUNCH(tcn_stream_append_rows_kernel, dim3(cer_blocks(n, 256)), dim3(256), 0, ST, rows, ring, row_stream, row_pos, S, C, R,
                n);
     CER_HIP_CHECK(hipGetLastError());

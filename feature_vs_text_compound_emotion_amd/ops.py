@@ -1616,9 +1616,10 @@ STREAM_TRACE = None   # a list collects (entry point, weight bytes read) per lau
 def _ring(t, name, channels=None):
     """A ring [S, R, C]: contiguous float32 on the GPU.  Returns (S, R, C)."""
     _dev_f32(t, name)
-    if t.dim() != 3 or (channels is not None and t.shape[2] != channels):
-        raise ValueError(f"{name}: expected a ring [S, R, {channels if channels is not None else 'C'}], got {tuple(t.shape)}")
-    return tuple(t.shape)
+    shape = tuple(t.shape)
+    if len(shape) != 3 or (channels is not None and shape[2] != channels):
+        raise ValueError(f"{name}: expected a ring [S, R, {channels if channels is not None else 'C'}], got {shape}")
+    return shape
 
 
 def pack_tcn_stream_weight(w_oik):
@@ -1645,6 +1646,50 @@ def tcn_stream_append(rows, ring, head):
         STREAM_TRACE.append(("append", 0))
 
 
+def _addr(t):
+    """``ptr`` as a plain int (the argtypes make the void *): a streamed push is bound by the host issuing its launches."""
+    return None if t is None else t.data_ptr()
+
+
+def _stream_conv(name, d, table, s, cin, rows, ring, w_packed, bias, res_ring, res_w, res_bias, out_ring, out_dense):
+    """What ``tcn_stream_conv`` and ``tcn_stream_conv_rows`` share, which is all that does not depend on how a row finds its
+    stream and position: the tensor checks, Cout and the residual and output rings of the entry's descriptor ``d``, the weight
+    bytes and the one launch.  ``table``: the pointers that follow ``d`` in the call; ``s``, ``cin``: of the checked ``ring``;
+    ``rows``: how many ``out_dense`` must have."""
+    _dev_f32(bias, "bias")
+    d.Cout = cout = bias.shape[0]
+    cout4 = (cout + 3) & ~3   # the packed filters' channel counts: rounded up to a multiple of 4
+    _dev_f32(w_packed, "w_packed", shape=(cout4, d.k, (cin + 3) & ~3))
+    wbytes = w_packed.numel() * 4
+    if res_ring is not None:
+        rs, d.res_R, d.res_C = _ring(res_ring, "res_ring")
+        if rs != s:
+            raise ValueError(f"res_ring: expected {s} streams, got {rs}")
+        if res_w is not None:
+            _dev_f32(res_w, "res_w", shape=(cout4, 1, (d.res_C + 3) & ~3))
+            _dev_f32(res_bias, "res_bias", shape=(cout,))
+            if res_bias is None:
+                raise ValueError("res_bias: the projection needs its bias")
+            wbytes += res_w.numel() * 4
+        elif d.res_C != cout:
+            raise ValueError(f"res_ring: {d.res_C} channels for Cout = {cout} and no projection")
+    elif res_w is not None or res_bias is not None:
+        raise ValueError("res_w / res_bias without res_ring")
+    if out_ring is None and out_dense is None:
+        raise ValueError(f"tcn_stream_{name}: no output")
+    if out_ring is not None:
+        os_, d.out_R, _ = _ring(out_ring, "out_ring", cout)
+        if os_ != s:
+            raise ValueError(f"out_ring: expected {s} streams, got {os_}")
+    _dev_f32(out_dense, "out_dense", shape=(rows, cout))
+    entry = "cer_tcn_stream_" + name
+    check(getattr(_lib.load(), entry)(ctypes.byref(d), *table, ring.data_ptr(), w_packed.data_ptr(), bias.data_ptr(),
+                                      _addr(res_ring), _addr(res_w), _addr(res_bias), _addr(out_ring), _addr(out_dense),
+                                      current_stream()), entry)
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append((name, wbytes))
+
+
 def tcn_stream_conv(ring, head, c, w_packed, bias, k, dil, *, res_ring=None, res_head=0, res_w=None, res_bias=None,
                     out_ring=None, out_head=0, out_dense=None, slope=LEAKY_SLOPE):
     """One conv of a streamed TemporalBlock over the ``c`` newest frames of ``ring`` [S, R, Cin] (written at ``head``):
@@ -1656,40 +1701,9 @@ def tcn_stream_conv(ring, head, c, w_packed, bias, k, dil, *, res_ring=None, res
     written to the c slots of ``out_ring`` [S, R', Cout] at ``out_head`` and / or to ``out_dense`` [S * c, Cout].
     ``w_packed``: ``pack_tcn_stream_weight`` of the [Cout, Cin, k] filter."""
     s, r, cin = _ring(ring, "ring")
-    _dev_f32(bias, "bias")
-    cout = bias.shape[0]
-    c4 = lambda n: -(-n // 4) * 4   # noqa: E731
-    _dev_f32(w_packed, "w_packed", shape=(c4(cout), k, c4(cin)))
-    d = _lib.TcnStreamDesc(S=s, c=int(c), Cin=cin, Cout=cout, k=int(k), dil=int(dil), R=r, head=int(head), slope=float(slope))
-    wbytes = w_packed.numel() * 4
-    if res_ring is not None:
-        rs, d.res_R, d.res_C = _ring(res_ring, "res_ring")
-        d.res_head = int(res_head)
-        if rs != s:
-            raise ValueError(f"res_ring: expected {s} streams, got {rs}")
-        if res_w is not None:
-            _dev_f32(res_w, "res_w", shape=(c4(cout), 1, c4(d.res_C)))
-            _dev_f32(res_bias, "res_bias", shape=(cout,))
-            if res_bias is None:
-                raise ValueError("res_bias: the projection needs its bias")
-            wbytes += res_w.numel() * 4
-        elif d.res_C != cout:
-            raise ValueError(f"res_ring: {d.res_C} channels for Cout = {cout} and no projection")
-    elif res_w is not None or res_bias is not None:
-        raise ValueError("res_w / res_bias without res_ring")
-    if out_ring is None and out_dense is None:
-        raise ValueError("tcn_stream_conv: no output")
-    if out_ring is not None:
-        os_, d.out_R, _ = _ring(out_ring, "out_ring", cout)
-        d.out_head = int(out_head)
-        if os_ != s:
-            raise ValueError(f"out_ring: expected {s} streams, got {os_}")
-    _dev_f32(out_dense, "out_dense", shape=(s * int(c), cout))
-    check(_lib.load().cer_tcn_stream_conv(ctypes.byref(d), ptr(ring), ptr(w_packed), ptr(bias), ptr(res_ring), ptr(res_w),
-                                          ptr(res_bias), ptr(out_ring), ptr(out_dense), current_stream()),
-          "cer_tcn_stream_conv")
-    if STREAM_TRACE is not None:
-        STREAM_TRACE.append(("conv", wbytes))
+    d = _lib.TcnStreamDesc(S=s, c=int(c), Cin=cin, k=int(k), dil=int(dil), R=r, head=int(head), res_head=int(res_head),
+                           out_head=int(out_head), slope=float(slope))
+    _stream_conv("conv", d, (), s, cin, s * int(c), ring, w_packed, bias, res_ring, res_w, res_bias, out_ring, out_dense)
 
 
 ROW_POS_MOD = 1 << 30   # row positions travel modulo 2^30: every ring length divides it, so each launch's mask sees the same slot
@@ -1746,36 +1760,6 @@ def tcn_stream_conv_rows(ring, row_stream, row_pos, max_count, w_packed, bias, k
     ``max_count`` of them.  The same bits as the lockstep launch gives the same frames."""
     s, r, cin = _ring(ring, "ring")
     m = _row_table(row_stream, row_pos, ring)
-    _dev_f32(bias, "bias")
-    cout = bias.shape[0]
-    c4 = lambda n: -(-n // 4) * 4   # noqa: E731
-    _dev_f32(w_packed, "w_packed", shape=(c4(cout), k, c4(cin)))
-    d = _lib.TcnStreamRowsDesc(S=s, M=m, max_count=int(max_count), Cin=cin, Cout=cout, k=int(k), dil=int(dil), R=r,
-                               slope=float(slope))
-    wbytes = w_packed.numel() * 4
-    if res_ring is not None:
-        rs, d.res_R, d.res_C = _ring(res_ring, "res_ring")
-        if rs != s:
-            raise ValueError(f"res_ring: expected {s} streams, got {rs}")
-        if res_w is not None:
-            _dev_f32(res_w, "res_w", shape=(c4(cout), 1, c4(d.res_C)))
-            _dev_f32(res_bias, "res_bias", shape=(cout,))
-            if res_bias is None:
-                raise ValueError("res_bias: the projection needs its bias")
-            wbytes += res_w.numel() * 4
-        elif d.res_C != cout:
-            raise ValueError(f"res_ring: {d.res_C} channels for Cout = {cout} and no projection")
-    elif res_w is not None or res_bias is not None:
-        raise ValueError("res_w / res_bias without res_ring")
-    if out_ring is None and out_dense is None:
-        raise ValueError("tcn_stream_conv_rows: no output")
-    if out_ring is not None:
-        os_, d.out_R, _ = _ring(out_ring, "out_ring", cout)
-        if os_ != s:
-            raise ValueError(f"out_ring: expected {s} streams, got {os_}")
-    _dev_f32(out_dense, "out_dense", shape=(m, cout))
-    check(_lib.load().cer_tcn_stream_conv_rows(ctypes.byref(d), ptr(row_stream), ptr(row_pos), ptr(ring), ptr(w_packed), ptr(bias),
-                                               ptr(res_ring), ptr(res_w), ptr(res_bias), ptr(out_ring), ptr(out_dense),
-                                               current_stream()), "cer_tcn_stream_conv_rows")
-    if STREAM_TRACE is not None:
-        STREAM_TRACE.append(("conv_rows", wbytes))
+    d = _lib.TcnStreamRowsDesc(S=s, M=m, max_count=int(max_count), Cin=cin, k=int(k), dil=int(dil), R=r, slope=float(slope))
+    _stream_conv("conv_rows", d, (ptr(row_stream), ptr(row_pos)), s, cin, m, ring, w_packed, bias, res_ring, res_w, res_bias,
+                 out_ring, out_dense)

@@ -35,23 +35,52 @@ def ring_frames(k, dil, max_new):
     return r
 
 
+class _Lockstep(tuple):
+    """(pos, c, out_pos): where the rows of a push sit when all streams stand at frame count ``pos`` and bring ``c`` frames.
+    Every ring's head is ``pos & (R - 1)``; the ring a block leaves its output in stands at ``out_pos`` (``block_push``)."""
+
+    def append(self, x, ring):
+        ops.tcn_stream_append(x, ring, self[0] & (ring.shape[1] - 1))
+
+    def conv(self, ring, w, b, k, dil, slope, out_ring, out_dense=None, res_ring=None, res_w=None, res_bias=None):
+        pos, c, out_pos = self
+        if res_ring is None:   # a block's first conv writes the block's own hring, which stands at pos
+            out_pos = pos
+        ops.tcn_stream_conv(ring, pos & (ring.shape[1] - 1), c, w, b, k, dil, res_ring=res_ring,
+                            res_head=0 if res_ring is None else pos & (res_ring.shape[1] - 1), res_w=res_w, res_bias=res_bias,
+                            out_ring=out_ring, out_head=0 if out_ring is None else out_pos & (out_ring.shape[1] - 1),
+                            out_dense=out_dense, slope=slope)
+
+
+class _Rows(tuple):
+    """(row_stream, row_pos, max_count): where they sit when each row names its stream and position, the table of
+    ``ops.stream_row_table`` and the most rows any one stream has in it."""
+
+    def append(self, x, ring):
+        ops.tcn_stream_append_rows(x, ring, *self)
+
+    def conv(self, ring, w, b, k, dil, slope, out_ring, out_dense=None, res_ring=None, res_w=None, res_bias=None):
+        ops.tcn_stream_conv_rows(ring, *self, w, b, k, dil, res_ring=res_ring, res_w=res_w, res_bias=res_bias, out_ring=out_ring,
+                                 out_dense=out_dense, slope=slope)
+
+
+def _block(pack, xring, hring, place, out_ring, out_dense, slope):
+    """Phase A and phase B of one block over the rows ``place`` names, already written to ``xring``."""
+    k, dil = pack["k"], pack["dil"]
+    place.conv(xring, pack["w1"], pack["b1"], k, dil, slope, hring)
+    place.conv(hring, pack["w2"], pack["b2"], k, dil, slope, out_ring, out_dense, xring, pack["dsw"], pack["dsb"])
+
+
 def block_push(pack, xring, hring, pos, c, out_ring=None, out_pos=0, out_dense=None, slope=ops.LEAKY_SLOPE):
     """The two launches of one block over the ``c`` frames already written to ``xring`` at frame count ``pos``.
     ``pack``: dict(k, dil, w1, b1, w2, b2, dsw, dsb) with packed filters (``dsw`` None: identity residual)."""
-    head = pos & (xring.shape[1] - 1)
-    ops.tcn_stream_conv(xring, head, c, pack["w1"], pack["b1"], pack["k"], pack["dil"], out_ring=hring, out_head=head, slope=slope)
-    ops.tcn_stream_conv(hring, head, c, pack["w2"], pack["b2"], pack["k"], pack["dil"], res_ring=xring, res_head=head,
-                        res_w=pack["dsw"], res_bias=pack["dsb"], out_ring=out_ring,
-                        out_head=out_pos & (out_ring.shape[1] - 1) if out_ring is not None else 0, out_dense=out_dense, slope=slope)
+    _block(pack, xring, hring, _Lockstep((pos, c, out_pos)), out_ring, out_dense, slope)
 
 
 def block_push_rows(pack, xring, hring, row_stream, row_pos, max_count, out_ring=None, out_dense=None, slope=ops.LEAKY_SLOPE):
     """``block_push`` over the rows of a row table (``ops.stream_row_table``) already written to ``xring``: the same two
     launches, each stream at its own position."""
-    ops.tcn_stream_conv_rows(xring, row_stream, row_pos, max_count, pack["w1"], pack["b1"], pack["k"], pack["dil"], out_ring=hring,
-                             slope=slope)
-    ops.tcn_stream_conv_rows(hring, row_stream, row_pos, max_count, pack["w2"], pack["b2"], pack["k"], pack["dil"], res_ring=xring,
-                             res_w=pack["dsw"], res_bias=pack["dsb"], out_ring=out_ring, out_dense=out_dense, slope=slope)
+    _block(pack, xring, hring, _Rows((row_stream, row_pos, max_count)), out_ring, out_dense, slope)
 
 
 def _check_tensor(x, name):
@@ -146,27 +175,18 @@ class TCNStream:
         if self.net.training:
             raise RuntimeError("TCNStream: the net is in train mode (dropout); call .eval() first")
 
-    def _lockstep(self, x, dense):
-        """x [S, n, Cin], n <= max_new, all streams at one position: the dense launches."""
-        pos, n, last = self._pos[0], x.shape[1], len(self.xrings) - 1
-        ops.tcn_stream_append(x, self.xrings[0], pos & (self.ring_frames[0] - 1))
+    def _push(self, x, place, dense):
+        """x: the new frames, stream-major, the rows ``place`` names ([S, c, Cin] in lockstep, [M, Cin] for a table) -> dense
+        [M, Cout]: one append and two launches per block."""
+        last = len(self.xrings) - 1
+        place.append(x, self.xrings[0])
         for lvl, pack in enumerate(self._pack()):
-            if lvl < last:
-                block_push(pack, self.xrings[lvl], self.hrings[lvl], pos, n, out_ring=self.xrings[lvl + 1], out_pos=pos)
-            else:
-                block_push(pack, self.xrings[lvl], self.hrings[lvl], pos, n, out_dense=dense)
+            _block(pack, self.xrings[lvl], self.hrings[lvl], place, self.xrings[lvl + 1] if lvl < last else None,
+                   dense if lvl == last else None, ops.LEAKY_SLOPE)
 
-    def _ragged(self, x, counts, dense):
-        """x [M, Cin] packed stream-major, counts[s] <= max_new frames of stream s, M >= 1: one table upload, one append and
-        two launches per block, each stream at its own position."""
-        row_stream, row_pos = ops.stream_row_table(self._pos, counts, self.device)
-        most, last = max(counts), len(self.xrings) - 1
-        ops.tcn_stream_append_rows(x, self.xrings[0], row_stream, row_pos, most)
-        for lvl, pack in enumerate(self._pack()):
-            if lvl < last:
-                block_push_rows(pack, self.xrings[lvl], self.hrings[lvl], row_stream, row_pos, most, out_ring=self.xrings[lvl + 1])
-            else:
-                block_push_rows(pack, self.xrings[lvl], self.hrings[lvl], row_stream, row_pos, most, out_dense=dense)
+    def _table(self, counts):
+        """One table upload for a push in which stream s brings ``counts[s]`` frames, each stream at its own position."""
+        return _Rows(ops.stream_row_table(self._pos, counts, self.device) + (max(counts),))
 
     def _advance(self, counts):
         self._pos = [p + c for p, c in zip(self._pos, counts)]
@@ -188,9 +208,10 @@ class TCNStream:
             chunk = x if whole else x[:, c0:c0 + n].contiguous()
             dense = out if whole else torch.empty((self.streams, n, self.cout), device=self.device, dtype=torch.float32)
             if len(set(self._pos)) == 1:
-                self._lockstep(chunk, dense.view(self.streams * n, self.cout))
+                place = _Lockstep((self._pos[0], n, self._pos[0]))
             else:
-                self._ragged(chunk.view(self.streams * n, self.cin), [n] * self.streams, dense.view(self.streams * n, self.cout))
+                place, chunk = self._table([n] * self.streams), chunk.view(self.streams * n, self.cin)
+            self._push(chunk, place, dense.view(self.streams * n, self.cout))
             if not whole:
                 out[:, c0:c0 + n] = dense
             self._advance([n] * self.streams)
@@ -206,7 +227,7 @@ class TCNStream:
         _check_packed(x, "x", sum(counts), (self.cin,))
         out = torch.empty((x.shape[0], self.cout), device=self.device, dtype=torch.float32)
         if x.shape[0]:
-            self._ragged(x.contiguous(), counts, out)
+            self._push(x.contiguous(), self._table(counts), out)
             self._advance(counts)
         return out
 

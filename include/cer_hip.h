@@ -623,7 +623,8 @@ int cer_copy_cols(const float *x, int x_ld, float *y, int y_ld, int R, int C, vo
  *
  * A ring is [S][R][C] fp32, channels-last, R a power of two.  The device keeps no counters: the host says where the
  * rows of a launch sit, in one of two ways.  An all-zero ring is a stream with no past: exactly the reference's left zero
- * padding.
+ * padding.  The two entry families share one validation and launch path and one kernel body; they differ only in how a row
+ * finds its stream and position.
  *
  * Lockstep (cer_tcn_stream_conv, cer_tcn_stream_append): all streams advance together: the host keeps the write
  * position `head` in [0, R) and passes it in.  Row (s, i), i < c, is the frame at slot (head + i) & (R - 1).
@@ -646,7 +647,7 @@ int cer_copy_cols(const float *x, int x_ld, float *y, int y_ld, int R, int C, vo
  * cer_tcn_stream_append: ring[s][(head + i) & (R - 1)][:] = rows[s * c + i][:] -- the first block's input.
  *
  * Invalid descriptors (null pointers, R not a power of two, head outside [0, R), c too large for R) return
- * CER_ERR_INVALID_ARG before any launch.
+ * CER_ERR_INVALID_ARG before any launch, with a cer_last_error() text that begins with the refusing entry's name.
  *
  * Row table (cer_tcn_stream_conv_rows, cer_tcn_stream_append_rows): streams advance independently.  The M rows of a
  * launch are named by two int32 arrays of length M in device memory: row_stream[m] is the stream of row m and row_pos[m]
@@ -663,9 +664,10 @@ int cer_copy_cols(const float *x, int x_ld, float *y, int y_ld, int R, int C, vo
  *   through either.
  *   The table's contents are never trusted with an address: row_stream[m] is clamped into [0, S) and every slot is masked
  *   by its ring length, so a wrong table gives wrong numbers and never an access outside a ring.
- *   Refused with CER_ERR_INVALID_ARG before any launch: a null table or pointer; M < 1; R, out_R or res_R not a power of
- *   two or above 2^30; (k - 1) * dil + max_count > R; max_count > out_R or res_R; the residual-width and weight-alignment
- *   rules of cer_tcn_stream_conv; ceil(M / 8) > 65535.
+ *   Refused with CER_ERR_INVALID_ARG before any launch: a null table; and, by the checks shared with cer_tcn_stream_conv
+ *   (there with M = S * c and max_count = c): a null pointer; M < 1; R, out_R or res_R not a power of two (2^30 is the
+ *   largest an int32 holds); (k - 1) * dil + max_count > R; max_count > out_R or res_R; the residual-width and
+ *   weight-alignment rules; ceil(M / 8) > 65535.
  * ---------------------------------------------------------------------- */
 typedef struct cer_tcn_stream_desc {
     int32_t S, c;              /* streams, new frames per stream */

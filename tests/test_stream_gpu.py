@@ -57,11 +57,14 @@ class _Arena:
         return bool(torch.isnan(self.flat[keep]).all())
 
 
-@pytest.mark.parametrize("case", BLOCK_CASES, ids=[c.name for c in BLOCK_CASES])
-def test_block_streamed_equals_the_float64_whole_sequence_block_bit_for_bit(case):
+# every case through both entry families; the lockstep ids stay the bare case names
+@pytest.mark.parametrize("case,via", [pytest.param(c, via, id=c.name if via == "lockstep" else f"{c.name}-{via}")
+                                      for via in ("lockstep", "rows") for c in BLOCK_CASES])
+def test_block_streamed_equals_the_float64_whole_sequence_block_bit_for_bit(case, via):
     """Exact data (stream_ref; precondition asserted in test_stream_cpu.py): any reduction order is exact, so no tolerance.
     T >= 3 R frames, so every ring wraps at least twice.  The rings are slices of a NaN-filled allocation: the guards stay NaN,
-    and a push changes nothing but its c new slots."""
+    and a push changes nothing but its c new slots.  ``via``: the lockstep entry points, or the row-table ones with the table
+    of the same dense push (every stream at ``pos`` brings c frames)."""
     ops, streaming = _pkg()
     d, ref = _block_operands(case)
     s, total = case.s, d["x"].shape[1]
@@ -84,8 +87,15 @@ def test_block_streamed_equals_the_float64_whole_sequence_block_bit_for_bit(case
             slots = [(pos + j) & (ring_len - 1) for j in range(c)]
             arena.view(allowed, i)[:, slots] = True
         dense = torch.empty(s * c, case.cout, device="cuda")
-        ops.tcn_stream_append(dev["x"][:, pos:pos + c].contiguous(), xring, pos & (r - 1))
-        streaming.block_push(pack, xring, hring, pos, c, out_ring=oring, out_pos=pos, out_dense=dense, slope=SLOPE)
+        new = dev["x"][:, pos:pos + c].contiguous()
+        if via == "lockstep":
+            ops.tcn_stream_append(new, xring, pos & (r - 1))
+            streaming.block_push(pack, xring, hring, pos, c, out_ring=oring, out_pos=pos, out_dense=dense, slope=SLOPE)
+        else:
+            row_stream, row_pos = ops.stream_row_table([pos] * s, [c] * s, "cuda")
+            ops.tcn_stream_append_rows(new.view(s * c, case.cin), xring, row_stream, row_pos, c)
+            streaming.block_push_rows(pack, xring, hring, row_stream, row_pos, max_count=c, out_ring=oring, out_dense=dense,
+                                      slope=SLOPE)
         same = (arena.flat == before) | (torch.isnan(arena.flat) & torch.isnan(before))
         stray |= (~same & ~allowed).any()
         mirrored &= torch.equal(oring[:, [(pos + j) & (2 * r - 1) for j in range(c)]], dense.view(s, c, -1))
