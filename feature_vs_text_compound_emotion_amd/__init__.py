@@ -12,4 +12,7 @@ def __getattr__(name):
     if name in ("TCNStream", "LFANStream", "CANStream", "stream_forward"):
         from . import streaming
         return getattr(streaming, name)
+    if name == "LogMelStream":
+        from . import audio_stream
+        return audio_stream.LogMelStream
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -16,52 +16,30 @@
 #include <math.h>
 
 #include "cer_internal.h"
+#include "logmel_row.h"
 
 namespace cer {
 
-constexpr int LM_WIN = 400, LM_HOP = 160, LM_FFT = 512, LM_BINS = 257, LM_MEL = 64;
-
-__device__ __forceinline__ double lm_sample(int16_t v) { return (double)v / 32768.0; }
-__device__ __forceinline__ double lm_sample(double v) { return v; }   // already in [-1, 1): the resampler's output
-
-// One block per STFT frame.  Direct DFT with an LDS twiddle table: 257 bins x 400 taps.
+// Sample n of frame `frame` of one clip, with np.pad(..., 'edge') read by clamping the index.
 template <typename T>
-__global__ __launch_bounds__(256) void logmel_kernel(const T *__restrict__ pcm, int num_samples,
-                                                     int frames_per_clip, const double *__restrict__ mel,
-                                                     float log_offset, float *__restrict__ out) {
-    __shared__ double xs[LM_WIN];
-    __shared__ double cs[LM_FFT], sn[LM_FFT];
-    __shared__ double mag[LM_BINS + 3];
-    const int clip = blockIdx.y, frame = blockIdx.x, tid = threadIdx.x;
-    const T *src = pcm + (size_t)clip * num_samples;
-    for (int n = tid; n < LM_WIN; n += 256) {
-        int idx = frame * LM_HOP + n;
-        idx = idx < num_samples ? idx : num_samples - 1;  // np.pad(..., 'edge')
-        const double w = 0.5 - 0.5 * cospi(2.0 * (double)n / (double)LM_WIN);
-        xs[n] = lm_sample(src[idx]) * w;
+struct lm_clip_sample {
+    const T *src;   // the clip's num_samples samples
+    int first, num_samples;
+    __device__ __forceinline__ double operator()(int n) const {
+        int idx = first + n;
+        idx = idx < num_samples ? idx : num_samples - 1;
+        return lm_sample(src[idx]);
     }
-    for (int j = tid; j < LM_FFT; j += 256) {
-        double s, c;
-        sincospi(2.0 * (double)j / (double)LM_FFT, &s, &c);
-        cs[j] = c;
-        sn[j] = s;
-    }
-    __syncthreads();
-    for (int k = tid; k < LM_BINS; k += 256) {
-        double re = 0.0, im = 0.0;
-        for (int n = 0; n < LM_WIN; ++n) {
-            const int j = (k * n) & (LM_FFT - 1);
-            re += xs[n] * cs[j];
-            im -= xs[n] * sn[j];
-        }
-        mag[k] = sqrt(re * re + im * im);
-    }
-    __syncthreads();
-    if (tid < LM_MEL) {
-        double acc = 0.0;
-        for (int k = 0; k < LM_BINS; ++k) acc += mag[k] * mel[k * LM_MEL + tid];
-        out[((size_t)clip * frames_per_clip + frame) * LM_MEL + tid] = (float)log(acc + (double)log_offset);
-    }
+};
+
+// One block per STFT frame; the row itself is logmel_row (logmel_row.h), shared with the streaming kernel.
+template <typename T>
+__global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const T *__restrict__ pcm, int num_samples, int frames_per_clip,
+                                                            const double *__restrict__ mel, float log_offset,
+                                                            float *__restrict__ out) {
+    const int clip = blockIdx.y, frame = blockIdx.x;
+    const lm_clip_sample<T> sample = {pcm + (size_t)clip * num_samples, frame * LM_HOP, num_samples};
+    logmel_row(sample, mel, log_offset, out + ((size_t)clip * frames_per_clip + frame) * LM_MEL);
 }
 
 constexpr int RS_BLOCK = 256, RS_WIN = 2048;
@@ -169,7 +147,7 @@ extern "C" int cer_logmel_fwd(const int16_t *pcm, int clips, int num_samples, in
     const int frames = cer_logmel_num_frames(num_samples, pad_samples);
     if (!pcm || !mel_matrix || !logmel || clips <= 0 || num_samples <= 0 || pad_samples < 0 || frames <= 0)
         return cer_set_error(CER_ERR_INVALID_ARG, "logmel_fwd: bad argument (need at least 400 samples incl. padding)");
-    CER_LAUNCH(logmel_kernel<int16_t>, dim3(frames, clips), dim3(256), 0, (hipStream_t)stream, pcm, num_samples, frames,
+    CER_LAUNCH(logmel_kernel<int16_t>, dim3(frames, clips), dim3(LM_THREADS), 0, (hipStream_t)stream, pcm, num_samples, frames,
                mel_matrix, log_offset, logmel);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
@@ -180,7 +158,7 @@ extern "C" int cer_logmel_f64_fwd(const double *samples, int clips, int num_samp
     const int frames = cer_logmel_num_frames(num_samples, 0);
     if (!samples || !mel_matrix || !logmel || clips <= 0 || clips > 65535 || num_samples <= 0 || frames <= 0)
         return cer_set_error(CER_ERR_INVALID_ARG, "logmel_f64_fwd: bad argument (need at least 400 samples, <= 65535 clips)");
-    CER_LAUNCH(logmel_kernel<double>, dim3(frames, clips), dim3(256), 0, (hipStream_t)stream, samples, num_samples, frames,
+    CER_LAUNCH(logmel_kernel<double>, dim3(frames, clips), dim3(LM_THREADS), 0, (hipStream_t)stream, samples, num_samples, frames,
                mel_matrix, log_offset, logmel);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;

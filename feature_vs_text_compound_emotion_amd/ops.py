@@ -1763,3 +1763,103 @@ def tcn_stream_conv_rows(ring, row_stream, row_pos, max_count, w_packed, bias, k
     d = _lib.TcnStreamRowsDesc(S=s, M=m, max_count=int(max_count), Cin=cin, k=int(k), dil=int(dil), R=r, slope=float(slope))
     _stream_conv("conv_rows", d, (ptr(row_stream), ptr(row_pos)), s, cin, m, ring, w_packed, bias, res_ring, res_w, res_bias,
                  out_ring, out_dense)
+
+
+# ------------------------------------------------------------------ streaming log-mel (csrc/logmel_stream.hip)
+def logmel_stream_tables(segments, rows, examples, device):
+    """The three tables of one streamed log-mel push, from Python ints, uploaded as ONE fresh int32 tensor (one H2D copy, no
+    staging buffer an unfinished copy could still read):
+
+      segments  (stream, position of the first new sample, count, offset into the packed input or None = repeat the sample
+                before the position ``count`` times)                                                   -> int32 [4, A]
+      rows      (stream, position of the row's first sample, row number)                               -> int32 [3, N]
+      examples  (stream, start row)                                                                    -> int32 [2, E]
+
+    Positions and row numbers are unbounded Python ints and are reduced modulo 2^30 here and only here.  Returns the three
+    views; an empty list gives None."""
+    cols = []
+    for s, pos, count, off in segments:
+        s, pos, count = int(s), int(pos), int(count)
+        off = -1 if off is None else int(off)
+        if pos < 0 or count < 1 or not -1 <= off < (1 << 31) - 1:
+            raise ValueError(f"logmel_stream_tables: segment of stream {s}: position {pos}, count {count}, offset {off}")
+        cols.append((s, pos % ROW_POS_MOD, count, off))
+    seg = [c[f] for f in range(4) for c in cols]
+    row = [(int(s), int(pos) % ROW_POS_MOD, int(r) % ROW_POS_MOD) for s, pos, r in rows]
+    ex = [(int(s), int(start) % ROW_POS_MOD) for s, start in examples]
+    flat = seg + [c[f] for f in range(3) for c in row] + [c[f] for f in range(2) for c in ex]
+    for v in flat:
+        if not -(1 << 31) <= v < (1 << 31):
+            raise ValueError(f"logmel_stream_tables: {v} does not fit an int32")
+    table = torch.tensor(flat, dtype=torch.int32, device=device)
+    a, n, e = 4 * len(cols), 3 * len(row), 2 * len(ex)
+    return (table[:a].view(4, -1) if a else None, table[a:a + n].view(3, -1) if n else None,
+            table[a + n:a + n + e].view(2, -1) if e else None)
+
+
+def _stream_table(t, name, fields, like):
+    """An int32 table [fields, n >= 1], contiguous, on the device of ``like``.  Returns n."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.device == like.device and t.dtype == torch.int32 and t.is_contiguous()
+            and t.dim() == 2 and t.shape[0] == fields and t.shape[1] >= 1):
+        raise ValueError(f"{name}: expected a contiguous int32 [{fields}, n >= 1] table on the GPU of the ring ({like.device}), "
+                         f"got {(t.dtype, t.device, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
+    return t.shape[1]
+
+
+def _sample_ring(t):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int16 and t.is_contiguous() and t.dim() == 2):
+        raise ValueError("ring: expected a contiguous [S, Rs] int16 GPU tensor")
+    return t.shape
+
+
+def _logmel_ring(t):
+    _dev_f32(t, "logmel_ring")
+    if t.dim() != 3 or t.shape[2] != 64:
+        raise ValueError(f"logmel_ring: expected [S, Rm, 64], got {tuple(t.shape)}")
+    return t.shape[0], t.shape[1]
+
+
+def logmel_stream_append(packed, segments, max_count, ring):
+    """Write the new int16 samples ``packed`` [M >= 1] of a push into the sample ring [S, Rs] as the segment table says
+    (``logmel_stream_tables``); ``max_count``: the largest count in it."""
+    s, rs = _sample_ring(ring)
+    if not (torch.is_tensor(packed) and packed.is_cuda and packed.device == ring.device and packed.dtype == torch.int16
+            and packed.is_contiguous() and packed.dim() == 1 and packed.shape[0] >= 1):
+        raise ValueError("packed: expected a contiguous int16 vector of at least one sample on the GPU of the ring")
+    a = _stream_table(segments, "segments", 4, ring)
+    check(_lib.load().cer_logmel_stream_append(ptr(packed), packed.shape[0], ptr(segments), a, int(max_count), ptr(ring), s, rs,
+                                               current_stream()), "cer_logmel_stream_append")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("logmel_append", 0))
+
+
+def logmel_stream_rows(ring, rows, mel_matrix_f64, logmel_ring, log_offset=0.01):
+    """One log-mel row per entry of the row table, from 400 samples of the sample ring [S, Rs] into the log-mel ring
+    [S, Rm, 64]: the bits ``logmel`` gives the same samples."""
+    s, rs = _sample_ring(ring)
+    sm, rm = _logmel_ring(logmel_ring)
+    if sm != s or logmel_ring.device != ring.device:
+        raise ValueError(f"logmel_ring: expected {s} streams on {ring.device}, got {sm} on {logmel_ring.device}")
+    if not (mel_matrix_f64.is_cuda and mel_matrix_f64.dtype == torch.float64 and tuple(mel_matrix_f64.shape) == (257, 64)
+            and mel_matrix_f64.is_contiguous() and mel_matrix_f64.device == ring.device):
+        raise ValueError("mel matrix: expected a contiguous [257, 64] float64 tensor on the GPU of the ring")
+    n = _stream_table(rows, "rows", 3, ring)
+    check(_lib.load().cer_logmel_stream_rows(ptr(ring), s, rs, ptr(rows), n, ptr(mel_matrix_f64), log_offset, ptr(logmel_ring),
+                                             rm, current_stream()), "cer_logmel_stream_rows")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("logmel_rows", 0))
+
+
+def logmel_stream_examples(logmel_ring, examples, win=96):
+    """Gather ``win`` rows of the log-mel ring [S, Rm, 64] per entry of the example table -> [E, win, 64]."""
+    s, rm = _logmel_ring(logmel_ring)
+    e = _stream_table(examples, "examples", 2, logmel_ring)
+    win = int(win)
+    if not 1 <= win <= rm:
+        raise ValueError(f"logmel_stream_examples: win = {win} outside 1 .. Rm = {rm}")
+    out = torch.empty((e, win, 64), device=logmel_ring.device, dtype=torch.float32)
+    check(_lib.load().cer_logmel_stream_examples(ptr(logmel_ring), s, rm, ptr(examples), e, win, ptr(out), current_stream()),
+          "cer_logmel_stream_examples")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("logmel_examples", 0))
+    return out

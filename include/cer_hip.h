@@ -698,6 +698,41 @@ int cer_tcn_stream_conv_rows(const cer_tcn_stream_rows_desc *d, const int32_t *r
 int cer_tcn_stream_append_rows(const float *rows, float *ring, const int32_t *row_stream, const int32_t *row_pos, int S, int M,
                                int max_count, int C, int R, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Streaming log-mel front end: cer_logmel_fwd and cer_frame_examples run on PCM chunks of S independent streams.
+ *
+ * State: a sample ring [S][Rs] int16 and a log-mel ring [S][Rm][64] fp32; Rs and Rm are powers of two up to 2^30.  The
+ * device keeps no counters.  The host says what a launch does in int32 tables in device memory; sample positions and row
+ * numbers in them are unwrapped, modulo 2^30 (every ring length divides 2^30, so the mask R - 1 finds the slot).  One push
+ * is the three launches below on one HIP stream, in this order.
+ *
+ * cer_logmel_stream_append: segments [4][num_segments] = stream, position of the segment's first sample, count, offset.
+ *     offset >= 0:  ring[stream][(pos + i) & (Rs - 1)] = packed[offset + i]                          for i < count
+ *     offset <  0:  ring[stream][(pos + i) & (Rs - 1)] = ring[stream][(pos - 1) & (Rs - 1)]          (repeat the sample before)
+ *   packed holds packed_len samples; an index past it reads as 0.  max_count is the largest count in the table (the entry
+ *   cannot read it); a larger count is cut to it.  A stream has at most one segment in a launch.
+ * cer_logmel_stream_rows: rows [3][num_rows] = stream, position of the row's first sample, row number.  Row m is the
+ *   log-mel of the 400 samples ring[stream][(pos + n) & (Rs - 1)], n < 400, computed by the one device function that
+ *   cer_logmel_fwd runs (csrc/logmel_row.h): the same bits as that entry gives the same samples.  It is written to
+ *   logmel_ring[stream][row & (Rm - 1)][0 .. 63].
+ * cer_logmel_stream_examples: examples [2][num_examples] = stream, start row.
+ *     out[e][f][:] = logmel_ring[stream][(start + f) & (Rm - 1)][:]   for f < win;   out [num_examples][win][64].
+ *
+ * The tables are never trusted with an address: a stream index is clamped into [0, S), every position is masked with its
+ * ring length and every read of `packed` is bounded by packed_len.  A wrong table gives wrong numbers, never an access
+ * outside a ring or outside the packed input.
+ * Refused with CER_ERR_INVALID_ARG before any launch, with a cer_last_error() text that begins with the entry's name: a null
+ * pointer; a count (packed_len, num_segments, max_count, num_rows, num_examples, win, S) below 1; Rs or Rm not a power of
+ * two up to 2^30; Rs < 400; max_count >= Rs; Rm < win; more than 65535 segments; a log-mel ring or an output of
+ * cer_logmel_stream_examples that is not 16-byte aligned.
+ * ---------------------------------------------------------------------- */
+int cer_logmel_stream_append(const int16_t *packed, int packed_len, const int32_t *segments, int num_segments, int max_count,
+                             int16_t *ring, int S, int Rs, void *stream);
+int cer_logmel_stream_rows(const int16_t *ring, int S, int Rs, const int32_t *rows, int num_rows, const double *mel_matrix,
+                           float log_offset, float *logmel_ring, int Rm, void *stream);
+int cer_logmel_stream_examples(const float *logmel_ring, int S, int Rm, const int32_t *examples, int num_examples, int win,
+                               float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
