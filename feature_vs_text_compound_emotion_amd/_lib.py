@@ -141,6 +141,9 @@ _SIGNATURES = {
     "cer_logmel_stream_append": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_int, c_int, _P]),
     "cer_logmel_stream_rows": (c_int, [_P, c_int, c_int, _P, c_int, _P, c_float, _P, c_int, _P]),
     "cer_logmel_stream_examples": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, _P]),
+    "cer_resample_stream_append": (c_int, [_P, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, _P]),
+    "cer_resample_stream_outputs": (c_int, [_P, c_int, c_int, _P, c_int, c_int, _P, c_int, c_int, c_int, _P, c_int, _P]),
+    "cer_logmel_stream_rows_f64": (c_int, [_P, c_int, c_int, _P, c_int, _P, c_float, _P, c_int, _P]),
     "cer_add_inplace": (c_int, [_P, _P, c_size_t, _P]),
     "cer_l2norm_rows": (c_int, [_P, _P, c_int, c_int, _P]),
     "cer_l2norm_rows_bwd": (c_int, [_P, _P, _P, c_int, c_int, _P]),

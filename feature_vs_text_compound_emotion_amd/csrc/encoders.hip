@@ -17,6 +17,7 @@
 
 #include "cer_internal.h"
 #include "logmel_row.h"
+#include "resample_row.h"
 
 namespace cer {
 
@@ -42,47 +43,30 @@ __global__ __launch_bounds__(LM_THREADS) void logmel_kernel(const T *__restrict_
     logmel_row(sample, mel, log_offset, out + ((size_t)clip * frames_per_clip + frame) * LM_MEL);
 }
 
-constexpr int RS_BLOCK = 256, RS_WIN = 2048;
+// Input sample k of one clip: the channel mean (rs_mix) for 0 <= k < S, the last of those for S <= k < S + pad (np.pad 'edge',
+// read by clamping the index like logmel_kernel) and zero outside.
+struct rs_clip_input {
+    const int16_t *src;   // the clip's S frames of C interleaved channels
+    int S, C;
+    long long padded;     // S + pad
+    __device__ __forceinline__ double operator()(long long k) const {
+        if (k < 0 || k >= padded) return 0.0;
+        return rs_mix(src + (size_t)(k < S ? k : S - 1) * C, C);
+    }
+};
 
-// out[c][n] = sum_j taps[r][j] * x[c][q - J + j] with q = (n M) div L, r = (n M) mod L, J = (T - 2) / 2, where
-// x[c][k] is the channel mean of pcm[c][k][:] / 32768 for 0 <= k < S, the last of those for S <= k < S + pad (np.pad
-// 'edge', read by clamping the index like logmel_kernel) and zero outside.  One thread per output.  A block's 256
-// outputs read one contiguous run of inputs; it is mixed down once into LDS, RS_WIN samples at a time, so the LDS need
-// does not grow with M / L or T, and every thread still adds its taps in the order j = 0 .. T - 1.
+// out[c][n] = sum_j taps[r][j] * x[c][q - J + j] with q = (n M) div L, r = (n M) mod L, J = (T - 2) / 2, x as rs_clip_input
+// has it.  One thread per output, 256 consecutive outputs per block; the sum itself is resample_block (resample_row.h),
+// shared with the streaming kernel.
 __global__ __launch_bounds__(RS_BLOCK) void resample_pcm_kernel(const int16_t *__restrict__ pcm, int S, int C, int pad,
                                                                 const double *__restrict__ taps, int L, int M, int T,
                                                                 int n_out, double *__restrict__ out) {
-    __shared__ double xs[RS_WIN];
-    const int clip = blockIdx.y, tid = threadIdx.x;
+    const int clip = blockIdx.y;
     const long long n_first = (long long)blockIdx.x * RS_BLOCK;
     const long long n_last = (n_first + RS_BLOCK < n_out ? n_first + RS_BLOCK : (long long)n_out) - 1;
-    const long long n = n_first + tid;
-    const long long nl = n <= n_last ? n : n_last;   // threads past the end shadow the last output and store nothing
-    const long long J = (T - 2) / 2;
-    const long long k0 = n_first * M / L - J;                 // first input the block reads
-    const long long span = n_last * M / L - J + T - k0;       // ... and how many
-    const long long d = nl * M / L - J - k0;                  // this thread's first input, relative to k0
-    const double *row = taps + (size_t)((nl * M) % L) * T;
-    const int16_t *src = pcm + (size_t)clip * S * C;
-    const long long padded = (long long)S + pad;
-    double acc = 0.0;
-    for (long long w = 0; w < span; w += RS_WIN) {
-        const int fill = (int)(span - w < RS_WIN ? span - w : RS_WIN);
-        for (int i = tid; i < fill; i += RS_BLOCK) {
-            const long long k = k0 + w + i;
-            double v = 0.0;
-            if (k >= 0 && k < padded) {
-                const int16_t *p = src + (size_t)(k < S ? k : S - 1) * C;
-                for (int ch = 0; ch < C; ++ch) v += (double)p[ch] / 32768.0;
-                v /= (double)C;
-            }
-            xs[i] = v;
-        }
-        __syncthreads();
-        const long long j_lo = w > d ? w - d : 0, j_hi = w + fill - d < T ? w + fill - d : T;
-        for (long long j = j_lo; j < j_hi; ++j) acc += row[j] * xs[d + j - w];
-        __syncthreads();
-    }
+    const long long n = n_first + threadIdx.x;
+    const rs_clip_input input = {pcm + (size_t)clip * S * C, S, C, (long long)S + pad};
+    const double acc = resample_block(input, taps, L, M, T, 0, n_first, n_last);
     if (n <= n_last) out[(size_t)clip * n_out + n] = acc;
 }
 

@@ -22,11 +22,32 @@
 // [0, S), a count into [0, max_count], every position is masked with its ring length and every read of the packed input is
 // bounded by its length (a sample past the end reads as 0).  A wrong table gives wrong numbers, never an access outside a
 // ring or outside the packed input.  No grid sync, no flags, no atomics, no scratch.
+//
+// RESAMPLED INPUT (PCM at any rate, any number of channels).  Two more rings stand in front: a mixed-input ring [S][Rin]
+// float64 (the channel mean at the input rate) and, in place of the int16 sample ring, a 16 kHz ring [S][Rs] float64 (the
+// resampler's output).  A push is then four launches:
+//
+//   mix-append  in[s][(pos + i) & (Rin - 1)] = rs_mix(packed frame offset + i), i < count; offset < 0 repeats the sample
+//               before the position (the edge padding, now at the input rate)
+//   resample    segment (s, n0, count, r0, pos of q0, lo, hi): output n0 + i sits at input q0 + (r0 + i M) / L; one thread per
+//               output, 256 consecutive outputs of one segment per block, summed by resample_block (resample_row.h, the
+//               body of the offline kernel) and written to ring[s][(n0 + i) & (Rs - 1)].  n0 M does not fit 32 bits over a
+//               long stream, so the host hands over r0 = (n0 M) mod L and the ring position of q0 = (n0 M) div L and the
+//               kernel advances from there in 64 bits.  Input q0 + k is a ring read only for lo <= k < hi, the stream's
+//               valid inputs relative to q0; outside it is ZERO BY THE RANGE CHECK, never a ring read: after a wrap the
+//               slots before the stream's first sample and after its last hold old samples.
+//   rows        the rows kernel above, instantiated for the float64 ring (lm_sample(double))
+//   examples    as above
+//
+// INVARIANT.  An output is a function of its T inputs only and is one chain of T multiply-adds in the order j = 0 .. T - 1 in
+// the one body the offline kernel runs; the mixed sample is computed by the one rs_mix.  So the 16 kHz ring holds the bits
+// ops.resample_pcm gives the padded whole signal, and the examples are those of wav_int16_to_examples(resample=...).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "cer_internal.h"
 #include "logmel_row.h"
+#include "resample_row.h"
 
 namespace cer {
 
@@ -57,22 +78,78 @@ __global__ void logmel_stream_append_kernel(const int16_t *__restrict__ packed, 
     dst[ls_slot(pos, i, Rs)] = v;
 }
 
-// Sample n of the row that starts at unwrapped position pos of one stream's ring.
+// Sample n of the row that starts at unwrapped position pos of one stream's ring (int16 PCM, or float64 resampler output).
+template <typename T>
 struct ls_ring_sample {
-    const int16_t *ring;   // the stream's Rs slots
+    const T *ring;   // the stream's Rs slots
     int pos, Rs;
     __device__ __forceinline__ double operator()(int n) const { return lm_sample(ring[ls_slot(pos, n, Rs)]); }
 };
 
 // rows: [3][N] int32 = stream, position of the row's first sample, row number.  One block per row.
-__global__ __launch_bounds__(LM_THREADS) void logmel_stream_rows_kernel(const int16_t *__restrict__ ring, int S, int Rs,
+template <typename T>
+__global__ __launch_bounds__(LM_THREADS) void logmel_stream_rows_kernel(const T *__restrict__ ring, int S, int Rs,
                                                                         const int32_t *__restrict__ rows, int N,
                                                                         const double *__restrict__ mel, float log_offset,
                                                                         float *__restrict__ melring, int Rm) {
     const int m = blockIdx.x;
     const int s = ls_stream(rows[m], S), pos = rows[N + m], row = rows[2 * N + m];
-    const ls_ring_sample sample = {ring + (size_t)s * Rs, pos, Rs};
+    const ls_ring_sample<T> sample = {ring + (size_t)s * Rs, pos, Rs};
     logmel_row(sample, mel, log_offset, melring + ((size_t)s * Rm + ls_slot(row, 0, Rm)) * LM_MEL);
+}
+
+// segments: [4][A] int32 = stream, position of the first new input sample, count, offset into `packed` in frames (< 0:
+// repeat).  packed: packed_frames frames of C interleaved int16 channels.  Grid (ceil(max_count / 256), A).  As in the append
+// kernel above, a repeat segment never overwrites the slot it reads (count <= max_count < Rin).
+__global__ void resample_stream_append_kernel(const int16_t *__restrict__ packed, int packed_frames, int C,
+                                              const int32_t *__restrict__ segments, int A, int max_count,
+                                              double *__restrict__ ring, int S, int Rin) {
+    const int a = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = ls_stream(segments[a], S), pos = segments[A + a], off = segments[3 * A + a];
+    const int count = min(max(segments[2 * A + a], 0), max_count);
+    if (i >= count) return;
+    double *dst = ring + (size_t)s * Rin;
+    double v;
+    if (off < 0) {
+        v = dst[ls_slot(pos, -1, Rin)];
+    } else {
+        const long long src = (long long)off + i;
+        v = src < packed_frames ? rs_mix(packed + (size_t)src * C, C) : 0.0;
+    }
+    dst[ls_slot(pos, i, Rin)] = v;
+}
+
+// Input q0 + k of one stream: a read of its mixed-input ring for lo <= k < hi, zero outside.
+struct rs_ring_input {
+    const double *ring;   // the stream's Rin slots
+    int pos, Rin;         // unwrapped position of q0
+    long long lo, hi;
+    __device__ __forceinline__ double operator()(long long k) const {
+        // (unsigned)k is k modulo 2^32, and Rin divides 2^32: the mask finds the slot of pos + k for a negative k too
+        return k >= lo && k < hi ? ring[((unsigned)pos + (unsigned)k) & (unsigned)(Rin - 1)] : 0.0;
+    }
+};
+
+// segments: [7][A] int32 = stream, position n0 of the first output, count, r0, position of q0, lo, hi.  Grid
+// (ceil(max_count / 256), A); a block past its segment's count leaves as a whole, before any barrier.  The valid range is cut
+// to the Rin samples before hi, so no two inputs of a launch can share a slot whatever the table says.
+__global__ __launch_bounds__(RS_BLOCK) void resample_stream_kernel(const double *__restrict__ in_ring, int S, int Rin,
+                                                                   const int32_t *__restrict__ segments, int A, int max_count,
+                                                                   const double *__restrict__ taps, int L, int M, int T,
+                                                                   double *__restrict__ out_ring, int Rs) {
+    const int a = blockIdx.y;
+    const int s = ls_stream(segments[a], S), n0 = segments[A + a];
+    const int count = min(max(segments[2 * A + a], 0), max_count);
+    const long long i_first = (long long)blockIdx.x * RS_BLOCK;
+    if (i_first >= count) return;
+    const long long i_last = (i_first + RS_BLOCK < count ? i_first + RS_BLOCK : (long long)count) - 1;
+    int r0 = segments[3 * A + a] % L;   // the tap row is (r0 + i M) mod L: in [0, L) for any table
+    r0 = r0 < 0 ? r0 + L : r0;
+    const long long hi = segments[6 * A + a], lo_t = segments[5 * A + a];
+    const rs_ring_input input = {in_ring + (size_t)s * Rin, segments[4 * A + a], Rin, lo_t > hi - Rin ? lo_t : hi - Rin, hi};
+    const double acc = resample_block(input, taps, L, M, T, r0, i_first, i_last);
+    const long long i = i_first + threadIdx.x;
+    if (i <= i_last) out_ring[(size_t)s * Rs + ls_slot(n0, (int)i, Rs)] = acc;
 }
 
 // examples: [2][E] int32 = stream, start row.  One thread per float4 of the output [E][win][64].
@@ -123,8 +200,63 @@ extern "C" int cer_logmel_stream_rows(const int16_t *ring, int S, int Rs, const 
     if (!ls_ring_len(Rs) || Rs < LM_WIN)
         LS_REFUSE("logmel_stream_rows: ring length Rs = %d is not a power of two from 512 to 2^30", Rs);
     if (!ls_ring_len(Rm)) LS_REFUSE("logmel_stream_rows: ring length Rm = %d is not a power of two up to 2^30", Rm);
-    CER_LAUNCH(logmel_stream_rows_kernel, dim3(num_rows), dim3(LM_THREADS), 0, ST, ring, S, Rs, rows, num_rows, mel_matrix,
+    CER_LAUNCH(logmel_stream_rows_kernel<int16_t>, dim3(num_rows), dim3(LM_THREADS), 0, ST, ring, S, Rs, rows, num_rows, mel_matrix,
                log_offset, logmel_ring, Rm);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_logmel_stream_rows_f64(const double *ring, int S, int Rs, const int32_t *rows, int num_rows,
+                                          const double *mel_matrix, float log_offset, float *logmel_ring, int Rm,
+                                          void *stream) {
+    if (!ring || !rows || !mel_matrix || !logmel_ring) LS_REFUSE("logmel_stream_rows_f64: null pointer");
+    if (S < 1 || num_rows < 1) LS_REFUSE("logmel_stream_rows_f64: streams and rows must be >= 1");
+    if (!ls_ring_len(Rs) || Rs < LM_WIN)
+        LS_REFUSE("logmel_stream_rows_f64: ring length Rs = %d is not a power of two from 512 to 2^30", Rs);
+    if (!ls_ring_len(Rm)) LS_REFUSE("logmel_stream_rows_f64: ring length Rm = %d is not a power of two up to 2^30", Rm);
+    CER_LAUNCH(logmel_stream_rows_kernel<double>, dim3(num_rows), dim3(LM_THREADS), 0, ST, ring, S, Rs, rows, num_rows,
+               mel_matrix, log_offset, logmel_ring, Rm);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_resample_stream_append(const int16_t *packed, int packed_frames, int channels, const int32_t *segments,
+                                          int num_segments, int max_count, int history, double *in_ring, int S, int Rin,
+                                          void *stream) {
+    if (!packed || !segments || !in_ring) LS_REFUSE("resample_stream_append: null pointer");
+    if (packed_frames < 1 || channels < 1 || num_segments < 1 || max_count < 1 || S < 1 || history < 0)
+        LS_REFUSE("resample_stream_append: packed frames, channels, segments, frames of a segment and streams must be >= 1, "
+                  "history >= 0");
+    if (!ls_ring_len(Rin)) LS_REFUSE("resample_stream_append: ring length Rin = %d is not a power of two up to 2^30", Rin);
+    if ((long long)history + max_count > Rin || max_count >= Rin)
+        LS_REFUSE("resample_stream_append: %d old inputs and %d new ones of a stream exceed Rin = %d", history, max_count, Rin);
+    if (num_segments > 65535) LS_REFUSE("resample_stream_append: %d segments exceed the grid", num_segments);
+    CER_LAUNCH(resample_stream_append_kernel, dim3(cer_blocks((size_t)max_count, 256), num_segments), dim3(256), 0, ST, packed,
+               packed_frames, channels, segments, num_segments, max_count, in_ring, S, Rin);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+extern "C" int cer_resample_stream_outputs(const double *in_ring, int S, int Rin, const int32_t *segments, int num_segments,
+                                           int max_count, const double *taps, int L, int M, int T, double *out_ring, int Rs,
+                                           void *stream) {
+    if (!in_ring || !segments || !taps || !out_ring) LS_REFUSE("resample_stream_outputs: null pointer");
+    if (S < 1 || num_segments < 1 || max_count < 1)
+        LS_REFUSE("resample_stream_outputs: streams, segments and outputs of a segment must be >= 1");
+    if (L <= 0 || M <= 0) LS_REFUSE("resample_stream_outputs: L = %d and M = %d must be positive", L, M);
+    if (T < 2 || (T & 1)) LS_REFUSE("resample_stream_outputs: T = %d taps per phase must be even and >= 2", T);
+    if (!ls_ring_len(Rin) || Rin < T)
+        LS_REFUSE("resample_stream_outputs: ring length Rin = %d is not a power of two from T = %d to 2^30", Rin, T);
+    if (!ls_ring_len(Rs)) LS_REFUSE("resample_stream_outputs: ring length Rs = %d is not a power of two up to 2^30", Rs);
+    if (max_count > Rs) LS_REFUSE("resample_stream_outputs: %d outputs of a stream exceed Rs = %d", max_count, Rs);
+    // The kernel's 64-bit r0 + i M (r0 < L < 2^31, i < max_count <= 2^30) stays below 2^62 and its 32-bit quantities (an LDS
+    // window's fill, a masked slot) do not grow with M / L; what grows is the run of inputs one block walks through.
+    if ((long long)RS_BLOCK * M / L + T > (1 << 24))
+        LS_REFUSE("resample_stream_outputs: a block of %d outputs would read %lld inputs (M / L = %d / %d, T = %d), more than "
+                  "2^24", RS_BLOCK, (long long)RS_BLOCK * M / L + T, M, L, T);
+    if (num_segments > 65535) LS_REFUSE("resample_stream_outputs: %d segments exceed the grid", num_segments);
+    CER_LAUNCH(resample_stream_kernel, dim3(cer_blocks((size_t)max_count, RS_BLOCK), num_segments), dim3(RS_BLOCK), 0, ST,
+               in_ring, S, Rin, segments, num_segments, max_count, taps, L, M, T, out_ring, Rs);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }

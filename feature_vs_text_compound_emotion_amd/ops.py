@@ -1863,3 +1863,108 @@ def logmel_stream_examples(logmel_ring, examples, win=96):
     if STREAM_TRACE is not None:
         STREAM_TRACE.append(("logmel_examples", 0))
     return out
+
+
+# ------------------------------------------------------------------ streaming resampler (csrc/logmel_stream.hip)
+def resample_stream_tables(mix, outputs, rows, examples, device):
+    """The four tables of one resampled push, from Python ints, uploaded as ONE fresh int32 tensor like
+    ``logmel_stream_tables``:
+
+      mix       (stream, position of the first new input frame, count, offset in frames into the packed input or None =
+                repeat the sample before the position)                                                  -> int32 [4, A]
+      outputs   (stream, first output n0, count, r0, q0, inputs the stream has) with q0, r0 = divmod(n0 M, L): the kernel
+                gets n0 and q0 as ring positions and the stream's valid inputs [0, inputs) as the range [-q0, inputs - q0)
+                relative to q0                                                                          -> int32 [7, B]
+      rows      (stream, position of the row's first 16 kHz sample, row number)                         -> int32 [3, N]
+      examples  (stream, start row)                                                                     -> int32 [2, E]
+
+    Positions are unbounded Python ints and are reduced modulo 2^30 here and only here; the two ends of the valid range are
+    clamped to +-2^30, further than any launch reads.  Returns the four views; an empty list gives None."""
+    mcols = []
+    for s, pos, count, off in mix:
+        s, pos, count = int(s), int(pos), int(count)
+        off = -1 if off is None else int(off)
+        if pos < 0 or count < 1 or not -1 <= off < (1 << 31) - 1:
+            raise ValueError(f"resample_stream_tables: mix segment of stream {s}: position {pos}, count {count}, offset {off}")
+        mcols.append((s, pos % ROW_POS_MOD, count, off))
+    ocols = []
+    for s, n0, count, r0, q0, inputs in outputs:
+        s, n0, count, r0, q0, inputs = int(s), int(n0), int(count), int(r0), int(q0), int(inputs)
+        if n0 < 0 or count < 1 or r0 < 0 or q0 < 0 or inputs < 0:
+            raise ValueError(f"resample_stream_tables: output segment of stream {s}: n0 {n0}, count {count}, r0 {r0}, q0 {q0}, "
+                             f"inputs {inputs}")
+        lo, hi = (min(max(v, -ROW_POS_MOD), ROW_POS_MOD) for v in (-q0, inputs - q0))
+        ocols.append((s, n0 % ROW_POS_MOD, count, r0, q0 % ROW_POS_MOD, lo, hi))
+    row = [(int(s), int(pos) % ROW_POS_MOD, int(r) % ROW_POS_MOD) for s, pos, r in rows]
+    ex = [(int(s), int(start) % ROW_POS_MOD) for s, start in examples]
+    flat = []
+    for cols, fields in ((mcols, 4), (ocols, 7), (row, 3), (ex, 2)):
+        flat += [c[f] for f in range(fields) for c in cols]
+    for v in flat:
+        if not -(1 << 31) <= v < (1 << 31):
+            raise ValueError(f"resample_stream_tables: {v} does not fit an int32")
+    table = torch.tensor(flat, dtype=torch.int32, device=device)
+    views, at = [], 0
+    for cols, fields in ((mcols, 4), (ocols, 7), (row, 3), (ex, 2)):
+        n = fields * len(cols)
+        views.append(table[at:at + n].view(fields, -1) if n else None)
+        at += n
+    return tuple(views)
+
+
+def _f64_ring(t, name):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 2):
+        raise ValueError(f"{name}: expected a contiguous [S, R] float64 GPU tensor")
+    return t.shape
+
+
+def resample_stream_append(packed, segments, max_count, history, in_ring):
+    """Mix the new int16 frames ``packed`` ([M >= 1] mono or interleaved [M, C]) of a push down into the mixed-input ring
+    [S, Rin] float64 as the mix table says (``resample_stream_tables``); ``max_count``: the largest count in it;
+    ``history``: the inputs before the new ones that are still needed (T - 1)."""
+    s, rin = _f64_ring(in_ring, "in_ring")
+    if not (torch.is_tensor(packed) and packed.is_cuda and packed.device == in_ring.device and packed.dtype == torch.int16
+            and packed.is_contiguous() and packed.dim() in (1, 2) and packed.shape[0] >= 1 and packed.numel() >= 1):
+        raise ValueError("packed: expected a contiguous int16 [M] or [M, C] tensor of at least one frame on the GPU of the ring")
+    channels = packed.shape[1] if packed.dim() == 2 else 1
+    a = _stream_table(segments, "segments", 4, in_ring)
+    check(_lib.load().cer_resample_stream_append(ptr(packed), packed.shape[0], channels, ptr(segments), a, int(max_count),
+                                                 int(history), ptr(in_ring), s, rin, current_stream()),
+          "cer_resample_stream_append")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("resample_append", 0))
+
+
+def resample_stream_outputs(in_ring, segments, max_count, taps, L, M, out_ring):
+    """The 16 kHz samples the output table names, from the mixed-input ring [S, Rin] into the sample ring [S, Rs] (both
+    float64): the bits ``resample_pcm`` gives the same inputs.  ``taps`` [L, T] float64; ``max_count``: the largest count."""
+    s, rin = _f64_ring(in_ring, "in_ring")
+    so, rs = _f64_ring(out_ring, "out_ring")
+    if so != s or out_ring.device != in_ring.device:
+        raise ValueError(f"out_ring: expected {s} streams on {in_ring.device}, got {so} on {out_ring.device}")
+    L, M = int(L), int(M)
+    if not (taps.is_cuda and taps.dtype == torch.float64 and taps.is_contiguous() and taps.dim() == 2 and L >= 1
+            and taps.shape[0] == L and taps.shape[1] >= 2 and taps.shape[1] % 2 == 0 and taps.device == in_ring.device):
+        raise ValueError("taps: expected a contiguous [L, T] float64 tensor with T even on the GPU of the rings")
+    b = _stream_table(segments, "segments", 7, in_ring)
+    check(_lib.load().cer_resample_stream_outputs(ptr(in_ring), s, rin, ptr(segments), b, int(max_count), ptr(taps), L, M,
+                                                  taps.shape[1], ptr(out_ring), rs, current_stream()),
+          "cer_resample_stream_outputs")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("resample_outputs", 0))
+
+
+def logmel_stream_rows_f64(ring, rows, mel_matrix_f64, logmel_ring, log_offset=0.01):
+    """``logmel_stream_rows`` on the float64 16 kHz ring [S, Rs]: the bits ``logmel_f64`` gives the same samples."""
+    s, rs = _f64_ring(ring, "ring")
+    sm, rm = _logmel_ring(logmel_ring)
+    if sm != s or logmel_ring.device != ring.device:
+        raise ValueError(f"logmel_ring: expected {s} streams on {ring.device}, got {sm} on {logmel_ring.device}")
+    if not (mel_matrix_f64.is_cuda and mel_matrix_f64.dtype == torch.float64 and tuple(mel_matrix_f64.shape) == (257, 64)
+            and mel_matrix_f64.is_contiguous() and mel_matrix_f64.device == ring.device):
+        raise ValueError("mel matrix: expected a contiguous [257, 64] float64 tensor on the GPU of the ring")
+    n = _stream_table(rows, "rows", 3, ring)
+    check(_lib.load().cer_logmel_stream_rows_f64(ptr(ring), s, rs, ptr(rows), n, ptr(mel_matrix_f64), log_offset,
+                                                 ptr(logmel_ring), rm, current_stream()), "cer_logmel_stream_rows_f64")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("logmel_rows_f64", 0))

@@ -733,6 +733,48 @@ int cer_logmel_stream_rows(const int16_t *ring, int S, int Rs, const int32_t *ro
 int cer_logmel_stream_examples(const float *logmel_ring, int S, int Rm, const int32_t *examples, int num_examples, int win,
                                float *out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Streaming resampler: cer_resample_pcm run on PCM chunks, in front of the streaming log-mel.  Any input rate, any number of
+ * interleaved channels.
+ *
+ * State: a mixed-input ring [S][Rin] float64 (the channel mean of pcm / 32768 at the input rate) and a 16 kHz sample ring
+ * [S][Rs] float64 (the resampler's output, in [-1, 1)), then the log-mel ring above; Rin and Rs are powers of two up to 2^30.
+ * The device keeps no counters; tables and positions as above (int32, unwrapped modulo 2^30).  One push is four launches on
+ * one HIP stream: cer_resample_stream_append, cer_resample_stream_outputs, cer_logmel_stream_rows_f64,
+ * cer_logmel_stream_examples.
+ *
+ * cer_resample_stream_append: segments [4][num_segments] = stream, position of the segment's first input sample, count,
+ *   offset in frames.  packed holds packed_frames frames of `channels` interleaved int16 samples.
+ *     offset >= 0:  in_ring[stream][(pos + i) & (Rin - 1)] = (sum_ch packed[offset + i][ch] / 32768.0) / channels   for i < count
+ *     offset <  0:  in_ring[stream][(pos + i) & (Rin - 1)] = in_ring[stream][(pos - 1) & (Rin - 1)]   (repeat the sample before)
+ *   A frame past packed_frames reads as 0; a count above max_count is cut to it.  history: how many inputs before the new
+ *   ones the caller still needs (T - 1 for a table of T taps per phase); only checked against Rin.
+ * cer_resample_stream_outputs: segments [7][num_segments] = stream, position n0 of the first output, count, r0, position of
+ *   input q0, lo, hi, where q0 = (n0 M) div L and r0 = (n0 M) mod L in the caller's unbounded integers.  For i < count, with
+ *   q = (r0 + i M) div L, r = (r0 + i M) mod L (64-bit) and J = (T - 2) / 2:
+ *     out_ring[stream][(n0 + i) & (Rs - 1)] = sum_{j < T} taps[r][j] * x[q - J + j]
+ *     x[k] = in_ring[stream][(pos_q0 + k) & (Rin - 1)]  for lo <= k < hi,  0 otherwise
+ *   [lo, hi) is the stream's valid input range relative to q0 (before its first sample and at or after its last appended
+ *   sample the ring holds old samples, so those inputs are zero by this check, never a ring read); it is cut to the Rin
+ *   inputs before hi.  taps is [L][T] float64.  The sum is the device function cer_resample_pcm runs
+ *   (csrc/resample_row.h), in the order j = 0 .. T - 1: the same bits as that entry gives the same inputs.
+ * cer_logmel_stream_rows_f64: cer_logmel_stream_rows on the float64 16 kHz ring (samples already in [-1, 1)).
+ *
+ * The tables are never trusted with an address: a stream index is clamped into [0, S), a count is cut to max_count, every
+ * position is masked with its ring length, every read of `packed` is bounded by packed_frames and r0 is reduced modulo L.
+ * Refused with CER_ERR_INVALID_ARG before any launch, with a cer_last_error() text that begins with the entry's name: a null
+ * pointer; a count (packed_frames, channels, num_segments, max_count, num_rows, S) below 1 or history < 0; a ring length
+ * that is not a power of two up to 2^30; Rs < 400 for the rows; history + max_count > Rin or max_count >= Rin for the append;
+ * Rin < T, max_count > Rs, T odd or < 2, L or M <= 0, or 256 M / L + T > 2^24 (the inputs one block walks through) for the
+ * outputs; more than 65535 segments.
+ * ---------------------------------------------------------------------- */
+int cer_resample_stream_append(const int16_t *packed, int packed_frames, int channels, const int32_t *segments,
+                               int num_segments, int max_count, int history, double *in_ring, int S, int Rin, void *stream);
+int cer_resample_stream_outputs(const double *in_ring, int S, int Rin, const int32_t *segments, int num_segments,
+                                int max_count, const double *taps, int L, int M, int T, double *out_ring, int Rs, void *stream);
+int cer_logmel_stream_rows_f64(const double *ring, int S, int Rs, const int32_t *rows, int num_rows, const double *mel_matrix,
+                               float log_offset, float *logmel_ring, int Rm, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
