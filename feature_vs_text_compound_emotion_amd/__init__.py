@@ -15,4 +15,10 @@ def __getattr__(name):
     if name == "LogMelStream":
         from . import audio_stream
         return audio_stream.LogMelStream
+    if name == "FrameStream":
+        from . import frames
+        return frames.FrameStream
+    if name == "AVStream":
+        from . import live
+        return live.AVStream
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

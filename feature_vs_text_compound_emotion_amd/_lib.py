@@ -159,6 +159,9 @@ _SIGNATURES = {
     "cer_frames_band_rows": (c_int, []),
     "cer_frames_transform": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int,
                                      c_int, c_float, c_float, _P, _P, _P]),
+    "cer_frames_stream_append": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P,
+                                         c_int, c_int, _P, c_int, c_int, _P]),
+    "cer_frames_stream_gather": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_float, c_float, _P, _P]),
 }
 
 _lib = None

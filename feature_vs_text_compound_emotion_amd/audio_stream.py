@@ -159,8 +159,8 @@ class LogMelStream:
     With the model streams: ``examples.transpose(1, 2)`` is the packed [M, 64, 96] view ``LFANStream.push_ragged`` takes
     under ``logmel`` (with ``example_counts`` as its counts), and ``model.spatial["audio"](examples)`` gives the 128-d rows for
     ``push_features_ragged`` under ``vggish``.  Example e belongs to video frame e and needs audio up to 0.975 s after that
-    frame's time (the reference's alignment, not a property of this class): the caller holds video frames back until
-    ``examples_emitted`` has reached them.  Buffering video is not done here."""
+    frame's time (the reference's alignment, not a property of this class): video frames have to wait until
+    ``examples_emitted`` has reached them.  Buffering video is not done here; ``live.AVStream`` holds the frames and pairs them."""
 
     def __init__(self, streams, hop_sec, window_sec=0.96, max_samples=4096, device="cuda", sample_rate=SAMPLE_RATE, channels=1,
                  resample=None):
@@ -287,8 +287,8 @@ class LogMelStream:
             self.samples_seen[s], self.resampled[s], self.rows_done[s], self.examples_emitted[s] = f, n, r, e
         return out, emitted
 
-    @torch.no_grad()
-    def push(self, pcm_int16, counts):
+    def check_push(self, pcm_int16, counts):
+        """Everything ``push`` refuses, without a launch or a change of state.  Returns (pcm as a tensor, counts as ints)."""
         pcm = torch.as_tensor(pcm_int16)
         if self.resample is not None:
             dims = (1, 2) if self.channels == 1 else (2,)
@@ -309,6 +309,19 @@ class LogMelStream:
                 raise ValueError(f"counts: stream {s} brings {c} samples, outside 0 .. max_samples = {self.max_samples}")
         if pcm.shape[0] != sum(counts):
             raise ValueError(f"pcm: {pcm.shape[0]} samples for counts that sum to {sum(counts)}")
+        return pcm, counts
+
+    def examples_after(self, s, count):
+        """``examples_emitted[s]`` as it will stand after a push that brings stream ``s`` ``count`` samples: host ints only."""
+        if self.resample is None:
+            return schedule(self.samples_seen[s], self.rows_done[s], self.examples_emitted[s], count, self.win,
+                            self.hop_frames)[0][2]
+        return resampled_step((self.samples_seen[s], self.resampled[s], self.rows_done[s], self.examples_emitted[s]), count, 0,
+                              self.L, self.M, self.T, self.win, self.hop_frames)[0][3]
+
+    @torch.no_grad()
+    def push(self, pcm_int16, counts):
+        pcm, counts = self.check_push(pcm_int16, counts)
         if not sum(counts):
             return self._empty(), [0] * self.streams
         offsets, at = [], 0

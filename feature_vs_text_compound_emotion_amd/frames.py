@@ -116,3 +116,145 @@ class FrameTransform:
                                            ptr(flat_out[s:e]), ptr(flat_u8[s:e]) if return_u8 else None,
                                            current_stream()), "cer_frames_transform")
         return (out, u8) if return_u8 else out
+
+
+def hold_ring(hold, max_new):
+    """Slots of a ring in which up to ``hold`` rows wait while a push adds up to ``max_new``: the power of two >= their sum."""
+    r = 1
+    while r < hold + max_new:
+        r *= 2
+    return r
+
+
+class FrameStream:
+    """``FrameTransform(size, crop, train=False)`` for ``streams`` live cameras, a few raw frames at a time; the video
+    counterpart of ``LogMelStream``.
+
+      push(frames_u8 [M, H, W, 3], counts)  stream s brings ``counts[s]`` (0 .. max_new) new frames, packed stream-major in
+                                            ascending stream order, each stream's in time order.  H and W may differ from push
+                                            to push (the ring holds crops; coefficient tables are cached per geometry).
+                                            Returns nothing: the frames wait.
+      take(pairs)                           pairs = (stream, frame number) per row -> float32 [M, 3, crop, crop], the bits
+                                            ``FrameTransform`` gives those frames.  A stream's frames up to the largest one
+                                            taken are released; the others go on waiting.
+      reset(streams=None)                   forget those streams.
+      frames_seen, frames_taken             host lists, one int per stream; ``held`` their difference.
+
+    State (csrc/frames_stream.hip): one uint8 ring [S, Rf, crop, crop, 3] on the device that holds the resized, cropped and
+    flipped bytes, Rf = ``hold_ring(hold, max_new)``, and the two host ints per stream.  A push uploads one row table and runs
+    one launch, a take one more of each, whatever the number of streams.  The crop is GroupCenterCrop's offset for every stream
+    unless ``crop_xyf`` [S, 3] = (x1, y1, flip) per stream says otherwise.
+
+    A push that would leave more than ``hold`` untaken frames in a stream, bad counts, and a tensor that is not uint8 RGB on
+    the GPU raise ValueError before any launch and leave the state as it was."""
+
+    def __init__(self, streams, size=48, crop=40, hold=64, max_new=32, mean=0.5, std=0.5, device="cuda", crop_xyf=None):
+        for name, v in (("streams", streams), ("size", size), ("crop", crop), ("hold", hold), ("max_new", max_new)):
+            if isinstance(v, bool) or int(v) != v or v < 1:
+                raise ValueError(f"{name} = {v!r}: must be an integer >= 1")
+        if crop > size:
+            raise ValueError(f"crop = {crop} exceeds size = {size}")
+        if float(std) == 0.0:
+            raise ValueError("std = 0")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"FrameStream runs on the HIP kernels only (no CPU fallback), got device {device!r}")
+        self.streams, self.size, self.crop, self.hold, self.max_new = int(streams), int(size), int(crop), int(hold), int(max_new)
+        self.ring_frames = hold_ring(self.hold, self.max_new)
+        self._xf = FrameTransform(self.size, self.crop, train=False, mean=mean, std=std)
+        if crop_xyf is None:
+            crop_xyf = self._xf.draw(self.streams)
+        crop_xyf = np.ascontiguousarray(crop_xyf, dtype=np.int32)
+        if crop_xyf.shape != (self.streams, 3):
+            raise ValueError(f"crop_xyf: expected one (x1, y1, flip) per stream [{self.streams}, 3], got {crop_xyf.shape}")
+        if (crop_xyf[:, :2] < 0).any() or (crop_xyf[:, :2] + self.crop > self.size).any():
+            raise ValueError("crop_xyf: crop offset outside the resized image")
+        self.crop_xyf = crop_xyf
+        self.frames_seen = [0] * self.streams
+        self.frames_taken = [0] * self.streams
+        self._base = [0] * self.streams   # ring position of a stream's frame 0
+        self.ring = self._cx = None       # allocated by the first push that launches
+
+    @property
+    def held(self):
+        return [n - t for n, t in zip(self.frames_seen, self.frames_taken)]
+
+    def _indices(self, streams):
+        idx = list(range(self.streams)) if streams is None else [int(s) for s in streams]
+        for s in idx:
+            if not 0 <= s < self.streams:
+                raise IndexError(f"stream {s} of {self.streams}")
+        return idx
+
+    def reset(self, streams=None):
+        """Forget ``streams`` (indices; None = all).  Only host ints change: no slot is read that was not written since."""
+        for s in self._indices(streams):
+            self.frames_seen[s] = self.frames_taken[s] = 0
+
+    def check_push(self, frames_u8, counts):
+        """Everything ``push`` refuses, without a launch or a change of state.  Returns the counts as ints."""
+        try:
+            counts = [int(c) for c in counts]
+        except TypeError:
+            raise ValueError(f"counts: expected a sequence of {self.streams} ints, got {type(counts).__name__}") from None
+        if len(counts) != self.streams:
+            raise ValueError(f"counts: expected one count per stream ({self.streams}), got {len(counts)}")
+        for s, c in enumerate(counts):
+            if not 0 <= c <= self.max_new:
+                raise ValueError(f"counts: stream {s} brings {c} frames, outside 0 .. max_new = {self.max_new}")
+            if self.held[s] + c > self.hold:
+                raise ValueError(f"stream {s}: {self.held[s]} frames wait and {c} more exceed hold = {self.hold}; take some first")
+        f = frames_u8
+        if not (torch.is_tensor(f) and f.is_cuda and f.dtype == torch.uint8 and f.dim() == 4 and f.shape[3] == 3):
+            raise ValueError("frames: expected raw RGB frames as a uint8 GPU tensor [M, H, W, 3] (there is no CPU fallback), got "
+                             f"{(f.dtype, f.device, tuple(f.shape)) if torch.is_tensor(f) else type(f)}")
+        if f.shape[0] != sum(counts):
+            raise ValueError(f"frames: {f.shape[0]} frames for counts that sum to {sum(counts)}")
+        if f.shape[0] > 65535:
+            raise ValueError(f"frames: {f.shape[0]} frames in one push exceed 65535")
+        if f.shape[0] and (f.shape[1] < 1 or f.shape[2] < 1):
+            raise ValueError(f"frames: empty images {tuple(f.shape)}")
+        return counts
+
+    @torch.no_grad()
+    def push(self, frames_u8, counts):
+        from . import ops
+        counts = self.check_push(frames_u8, counts)
+        if not sum(counts):
+            return
+        frames = frames_u8.contiguous()
+        _, h, w, _ = frames.shape
+        tables, _, _, span = self._xf._get_tables(h, w, frames.device)
+        if self.ring is None:
+            self.ring = torch.zeros((self.streams, self.ring_frames, self.crop, self.crop, 3), device=self.device,
+                                    dtype=torch.uint8)
+            self._cx = torch.from_numpy(self.crop_xyf).to(self.device)
+        first = [b + n for b, n in zip(self._base, self.frames_seen)]
+        row_stream, row_pos = ops.stream_row_table(first, counts, self.device)
+        ops.frames_stream_append(frames, tables, span, self.size, self._cx, row_stream, row_pos, max(counts), self.ring)
+        self.frames_seen = [n + c for n, c in zip(self.frames_seen, counts)]
+
+    def check_take(self, pairs):
+        """What ``take`` refuses.  Returns the pairs as ints."""
+        pairs = [(int(s), int(i)) for s, i in pairs]
+        for s, i in pairs:
+            if not 0 <= s < self.streams:
+                raise ValueError(f"take: stream {s} of {self.streams}")
+            if not self.frames_taken[s] <= i < self.frames_seen[s]:
+                raise ValueError(f"take: frame {i} of stream {s} is not held (frames {self.frames_taken[s]} .. "
+                                 f"{self.frames_seen[s] - 1} are)")
+        if len(pairs) > 65535:
+            raise ValueError(f"take: {len(pairs)} frames in one call exceed 65535")
+        return pairs
+
+    @torch.no_grad()
+    def take(self, pairs):
+        from . import ops
+        pairs = self.check_take(pairs)
+        if not pairs:
+            return torch.empty((0, 3, self.crop, self.crop), device=self.device, dtype=torch.float32)
+        row_stream, row_pos = ops.stream_pair_table([(s, self._base[s] + i) for s, i in pairs], self.device)
+        out = ops.frames_stream_gather(self.ring, row_stream, row_pos, self._xf.mean, self._xf.std)
+        for s, i in pairs:
+            self.frames_taken[s] = max(self.frames_taken[s], i + 1)
+        return out

@@ -1,0 +1,263 @@
+"""Live audio-visual sessions: raw camera frames and raw PCM of S independent streams in, logits out.
+
+``AVStream`` owns the three streamed stages and pairs them: a ``FrameStream`` (raw uint8 frames -> the cropped bytes, held on
+the device), a ``LogMelStream`` (PCM at any rate -> VGGish examples, hop 1 / fps) and an ``LFANStream`` or ``CANStream``.  Example
+e belongs to video frame e but is complete only 0.975 s after that frame's time, so frames wait on the device for their
+examples; when the video side lags, examples wait for their frames.  Every stage is bit-identical to its offline counterpart
+and the holds copy bits, so the logits of a stream are the bits ``stream_forward`` gives the offline-prepared clip, under any
+chunking of either side and any number of neighbouring streams.
+
+The pairing rule (``pair_schedule``, a pure function of ints).  A stream has F frames pushed, E examples emitted, P pairs
+emitted.  After every push, frames P .. min(F, E) - 1 are emitted, frame i with example i.  When the stream ends, the audio
+stage brings E to its final n (the reference's count for the padded signal) and frames P .. F - 1 are emitted with example
+min(i, n - 1): later frames repeat the last example and examples >= F are dropped, which is ``use = min(n, L)`` and "repeat the
+last row" of ``MultimodalFeatureExtractor.audio_features``.
+
+State.  Host: the three ints per stream.  Device: the ``FrameStream`` ring [S, Rf, crop, crop, 3] uint8; an example ring
+[S, Re, win * 64] float32; one ring [S, Rf, E_m] float32 per further modality (``bert`` rows that come with the frames and wait
+as long as they do).  The float rings are written with ``ops.tcn_stream_append_rows`` and read with ``ops.gather_rows``: no
+kernel of their own.  Rf = ``hold_ring(hold, max_new)``: at most ``hold`` frames wait when a push brings at most ``max_new``.
+Re = ``hold_ring(lead, examples_per_step(...))``: at most ``lead`` examples wait when a push completes at most
+``examples_per_step`` new ones.  Example e sits in slot e mod Re; a stream's last example stays in its slot until the stream
+is reset.
+
+Examples per step.  A push (or one padding step of the audio stage's ``finish``) adds at most ``max_out`` 16 kHz samples to a
+stream (``max_samples``, or the resampler's ``max_outputs``), hence at most r = max_out // 160 + 1 STFT rows.  Example e
+becomes complete when round(hop e) + win <= rows, so the new ones have round(hop e) in an integer interval of length r, hop e
+in a real interval of length at most r + 1, and there are at most floor((r + 1) / hop) + 1 of them (hop in rows, >= 1).
+"""
+import torch
+
+from . import ops
+from .audio_stream import ROW_HOP, LogMelStream
+from .frames import FrameStream, hold_ring
+from .fusion_heads import CAN
+from .streaming import CANStream, LFANStream
+
+AUDIO_KEYS = ("logmel", "vggish")
+
+
+def pair_schedule(frames, examples, paired, final=None):
+    """The (frame, example) pairs a stream with ``frames`` frames pushed, ``examples`` examples emitted and ``paired`` pairs
+    emitted owes now.  ``final``: the stream has ended with that many examples in all (0: it never received a sample, and
+    its frames are dropped).  Python ints, no GPU."""
+    if final is None:
+        return [(i, i) for i in range(paired, min(frames, examples))]
+    return [(i, min(i, final - 1)) for i in range(paired, frames)] if final > 0 else []
+
+
+def examples_per_step(max_out, hop_frames):
+    """The most examples that ``max_out`` new 16 kHz samples of one stream can complete (derivation in the module text)."""
+    return int((max_out // ROW_HOP + 2) / hop_frames) + 1
+
+
+def check_waiting(frames, examples, paired, new_frames, examples_after, hold, lead):
+    """What ``AVStream.push`` refuses for one stream, as ints: the frames that wait plus the new ones (they count as waiting
+    until the call has paired them) may not exceed ``hold``; the examples still ahead of their frames after the push may not
+    exceed ``lead``.  Returns (frames waiting before pairing, examples waiting after it)."""
+    waiting_frames = frames - paired + new_frames
+    waiting_examples = max(examples_after - (frames + new_frames), 0)
+    if waiting_frames > hold:
+        raise ValueError(f"{frames - paired} frames wait for their audio and {new_frames} more exceed hold = {hold}")
+    if waiting_examples > lead:
+        raise ValueError(f"{waiting_examples} examples would wait for their frames, more than lead = {lead}")
+    return waiting_frames, waiting_examples
+
+
+class AVStream:
+    """An eval-mode LFAN or CAN on ``streams`` live audio-visual streams at ``fps`` frames per second.
+
+      push(video=None, video_counts=None, audio=None, audio_counts=None, extra=None)
+            video [M, H, W, 3] uint8 raw frames, ``video_counts[s]`` (0 .. max_new) of stream s, packed stream-major; audio
+            int16 PCM as ``LogMelStream.push`` takes it with ``audio_counts``; either side may be absent.  ``extra[m]``
+            [M, embedding_dim[m]] float32: the rows of every further modality of the model (``bert``) for the new frames.
+            -> (logits [P, n_cls], counts): every frame that became paired in this call, stream-major, each stream's frames in
+            time order (the row order of ``push_ragged``); counts[s] of them belong to stream s.  Nothing paired: an empty
+            [0, n_cls] and no model launch.
+      finish(streams=None)   the streams have ended: the same pair for their remaining frames (the audio stage's one second of
+            edge padding, the last example repeated, examples past the last frame dropped); those streams are reset.  A stream
+            that received frames but never a sample emits nothing for them.
+      reset(streams=None)    forget those streams.
+      frames_seen, examples_seen, paired   host lists, one int per stream.
+
+    The model's modalities must contain ``video`` and exactly one of ``logmel`` / ``vggish``.  Under ``vggish`` the session runs
+    ``audio_backbone`` (default: the model's ``spatial["audio"]``) on the examples itself, ``encoder_batch`` at a time like
+    the encoders inside the model, so a row's bits do not depend on how many frames a push paired.  The dict handed to the model
+    stream is keyed in the model's own modality order.
+
+    A push that would let more than ``hold`` frames or ``lead`` examples wait, and any argument one of the stages refuses,
+    raises ValueError before any launch and changes no state, the stages' included.  A stream's counts above ``max_new`` in one
+    call reach the model in several pushes, in time order."""
+
+    def __init__(self, model, streams, fps, *, sample_rate=16000, channels=1, resample=None, size=48, crop=40, hold=64, lead=8,
+                 max_new=32, max_samples=4096, encoder_batch=8, audio_backbone=None):
+        cls = CANStream if isinstance(model, CAN) else LFANStream
+        if not isinstance(model, cls._model_class):
+            raise TypeError(f"AVStream needs an LFAN or a CAN (JMT / MT attend over time and are not causal), got "
+                            f"{type(model).__name__}")
+        if model.training:
+            raise RuntimeError("AVStream: the model is in train mode; batch statistics are undefined frame by frame -- call .eval()")
+        mods = list(cls._modalities(model))
+        audio_keys = [m for m in mods if m in AUDIO_KEYS]
+        if "video" not in mods or len(audio_keys) != 1:
+            raise ValueError(f"AVStream needs a model with 'video' and exactly one of {AUDIO_KEYS}, got {mods}")
+        if not fps > 0:
+            raise ValueError(f"fps = {fps!r}: must be positive")
+        if isinstance(lead, bool) or int(lead) != lead or lead < 1:
+            raise ValueError(f"lead = {lead!r}: must be an integer >= 1")
+        self.audio_key = audio_keys[0]
+        self.extra_keys = [m for m in mods if m != "video" and m != self.audio_key]
+        self.audio_backbone = None
+        if self.audio_key == "vggish":
+            spatial = getattr(model, "spatial", {})
+            self.audio_backbone = audio_backbone if audio_backbone is not None else (spatial["audio"] if "audio" in spatial else None)
+            if self.audio_backbone is None:
+                raise ValueError("AVStream: the model takes 'vggish' rows and has no audio backbone of its own: pass audio_backbone=")
+        self.model, self.streams, self.fps, self.hold, self.lead, self.max_new = model, int(streams), fps, int(hold), int(lead), int(max_new)
+        device = next(model.parameters()).device
+        self.frame_stream = FrameStream(streams, size=size, crop=crop, hold=hold, max_new=max_new, device=device)
+        self.audio_stream = LogMelStream(streams, 1.0 / fps, max_samples=max_samples, device=device, sample_rate=sample_rate,
+                                         channels=channels, resample=resample)   # hop_sec: the expression of audio_features
+        self.model_stream = cls(model, streams, max_new=max_new, encoder_batch=encoder_batch)
+        self.device, self.win = device, self.audio_stream.win
+        max_out = max_samples if resample is None else self.audio_stream.max_outputs
+        self.examples_per_step = examples_per_step(max_out, self.audio_stream.hop_frames)
+        self.ring_frames = self.frame_stream.ring_frames
+        self.ring_examples = hold_ring(self.lead, self.examples_per_step)
+        self.extra_dims = {m: self.model_stream.tcn[m].cin for m in self.extra_keys}
+        for m, e in self.extra_dims.items():
+            if e % 4:
+                raise ValueError(f"{m}: embedding dim {e} is not a multiple of 4 (the row gather moves float4)")
+        self.frames_seen, self.examples_seen, self.paired = [0] * self.streams, [0] * self.streams, [0] * self.streams
+        self._exring, self._extra = None, {}   # allocated by the first push that needs them
+
+    # ------------------------------------------------------------------------------------------------ checks (no launch)
+    def _indices(self, streams):
+        return self.frame_stream._indices(streams)
+
+    def _check_extra(self, extra, rows):
+        extra = {} if extra is None else dict(extra)
+        if not rows and not extra:
+            return extra
+        if sorted(extra) != sorted(self.extra_keys):
+            raise ValueError(f"extra: expected rows for {self.extra_keys} next to the new frames, got {sorted(extra)}")
+        for m, x in extra.items():
+            if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+                    and tuple(x.shape) == (rows, self.extra_dims[m])):
+                raise ValueError(f"extra[{m!r}]: expected float32 [{rows}, {self.extra_dims[m]}] on the GPU, one row per new frame, "
+                                 f"got {(x.dtype, x.device, tuple(x.shape)) if torch.is_tensor(x) else type(x)}")
+        return extra
+
+    # ------------------------------------------------------------------------------------------------ the holds
+    def _alloc(self):
+        if self._exring is None:
+            self._exring = torch.zeros((self.streams, self.ring_examples, self.win * 64), device=self.device, dtype=torch.float32)
+            self._extra = {m: torch.zeros((self.streams, self.ring_frames, e), device=self.device, dtype=torch.float32)
+                           for m, e in self.extra_dims.items()}
+
+    def _hold_rows(self, rows, ring, positions, counts):
+        row_stream, row_pos = ops.stream_row_table(positions, counts, self.device)
+        ops.tcn_stream_append_rows(rows.contiguous(), ring, row_stream, row_pos, max(counts))
+
+    def _held_rows(self, ring, pairs):
+        """ring [S, R, C], pairs (stream, position) -> [len(pairs), C]."""
+        r = ring.shape[1]
+        index = torch.tensor([s * r + (p & (r - 1)) for s, p in pairs], dtype=torch.int64, device=self.device)
+        return ops.gather_rows(ring.view(-1, ring.shape[2]), index)
+
+    def _emit(self, owed, example_rows):
+        """owed[s]: the (frame, example) pairs of stream s, in time order; ``example_rows``: (stream, example) list ->
+        [n, win * 64].  Takes the frames, runs the model ``max_new`` frames of a stream at a time -> (logits, counts)."""
+        counts = [len(p) for p in owed]
+        parts, at = [[] for _ in owed], [0] * self.streams
+        while any(a < c for a, c in zip(at, counts)):
+            step = [min(self.max_new, c - a) for a, c in zip(at, counts)]
+            rows = [(s, f, e) for s in range(self.streams) for f, e in owed[s][at[s]:at[s] + step[s]]]
+            X = {}
+            for m in self.model_stream.modalities:   # the model's own order
+                if m == "video":
+                    X[m] = self.frame_stream.take([(s, f) for s, f, _ in rows])
+                elif m == self.audio_key:
+                    ex = example_rows([(s, e) for s, _, e in rows]).view(len(rows), self.win, 64)
+                    X[m] = ex.transpose(1, 2) if m == "logmel" else self.model_stream._in_groups(self.audio_backbone, ex)
+                else:
+                    X[m] = self._held_rows(self._extra[m], [(s, f) for s, f, _ in rows])
+            logits, k = self.model_stream.push_ragged(X, step), 0
+            for s, c in enumerate(step):
+                if c:
+                    parts[s].append(logits[k:k + c])
+                    k += c
+                at[s] += c
+        for s, c in enumerate(counts):
+            self.paired[s] += c
+        flat = [p for per in parts for p in per]
+        return (torch.cat(flat) if len(flat) > 1 else flat[0]) if flat else self.model_stream._nothing(), counts
+
+    # ------------------------------------------------------------------------------------------------ the session
+    @torch.no_grad()
+    def push(self, video=None, video_counts=None, audio=None, audio_counts=None, extra=None):
+        zeros = [0] * self.streams
+        if (video is None) != (video_counts is None) or (audio is None) != (audio_counts is None):
+            raise ValueError("push: video and video_counts come together, and so do audio and audio_counts")
+        self.model_stream._check_keys(dict.fromkeys(self.model_stream.modalities))   # the model may have left eval mode
+        vcounts = self.frame_stream.check_push(video, video_counts) if video is not None else zeros
+        extra = self._check_extra(extra, sum(vcounts))
+        pcm, acounts = self.audio_stream.check_push(audio, audio_counts) if audio is not None else (None, zeros)
+        for s in range(self.streams):
+            after = self.audio_stream.examples_after(s, acounts[s]) if acounts[s] else self.examples_seen[s]
+            try:
+                check_waiting(self.frames_seen[s], self.examples_seen[s], self.paired[s], vcounts[s], after, self.hold, self.lead)
+            except ValueError as err:
+                raise ValueError(f"stream {s}: {err}") from None
+        # nothing below refuses
+        self._alloc()
+        if sum(acounts):
+            examples, got = self.audio_stream.push(pcm, acounts)
+            if sum(got):
+                self._hold_rows(examples.view(-1, self.win * 64), self._exring, self.examples_seen, got)
+                self.examples_seen = [e + g for e, g in zip(self.examples_seen, got)]
+        if sum(vcounts):
+            self.frame_stream.push(video, vcounts)
+            for m in self.extra_keys:
+                self._hold_rows(extra[m], self._extra[m], self.frames_seen, vcounts)
+            self.frames_seen = [f + c for f, c in zip(self.frames_seen, vcounts)]
+        owed = [pair_schedule(f, e, p) for f, e, p in zip(self.frames_seen, self.examples_seen, self.paired)]
+        return self._emit(owed, lambda pairs: self._held_rows(self._exring, pairs))
+
+    @torch.no_grad()
+    def finish(self, streams=None):
+        idx = sorted(set(self._indices(streams)))
+        self.model_stream._check_keys(dict.fromkeys(self.model_stream.modalities))
+        self._alloc()
+        before = list(self.examples_seen)
+        last, got = self.audio_stream.finish(idx)   # every remaining example of those streams, stream-major
+        first, at = {}, 0
+        for s in idx:
+            first[s], at = at, at + got[s]
+            self.examples_seen[s] += got[s]
+        owed = [pair_schedule(self.frames_seen[s], self.examples_seen[s], self.paired[s], final=self.examples_seen[s])
+                if s in first else [] for s in range(self.streams)]
+        re, tail = self.ring_examples, last.view(-1, self.win * 64)
+
+        def example_rows(pairs):
+            # an example emitted before the end sits in its ring slot (only the last one can be asked for: the earlier ones
+            # were paired when they came, or belong to frames that never came); one the end produced is a row of ``last``
+            index = [s * re + (e & (re - 1)) if e < before[s] else self.streams * re + first[s] + e - before[s] for s, e in pairs]
+            src = self._exring.view(-1, self.win * 64)
+            if any(i < self.streams * re for i in index):
+                src = torch.cat([src, tail])
+            else:
+                src, index = tail, [i - self.streams * re for i in index]
+            return ops.gather_rows(src.contiguous(), torch.tensor(index, dtype=torch.int64, device=self.device))
+
+        out = self._emit(owed, example_rows)
+        self.reset(idx)
+        return out
+
+    def reset(self, streams=None):
+        idx = self._indices(streams)
+        self.frame_stream.reset(idx)
+        self.audio_stream.reset(idx)
+        self.model_stream.reset(idx)
+        for s in idx:
+            self.frames_seen[s] = self.examples_seen[s] = self.paired[s] = 0

@@ -1968,3 +1968,73 @@ def logmel_stream_rows_f64(ring, rows, mel_matrix_f64, logmel_ring, log_offset=0
                                                  ptr(logmel_ring), rm, current_stream()), "cer_logmel_stream_rows_f64")
     if STREAM_TRACE is not None:
         STREAM_TRACE.append(("logmel_rows_f64", 0))
+
+
+# ------------------------------------------------------------------ streaming frame transform (csrc/frames_stream.hip)
+def stream_pair_table(pairs, device):
+    """The row table of explicit rows: ``pairs`` = (stream, position) per row, in the caller's order, Python ints of any size
+    -> (row_stream, row_pos) like ``stream_row_table``: int32 [M] each, positions modulo 2^30, one fresh upload."""
+    pairs = [(int(s), int(p)) for s, p in pairs]
+    for s, p in pairs:
+        if p < 0 or not -(1 << 31) <= s < (1 << 31):
+            raise ValueError(f"stream_pair_table: row (stream {s}, position {p}): a position must be >= 0, a stream an int32")
+    table = torch.tensor([[s for s, _ in pairs], [p % ROW_POS_MOD for _, p in pairs]], dtype=torch.int32,
+                         device=device).view(2, len(pairs))
+    return table[0], table[1]
+
+
+def _u8_ring(t, crop=None):
+    """The frame ring [S, Rf, crop, crop, 3]: contiguous uint8 on the GPU.  Returns (S, Rf, crop)."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 5
+            and t.shape[2] == t.shape[3] and t.shape[4] == 3 and (crop is None or t.shape[2] == crop)):
+        raise ValueError(f"u8ring: expected a contiguous uint8 [S, Rf, {crop or 'crop'}, {crop or 'crop'}, 3] GPU tensor, got "
+                         f"{(t.dtype, t.device, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
+    return t.shape[0], t.shape[1], t.shape[2]
+
+
+def _i32_table(t, name, shape, like):
+    if not (torch.is_tensor(t) and t.is_cuda and t.device == like.device and t.dtype == torch.int32 and t.is_contiguous()
+            and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{name}: expected a contiguous int32 {list(shape)} tensor on the GPU of the ring ({like.device}), got "
+                         f"{(t.dtype, t.device, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
+
+
+def frames_stream_append(frames, tables, span, size, crop_xyf, row_stream, row_pos, max_count, u8ring):
+    """GroupScale(size) -> crop -> flip of the raw frames ``frames`` [n, H, W, 3] uint8 into the ring ``u8ring``
+    [S, Rf, crop, crop, 3]: row m of the row table (``stream_row_table``) is frame m and lands in slot
+    (row_stream[m], row_pos[m] % Rf).  ``tables``: (hbounds, hcoef, vbounds, vcoef) of ``frames.resample_tables`` for
+    (W -> size, H -> size) as int32 GPU tensors; ``span``: the most input rows one band of output rows needs;
+    ``crop_xyf`` int32 [S, 3]: (x1, y1, flip) per stream; ``max_count``: the most rows any one stream has in the table.
+    The bytes are ``return_u8`` of ``FrameTransform`` for the same frame and crop entry."""
+    s, rf, crop = _u8_ring(u8ring)
+    if not (torch.is_tensor(frames) and frames.is_cuda and frames.device == u8ring.device and frames.dtype == torch.uint8
+            and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
+        raise ValueError("frames: expected a contiguous uint8 [n >= 1, H, W, 3] tensor on the GPU of the ring, got "
+                         f"{(frames.dtype, frames.device, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
+    n, h, w, _ = frames.shape
+    m = _row_table(row_stream, row_pos, u8ring)
+    hb, hk, vb, vk = tables
+    size = int(size)
+    for t, name, rows in ((hb, "hbounds", 2), (vb, "vbounds", 2), (hk, "hcoef", None), (vk, "vcoef", None)):
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise ValueError(f"{name}: expected an int32 [size, k] GPU tensor")
+        _i32_table(t, name, (size, rows if rows is not None else t.shape[1]), u8ring)
+    _i32_table(crop_xyf, "crop_xyf", (s, 3), u8ring)
+    check(_lib.load().cer_frames_stream_append(ptr(frames), n, h, w, ptr(hb), ptr(hk), hk.shape[1], ptr(vb), ptr(vk), vk.shape[1],
+                                               size, crop, ptr(crop_xyf), int(span), ptr(row_stream), ptr(row_pos), m,
+                                               int(max_count), ptr(u8ring), s, rf, current_stream()), "cer_frames_stream_append")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("frames_append", 0))
+
+
+def frames_stream_gather(u8ring, row_stream, row_pos, mean=0.5, std=0.5):
+    """out[m] = ((u8ring[row_stream[m], row_pos[m] % Rf] / 255) - mean) / std as float32 [M, 3, crop, crop]: the tensor
+    ``FrameTransform`` gives the same frames."""
+    s, rf, crop = _u8_ring(u8ring)
+    m = _row_table(row_stream, row_pos, u8ring)
+    out = torch.empty((m, 3, crop, crop), device=u8ring.device, dtype=torch.float32)
+    check(_lib.load().cer_frames_stream_gather(ptr(u8ring), s, rf, crop, ptr(row_stream), ptr(row_pos), m, float(mean), float(std),
+                                               ptr(out), current_stream()), "cer_frames_stream_gather")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("frames_gather", 0))
+    return out

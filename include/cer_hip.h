@@ -775,6 +775,39 @@ int cer_resample_stream_outputs(const double *in_ring, int S, int Rin, const int
 int cer_logmel_stream_rows_f64(const double *ring, int S, int Rs, const int32_t *rows, int num_rows, const double *mel_matrix,
                                float log_offset, float *logmel_ring, int Rm, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Streaming frame transform: cer_frames_transform on raw camera frames of S independent streams.
+ *
+ * State: one ring u8ring [S][Rf][crop][crop][3] uint8, the GroupScale -> crop -> flip result of each stream's last Rf
+ * frames, channels last; Rf is a power of two up to 2^30.  The ring holds the bytes (return_u8 of cer_frames_transform), not
+ * the floats: the float is a pure function of the byte.  The device keeps no counters.  Rows are named as for the streaming
+ * TCN: row_stream[m] is the stream of row m, row_pos[m] that frame's number in its stream, unwrapped, modulo 2^30; its
+ * slot is row_pos[m] & (Rf - 1).
+ *
+ * cer_frames_stream_append: frames [n_frames][H][W][3] uint8 packed; row m of the table is packed frame m (frame
+ *   n_frames - 1 for m >= n_frames).  The coefficient tables, size, crop and max_band_rows are those of
+ *   cer_frames_transform; crop_xyf is [S][3] = (x1, y1, flip), one entry per STREAM.  The kernel is the one
+ *   cer_frames_transform launches (csrc/frames_kernel.h), so
+ *     u8ring[row_stream[m]][row_pos[m] & (Rf - 1)] = out_u8 of cer_frames_transform for that frame and that crop entry.
+ *   max_count is the largest number of rows any one stream has in the table (the entry cannot read it).
+ * cer_frames_stream_gather: out[m][c][y][x] = ((float)v / 255.0f - mean) / stdv for the byte
+ *   v = u8ring[row_stream[m]][row_pos[m] & (Rf - 1)][y][x][c]; out is [num_rows][3][crop][crop] fp32, the expression
+ *   cer_frames_transform applies to the same byte.
+ *
+ * The tables are never trusted with an address: a stream index is clamped into [0, S), a position is masked with Rf - 1,
+ * the packed frame index is bounded by n_frames, and x1, y1 are clamped into [0, size - crop].  A wrong table gives wrong
+ * numbers, never an access outside the ring or the packed input.
+ * Refused before any launch, with a cer_last_error() text that begins with the entry's name: a null pointer; a count or a
+ * dimension below 1; Rf not a power of two up to 2^30; crop > size; max_count > Rf; more than 65535 rows or frames per call
+ * (CER_ERR_INVALID_ARG); a band of input rows that needs more than the 160 KiB LDS (CER_ERR_UNSUPPORTED).
+ * ---------------------------------------------------------------------- */
+int cer_frames_stream_append(const uint8_t *frames, int n_frames, int H, int W, const int32_t *hbounds, const int32_t *hcoef,
+                             int hksize, const int32_t *vbounds, const int32_t *vcoef, int vksize, int size, int crop,
+                             const int32_t *crop_xyf, int max_band_rows, const int32_t *row_stream, const int32_t *row_pos,
+                             int num_rows, int max_count, uint8_t *u8ring, int S, int Rf, void *stream);
+int cer_frames_stream_gather(const uint8_t *u8ring, int S, int Rf, int crop, const int32_t *row_stream, const int32_t *row_pos,
+                             int num_rows, float mean, float stdv, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
