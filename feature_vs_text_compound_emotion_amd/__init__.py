@@ -21,4 +21,7 @@ def __getattr__(name):
     if name == "AVStream":
         from . import live
         return live.AVStream
+    if name == "DecisionStream":
+        from . import decisions
+        return decisions.DecisionStream
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -47,6 +47,11 @@ class TcnStreamRowsDesc(Structure):
                                        "out_R")] + [("slope", c_float)]
 
 
+class DecisionStreamDesc(Structure):
+    """cer_decision_stream_desc (see include/cer_hip.h)."""
+    _fields_ = [(n, c_int32) for n in ("S", "C", "M", "max_count", "W", "R", "drop_last", "classify")]
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "cer_last_error": (c_char_p, []),
@@ -162,6 +167,8 @@ _SIGNATURES = {
     "cer_frames_stream_append": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P,
                                          c_int, c_int, _P, c_int, c_int, _P]),
     "cer_frames_stream_gather": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_float, c_float, _P, _P]),
+    "cer_decision_stream_push": (c_int, [POINTER(DecisionStreamDesc), _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cer_decision_stream_read": (c_int, [POINTER(DecisionStreamDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

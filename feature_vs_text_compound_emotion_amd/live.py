@@ -79,6 +79,12 @@ class AVStream:
             that received frames but never a sample emits nothing for them.
       reset(streams=None)    forget those streams.
       frames_seen, examples_seen, paired   host lists, one int per stream.
+      decisions              with ``decisions=`` (a dict of ``DecisionStream`` keyword arguments, ``{}`` for the defaults): a
+            ``DecisionStream`` the session owns and feeds every logit row it emits, in ``push`` and in ``finish``;
+            ``av.decisions.decide()`` gives the running video-level decisions.  ``finish`` leaves a stream's decisions
+            standing, to be read; they are forgotten by ``reset``, or when that stream emits its next row.  Its ``max_new``
+            defaults to the session's and may not be smaller, so it refuses nothing the session emits: what it does refuse
+            (its own arguments) it refuses here, at construction.
 
     The model's modalities must contain ``video`` and exactly one of ``logmel`` / ``vggish``.  Under ``vggish`` the session runs
     ``audio_backbone`` (default: the model's ``spatial["audio"]``) on the examples itself, ``encoder_batch`` at a time like
@@ -90,7 +96,7 @@ class AVStream:
     call reach the model in several pushes, in time order."""
 
     def __init__(self, model, streams, fps, *, sample_rate=16000, channels=1, resample=None, size=48, crop=40, hold=64, lead=8,
-                 max_new=32, max_samples=4096, encoder_batch=8, audio_backbone=None):
+                 max_new=32, max_samples=4096, encoder_batch=8, audio_backbone=None, decisions=None):
         cls = CANStream if isinstance(model, CAN) else LFANStream
         if not isinstance(model, cls._model_class):
             raise TypeError(f"AVStream needs an LFAN or a CAN (JMT / MT attend over time and are not causal), got "
@@ -130,6 +136,16 @@ class AVStream:
                 raise ValueError(f"{m}: embedding dim {e} is not a multiple of 4 (the row gather moves float4)")
         self.frames_seen, self.examples_seen, self.paired = [0] * self.streams, [0] * self.streams, [0] * self.streams
         self._exring, self._extra = None, {}   # allocated by the first push that needs them
+        self.decisions, self._ended = None, set()   # _ended: finished streams whose decisions still stand
+        if decisions is not None:
+            from .decisions import DecisionStream
+            kw = dict(decisions)
+            if "task" in kw or "device" in kw:
+                raise ValueError("decisions: the task and the device are the model's")
+            kw.setdefault("max_new", self.max_new)
+            if int(kw["max_new"]) < self.max_new:
+                raise ValueError(f"decisions: max_new = {kw['max_new']} is below the session's {self.max_new}")
+            self.decisions = DecisionStream(self.model_stream._n_out(), self.streams, task=model.task, device=device, **kw)
 
     # ------------------------------------------------------------------------------------------------ checks (no launch)
     def _indices(self, streams):
@@ -183,6 +199,11 @@ class AVStream:
                 else:
                     X[m] = self._held_rows(self._extra[m], [(s, f) for s, f, _ in rows])
             logits, k = self.model_stream.push_ragged(X, step), 0
+            if self.decisions is not None:
+                stale = [s for s in self._ended if step[s]]
+                self.decisions.reset(stale)
+                self._ended.difference_update(stale)
+                self.decisions.push_ragged(logits, step)
             for s, c in enumerate(step):
                 if c:
                     parts[s].append(logits[k:k + c])
@@ -251,11 +272,18 @@ class AVStream:
             return ops.gather_rows(src.contiguous(), torch.tensor(index, dtype=torch.int64, device=self.device))
 
         out = self._emit(owed, example_rows)
-        self.reset(idx)
+        self._reset_stages(idx)
+        self._ended.update(idx)
         return out
 
     def reset(self, streams=None):
         idx = self._indices(streams)
+        self._reset_stages(idx)
+        if self.decisions is not None:
+            self.decisions.reset(idx)
+            self._ended.difference_update(idx)
+
+    def _reset_stages(self, idx):
         self.frame_stream.reset(idx)
         self.audio_stream.reset(idx)
         self.model_stream.reset(idx)

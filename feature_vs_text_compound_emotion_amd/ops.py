@@ -1726,6 +1726,28 @@ def stream_row_table(positions, counts, device):
     return table[0], table[1]
 
 
+DECISION_FIELDS = 6   # stream, count, offset, position, frames (low word), frames (high word)
+
+
+def decision_segment_table(segments, device):
+    """The table of one ``decision_stream_push`` (or ``decision_stream_read``): ``segments`` = (stream, count, offset into the
+    packed rows, ring position, frames since reset) per entry, Python ints -> int32 [6, A] on ``device``: the first three as
+    they are, the position modulo 2^30, the frames as a 64-bit value split into its low and high 32-bit words (each stored as
+    the int32 with those bits).  One fresh tensor per call, like ``stream_row_table``."""
+    cols = []
+    for s, count, off, pos, frames in segments:
+        s, count, off, pos, frames = int(s), int(count), int(off), int(pos), int(frames)
+        if count < 0 or pos < 0 or not 0 <= frames < (1 << 63) or not 0 <= off < (1 << 31) or not -(1 << 31) <= s < (1 << 31) \
+                or count >= (1 << 31):
+            raise ValueError(f"decision_segment_table: segment of stream {s}: count {count}, offset {off}, position {pos}, "
+                             f"frames {frames}")
+        lo, hi = frames & 0xffffffff, frames >> 32
+        cols.append((s, count, off, pos % ROW_POS_MOD, lo - (1 << 32) if lo >= (1 << 31) else lo, hi))
+    if not cols:
+        raise ValueError("decision_segment_table: no segment")
+    return torch.tensor([[c[f] for c in cols] for f in range(DECISION_FIELDS)], dtype=torch.int32, device=device)
+
+
 def _row_table(row_stream, row_pos, ring):
     """Both tables int32, contiguous, one-dimensional, on the ring's device and of one length M >= 1.  Returns M."""
     for t, n in ((row_stream, "row_stream"), (row_pos, "row_pos")):
@@ -2038,3 +2060,90 @@ def frames_stream_gather(u8ring, row_stream, row_pos, mean=0.5, std=0.5):
     if STREAM_TRACE is not None:
         STREAM_TRACE.append(("frames_gather", 0))
     return out
+
+
+# ------------------------------------------------------------------ running decisions (csrc/decision_stream.hip)
+DECISION_NEVER = (1 << 63) - 1   # ``first`` of a class no frame has been predicted as
+
+
+def decision_stream_state(streams, n_out, *, window=None, max_new=32, classify=True, device="cuda"):
+    """The device state of ``streams`` reset streams as a dict.  Whole-stream (``window`` None): ``slog`` [S, C] float64 and,
+    with ``classify``, ``votes`` / ``first`` [S, C] int64 and ``sprob`` [S, C] float64.  Window: ``zring`` [S, R, C] float32, R
+    the power of two >= window + max_new."""
+    if window is None:
+        state = {"slog": torch.zeros((streams, n_out), dtype=torch.float64, device=device)}
+        if classify:
+            state["votes"] = torch.zeros((streams, n_out), dtype=torch.int64, device=device)
+            state["first"] = torch.full((streams, n_out), DECISION_NEVER, dtype=torch.int64, device=device)
+            state["sprob"] = torch.zeros((streams, n_out), dtype=torch.float64, device=device)
+        return state
+    r = 1
+    while r < int(window) + int(max_new):
+        r *= 2
+    return {"zring": torch.zeros((streams, r, n_out), dtype=torch.float32, device=device)}
+
+
+def _decision_state(state, window, classify):
+    """Check the state tensors of the mode.  Returns (descriptor without M / max_count, the five pointers, device)."""
+    def want(name, dtype, shape=None):
+        t = state.get(name)
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+                and (shape is None or tuple(t.shape) == tuple(shape))):
+            raise ValueError(f"{name}: expected a contiguous {dtype} GPU tensor" + (f" of shape {tuple(shape)}" if shape else "")
+                             + f", got {(t.dtype, t.device, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
+        return t
+    d = _lib.DecisionStreamDesc(classify=int(bool(classify)))
+    if window is None:
+        slog = want("slog", torch.float64)
+        if slog.dim() != 2:
+            raise ValueError(f"slog: expected [S, C], got {tuple(slog.shape)}")
+        d.S, d.C = slog.shape
+        names = ("votes", "first", "sprob") if classify else ()
+        ts = {n: want(n, torch.float64 if n == "sprob" else torch.int64, slog.shape) for n in names}
+        if any(t.device != slog.device for t in ts.values()):
+            raise ValueError("the state tensors sit on different devices")
+        return d, (_addr(ts.get("votes")), _addr(ts.get("first")), _addr(slog), _addr(ts.get("sprob")), None), slog.device
+    window = int(window)
+    if window < 1:
+        raise ValueError(f"window = {window}: must be >= 1, or None for the whole stream")
+    d.S, d.R, d.C = _ring(want("zring", torch.float32), "zring")
+    d.W = window
+    return d, (None, None, None, None, _addr(state["zring"])), state["zring"].device
+
+
+def decision_stream_push(rows, segments, max_count, state, *, window=None, drop_last=False, classify=True, track=False):
+    """Append the packed rows ``rows`` [M, C] of one push to the streams' state as the table ``segments``
+    (``decision_segment_table``) says; ``max_count``: the largest count in it.  ``track``: also return (decisions [M, 3] int32
+    or None without ``classify``, means [M, 2, C]) as they stand after each new row."""
+    d, state_ptrs, dev = _decision_state(state, window, classify)
+    _dev_f32(rows, "rows")
+    if not torch.is_tensor(rows) or rows.dim() != 2 or rows.shape[1] != d.C or rows.shape[0] < 1 or rows.device != dev:
+        raise ValueError(f"rows: expected [M >= 1, {d.C}] on {dev}, got "
+                         f"{(tuple(rows.shape), rows.device) if torch.is_tensor(rows) else type(rows)}")
+    a = _stream_table(segments, "segments", DECISION_FIELDS, rows)
+    d.M, d.max_count, d.drop_last = rows.shape[0], int(max_count), int(bool(drop_last))
+    dec = torch.empty((d.M, 3), dtype=torch.int32, device=dev) if track and classify else None
+    means = torch.empty((d.M, 2, d.C), dtype=torch.float32, device=dev) if track else None
+    check(_lib.load().cer_decision_stream_push(ctypes.byref(d), rows.data_ptr(), segments.data_ptr(), a, *state_ptrs, _addr(dec),
+                                               _addr(means), current_stream()), "cer_decision_stream_push")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("decision_push", 0))
+    return (dec, means) if track else None
+
+
+def decision_stream_read(table, max_count, state, *, window=None, drop_last=False, classify=True):
+    """The decisions as they stand: ``table`` [6, S] (``decision_segment_table``, one entry per stream in stream order: count
+    = rows in the window, position = where the next row goes, frames since reset) -> (decisions [S, 3] int32 with -1 for a
+    stream without a frame, or None without ``classify``; means [S, 2, C], NaN for such a stream)."""
+    d, state_ptrs, dev = _decision_state(state, window, classify)
+    like = state["slog"] if window is None else state["zring"]
+    if _stream_table(table, "table", DECISION_FIELDS, like) != d.S:
+        raise ValueError(f"table: expected one entry per stream ({d.S}), got {table.shape[1]}")
+    d.M, d.max_count, d.drop_last = 1, int(max_count), int(bool(drop_last))
+    dec = torch.empty((d.S, 3), dtype=torch.int32, device=dev) if classify else None
+    means = torch.empty((d.S, 2, d.C), dtype=torch.float32, device=dev)
+    check(_lib.load().cer_decision_stream_read(ctypes.byref(d), table.data_ptr(), *state_ptrs, _addr(dec), means.data_ptr(),
+                                               current_stream()), "cer_decision_stream_read")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("decision_read", 0))
+    return dec, means

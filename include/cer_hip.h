@@ -808,6 +808,61 @@ int cer_frames_stream_append(const uint8_t *frames, int n_frames, int H, int W, 
 int cer_frames_stream_gather(const uint8_t *u8ring, int S, int Rf, int crop, const int32_t *row_stream, const int32_t *row_pos,
                              int num_rows, float mean, float stdv, float *out, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Running video-level decisions of S live streams (csrc/decision_stream.hip): logit rows in, the three decisions of
+ * metrics.py:118-139 out -- majority vote over the frame predictions, argmax of the mean logits, argmax of the mean softmax
+ * probabilities -- over the first nc = C - (drop_last ? 1 : 0) columns.
+ *
+ * State.  Whole-stream (W = 0: all frames since the stream's reset): votes [S][C] and first [S][C] int64 (frames predicted
+ * as class c; index since reset of the first of them, INT64_MAX while there is none), slog [S][C] and sprob [S][C] float64
+ * (sums of the logits and of the probabilities).  A reset stream has votes = slog = sprob = 0 and first = INT64_MAX.
+ * Window (W >= 1: the last min(n, W) frames): zring [S][R][C] fp32, the logits themselves, R a power of two >= W +
+ * max_count; nothing is accumulated across calls, a decision is recomputed from the window's rows.  Without `classify`
+ * (regression outputs) only slog / zring exist and only the mean of the rows is defined.
+ *
+ * Arithmetic, one definition for both modes: prediction = the first NaN, otherwise the first maximum (numpy.argmax);
+ * probability = expf(z[c]) / (expf(z[0]) + ... + expf(z[nc - 1])) in fp32 without max subtraction; column sums
+ * acc += (double)value, one chain per (stream, class) in time order -- continued from the accumulators whole-stream,
+ * started at the window's oldest row otherwise; mean = sum / n in double (the decisions compare the doubles; outputs are
+ * rounded once to fp32); vote ties go to the class first seen earliest (inside the window, in window mode).  A result is
+ * the same bits however the rows were cut into pushes, whatever max_count, the ring position, S or the other streams.
+ *
+ * Tables.  The device keeps no counters.  segments [6][num_segments] int32 = stream, count, offset of the stream's first new
+ * row in `rows`, ring position of that row (unwrapped, modulo 2^30), and the stream's frames since reset BEFORE the push as a
+ * 64-bit value (low word, then high word).  A stream has at most one segment per push.  cer_decision_stream_read takes the
+ * same six fields, one column per stream in stream order (the stream field is not read): count = rows in the window
+ * (ignored when W = 0), position = where the next row would go, frames = frames since reset.  One block of 64 lanes per
+ * segment (per stream for a read); no atomics, no flags, no scratch.
+ *
+ * cer_decision_stream_push: appends `count` rows per segment.  track [M][3] int32 (may be NULL) receives the three
+ * decisions as they stand AFTER each new row, track_means [M][2][C] fp32 (may be NULL) the mean logits and the mean
+ * probabilities after it (the dropped column: its mean logit, and 0; without classify the second half is 0).
+ * cer_decision_stream_read: decisions [S][3] int32 (-1 for a stream with no frame; NULL without classify) and means
+ * [S][2][C] fp32 (NaN for a stream with no frame).  It takes the descriptor of the pushes; M only has to be >= 1.
+ *
+ * The tables are never trusted with an address: the stream is clamped into [0, S), a count is cut to max_count (to W in a
+ * read), positions are masked with R - 1, and every access to `rows`, `track` and `track_means` is bounded by M (a row
+ * outside reads as 0).  A wrong table gives wrong numbers, never an access outside the state or the packed rows.
+ * Refused with CER_ERR_INVALID_ARG before any launch, with a cer_last_error() text that begins with the entry's name: a null
+ * pointer (descriptor, rows, table, a state tensor of the mode, the outputs of a read); C < 2 or C > 16; S, M or max_count
+ * < 1; W < 0; for W >= 1, R not a power of two or W + max_count > R; drop_last with C < 3 or without classify; a track
+ * without classify; num_segments < 1.
+ * ---------------------------------------------------------------------- */
+typedef struct cer_decision_stream_desc {
+    int32_t S, C;              /* streams, columns of a row */
+    int32_t M, max_count;      /* packed rows of the push, the largest count of one stream */
+    int32_t W, R;              /* window length (0: whole-stream) and ring length (read when W >= 1) */
+    int32_t drop_last;         /* decide over the first C - 1 columns */
+    int32_t classify;          /* 0: rows are regression outputs, only their mean is kept */
+} cer_decision_stream_desc;
+
+int cer_decision_stream_push(const cer_decision_stream_desc *d, const float *rows, const int32_t *segments, int num_segments,
+                             long long *votes, long long *first, double *slog, double *sprob, float *zring, int32_t *track,
+                             float *track_means, void *stream);
+int cer_decision_stream_read(const cer_decision_stream_desc *d, const int32_t *table, const long long *votes,
+                             const long long *first, const double *slog, const double *sprob, const float *zring,
+                             int32_t *decisions, float *means, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
