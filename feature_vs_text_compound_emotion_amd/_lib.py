@@ -167,6 +167,10 @@ _SIGNATURES = {
     "cer_frames_stream_append": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int, _P, _P,
                                          c_int, c_int, _P, c_int, c_int, _P]),
     "cer_frames_stream_gather": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, c_float, c_float, _P, _P]),
+    "cer_frames_transform_boxes": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int,
+                                           c_float, c_float, _P, _P, _P]),
+    "cer_frames_stream_append_boxes": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P,
+                                               c_int, c_int, _P, c_int, c_int, _P]),
     "cer_decision_stream_push": (c_int, [POINTER(DecisionStreamDesc), _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cer_decision_stream_read": (c_int, [POINTER(DecisionStreamDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }

@@ -44,15 +44,133 @@ def resample_tables(in_size, out_size):
     return bounds, coef
 
 
+def _resample_tables_np(in_size, out_size):
+    """``resample_tables`` with the taps of every output computed at once: the same float64 operations in the same order
+    (the running sum is ``np.add.accumulate``, left to right), so the same integers.  tests/test_frames_boxes_cpu.py holds the
+    two equal for every side the table store can hold."""
+    scale = float(np.float32(in_size)) / out_size
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    inv = 1.0 / filterscale
+    center = ((np.arange(out_size, dtype=np.float64) + 0.5) * scale)[:, None]
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)
+    cnt = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    live = x < cnt
+    w = np.where(live, np.maximum(0.0, 1.0 - np.abs(((x + xmin) - center + 0.5) * inv)), 0.0)
+    total = np.add.accumulate(w, axis=1)[:, -1:]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v = np.where(total != 0.0, w / total, w) * (1 << PRECISION_BITS)
+    coef = np.where(live, np.where(v < 0, v - 0.5, v + 0.5).astype(np.int64), 0).astype(np.int32)
+    return np.concatenate([xmin, cnt], axis=1).astype(np.int32), coef
+
+
+BOX_MAX_SIDE = 1024     # default of ``max_side``: the largest box side the table store holds
+BOX_COORD = 1 << 20     # |box coordinate| bound of csrc/frames_box.hip (FB_COORD)
+
+
+class BoxTables:
+    """The table store of the boxed entries (csrc/frames_box.hip): Pillow's bounds and coefficients of EVERY side
+    n = 1 .. ``max_side`` resampled to ``size``, concatenated in one int32 array ``data``, and ``meta`` [max_side + 1, 4] =
+    (offset of the bounds, offset of the coefficients, ksize, band span) of side n.  The band span is the most box rows one
+    band of ``cer_frames_band_rows()`` output rows needs, over every crop offset; ``max_rows`` and ``max_ks`` are the largest
+    span and ksize of the store and size the kernel's LDS.  Built on the host once per (size, max_side) by ``box_tables``,
+    uploaded once per device."""
+
+    def __init__(self, size, max_side):
+        band = _lib.load().cer_frames_band_rows()
+        self.size, self.max_side = int(size), int(max_side)
+        meta = np.zeros((self.max_side + 1, 4), np.int64)
+        parts, at = [], 0
+        y0 = np.arange(self.size)
+        y1 = np.minimum(self.size, y0 + band) - 1
+        for n in range(1, self.max_side + 1):
+            b, k = _resample_tables_np(n, self.size)
+            span = int((b[y1, 0] + b[y1, 1] - b[y0, 0]).max())
+            meta[n] = (at, at + b.size, k.shape[1], span)
+            parts += [b.ravel(), k.ravel()]
+            at += b.size + k.size
+        if at >= 1 << 31:
+            raise ValueError(f"the table store of size {size}, max_side {max_side} exceeds int32 offsets")
+        meta[0] = meta[1]
+        self.meta, self.data = meta.astype(np.int32), np.concatenate(parts)
+        self.max_rows, self.max_ks = int(meta[1:, 3].max()), int(meta[1:, 2].max())
+        self._dev = {}
+
+    def rows(self, n):
+        """(bounds [size, 2], coefficients [size, ksize]) of side n, as ``resample_tables(n, size)`` gives them."""
+        b, k, ks, _ = (int(v) for v in self.meta[n])
+        return self.data[b:b + 2 * self.size].reshape(self.size, 2), self.data[k:k + self.size * ks].reshape(self.size, ks)
+
+    def on(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.meta).to(device), torch.from_numpy(self.data).to(device))
+        return self._dev[key]
+
+
+_BOX_TABLES = {}
+
+
+def box_tables(size, max_side=BOX_MAX_SIDE):
+    """The ``BoxTables`` of (size, max_side), built by the first call that asks for it."""
+    key = (int(size), int(max_side))
+    if key not in _BOX_TABLES:
+        _BOX_TABLES[key] = BoxTables(*key)
+    return _BOX_TABLES[key]
+
+
+def check_boxes(boxes, rows, max_side):
+    """Everything the boxed calls refuse about ``boxes``, on the host: -> int32 numpy [rows, 4] = (x0, y0, x1, y1), PIL's
+    (left, upper, right, lower).  Boxes are host integers like ``counts``: checking a GPU tensor would cost a
+    synchronisation, so one is refused."""
+    if torch.is_tensor(boxes):
+        if boxes.is_cuda:
+            raise ValueError("boxes: expected host integers (a list, a numpy array or a CPU tensor), got a GPU tensor")
+        if boxes.is_floating_point() or boxes.is_complex() or boxes.dtype == torch.bool:
+            raise ValueError(f"boxes: expected integers, got dtype {boxes.dtype}")
+        arr = boxes.numpy()
+    else:
+        arr = np.asarray(boxes)
+    if arr.size == 0 and rows == 0:
+        return np.zeros((0, 4), np.int32)
+    if arr.dtype.kind not in "iu":
+        raise ValueError(f"boxes: expected integers, got dtype {arr.dtype}")
+    if arr.ndim == 3:
+        arr = arr.reshape(-1, arr.shape[2])
+    if arr.shape != (rows, 4):
+        raise ValueError(f"boxes: expected one (x0, y0, x1, y1) per frame [{rows}, 4], got {arr.shape}")
+    arr = arr.astype(np.int64)
+    w, h = arr[:, 2] - arr[:, 0], arr[:, 3] - arr[:, 1]
+    if (w < 1).any() or (h < 1).any():
+        i = int(np.nonzero((w < 1) | (h < 1))[0][0])
+        raise ValueError(f"boxes: box {i} = {arr[i].tolist()} is empty (x1 <= x0 or y1 <= y0)")
+    if (w > max_side).any() or (h > max_side).any():
+        i = int(np.nonzero((w > max_side) | (h > max_side))[0][0])
+        raise ValueError(f"boxes: box {i} = {arr[i].tolist()} has a side above max_side = {max_side}")
+    if (np.abs(arr) > BOX_COORD).any():
+        raise ValueError(f"boxes: a coordinate lies beyond +-{BOX_COORD}")
+    return arr.astype(np.int32)
+
+
 class FrameTransform:
     """``FrameTransform(size=48, crop=40, train=True)(frames_u8[B,L,H,W,3]) -> float32 [B,L,3,crop,crop]``.
 
     train=True draws one (x1, y1) crop offset and one flip per clip with Python's ``random`` in the
     reference's call order (transforms3D.py:52-53,80); train=False uses GroupCenterCrop's offset.
+
+    ``boxes`` [B, L, 4] or [B * L, 4] host integers: the frames are full camera frames and frame f is first cropped to its
+    box (x0, y0, x1, y1) as ``PIL.Image.crop`` does -- right and lower exclusive, zero outside the frame -- so the result is
+    what the unboxed call gives the contiguous zero-padded slice; a box equal to the whole frame gives the unboxed bits.
+    One launch for any mix of boxes (csrc/frames_box.hip); sides up to ``max_side``.
     """
 
-    def __init__(self, size=48, crop=40, train=True, mean=0.5, std=0.5):
+    def __init__(self, size=48, crop=40, train=True, mean=0.5, std=0.5, max_side=BOX_MAX_SIDE):
         self.size, self.crop, self.train, self.mean, self.std = size, crop, train, float(mean), float(std)
+        if isinstance(max_side, bool) or int(max_side) != max_side or not 1 <= max_side <= BOX_COORD:
+            raise ValueError(f"max_side = {max_side!r}: must be an integer in 1 .. {BOX_COORD}")
+        self.max_side = int(max_side)
         self._tables = {}
 
     def _get_tables(self, h, w, device):
@@ -84,7 +202,7 @@ class FrameTransform:
                 out[i, 0] = out[i, 1] = int(round((self.size - self.crop) / 2.0))
         return out
 
-    def __call__(self, frames, crop_xyf=None, return_u8=False):
+    def __call__(self, frames, crop_xyf=None, return_u8=False, boxes=None):
         if not frames.is_cuda or frames.dtype != torch.uint8:
             raise RuntimeError("FrameTransform needs a uint8 CUDA tensor [B,L,H,W,3] (there is no CPU fallback)")
         if frames.dim() == 4:
@@ -98,6 +216,8 @@ class FrameTransform:
         crop_xyf = np.ascontiguousarray(crop_xyf, dtype=np.int32).reshape(b, 3)
         if (crop_xyf[:, :2] < 0).any() or (crop_xyf[:, :2] + self.crop > self.size).any():
             raise RuntimeError("FrameTransform: crop offset outside the resized image")
+        if boxes is not None:
+            return self._boxed(frames, crop_xyf, return_u8, check_boxes(boxes, b * l, self.max_side))
         (hb, hk, vb, vk), hks, vks, span = self._get_tables(h, w, frames.device)
         cx = torch.from_numpy(crop_xyf).to(frames.device)
         out = torch.empty((b, l, 3, self.crop, self.crop), dtype=torch.float32, device=frames.device)
@@ -117,6 +237,24 @@ class FrameTransform:
                                            current_stream()), "cer_frames_transform")
         return (out, u8) if return_u8 else out
 
+    def _boxed(self, frames, crop_xyf, return_u8, boxes):
+        from . import ops
+        b, l, h, w, _ = frames.shape
+        if l > 65535:
+            raise RuntimeError("FrameTransform: clip longer than 65535 frames")
+        store = box_tables(self.size, self.max_side)
+        cx, bx = torch.from_numpy(crop_xyf).to(frames.device), torch.from_numpy(boxes).to(frames.device)
+        out = torch.empty((b, l, 3, self.crop, self.crop), dtype=torch.float32, device=frames.device)
+        u8 = torch.empty((b, l, self.crop, self.crop, 3), dtype=torch.uint8, device=frames.device) if return_u8 else None
+        n, step = b * l, 65535 // l * l
+        flat_in, flat_out = frames.view(n, h, w, 3), out.view(n, 3, self.crop, self.crop)
+        flat_u8 = u8.view(n, self.crop, self.crop, 3) if return_u8 else None
+        for s in range(0, n, step):
+            e = min(n, s + step)
+            ops.frames_transform_boxes(flat_in[s:e], bx[s:e], store, self.size, cx[s // l:e // l], l, self.mean, self.std,
+                                       flat_out[s:e], flat_u8[s:e] if return_u8 else None)
+        return (out, u8) if return_u8 else out
+
 
 def hold_ring(hold, max_new):
     """Slots of a ring in which up to ``hold`` rows wait while a push adds up to ``max_new``: the power of two >= their sum."""
@@ -130,10 +268,15 @@ class FrameStream:
     """``FrameTransform(size, crop, train=False)`` for ``streams`` live cameras, a few raw frames at a time; the video
     counterpart of ``LogMelStream``.
 
-      push(frames_u8 [M, H, W, 3], counts)  stream s brings ``counts[s]`` (0 .. max_new) new frames, packed stream-major in
+      push(frames_u8 [M, H, W, 3], counts, boxes=None)
+                                            stream s brings ``counts[s]`` (0 .. max_new) new frames, packed stream-major in
                                             ascending stream order, each stream's in time order.  H and W may differ from push
                                             to push (the ring holds crops; coefficient tables are cached per geometry).
-                                            Returns nothing: the frames wait.
+                                            Returns nothing: the frames wait.  ``boxes`` [M, 4] host integers, one
+                                            (x0, y0, x1, y1) per packed frame: the frames are full camera frames and each
+                                            is cropped to its box first, as ``FrameTransform(..., boxes=)`` does (sides up
+                                            to ``max_side``; still one upload and one launch).  Boxed and unboxed pushes
+                                            may alternate: the ring holds crops.
       take(pairs)                           pairs = (stream, frame number) per row -> float32 [M, 3, crop, crop], the bits
                                             ``FrameTransform`` gives those frames.  A stream's frames up to the largest one
                                             taken are released; the others go on waiting.
@@ -148,8 +291,10 @@ class FrameStream:
     A push that would leave more than ``hold`` untaken frames in a stream, bad counts, and a tensor that is not uint8 RGB on
     the GPU raise ValueError before any launch and leave the state as it was."""
 
-    def __init__(self, streams, size=48, crop=40, hold=64, max_new=32, mean=0.5, std=0.5, device="cuda", crop_xyf=None):
-        for name, v in (("streams", streams), ("size", size), ("crop", crop), ("hold", hold), ("max_new", max_new)):
+    def __init__(self, streams, size=48, crop=40, hold=64, max_new=32, mean=0.5, std=0.5, device="cuda", crop_xyf=None,
+                 max_side=BOX_MAX_SIDE):
+        for name, v in (("streams", streams), ("size", size), ("crop", crop), ("hold", hold), ("max_new", max_new),
+                        ("max_side", max_side)):
             if isinstance(v, bool) or int(v) != v or v < 1:
                 raise ValueError(f"{name} = {v!r}: must be an integer >= 1")
         if crop > size:
@@ -161,7 +306,8 @@ class FrameStream:
             raise ValueError(f"FrameStream runs on the HIP kernels only (no CPU fallback), got device {device!r}")
         self.streams, self.size, self.crop, self.hold, self.max_new = int(streams), int(size), int(crop), int(hold), int(max_new)
         self.ring_frames = hold_ring(self.hold, self.max_new)
-        self._xf = FrameTransform(self.size, self.crop, train=False, mean=mean, std=std)
+        self._xf = FrameTransform(self.size, self.crop, train=False, mean=mean, std=std, max_side=max_side)
+        self.max_side = self._xf.max_side
         if crop_xyf is None:
             crop_xyf = self._xf.draw(self.streams)
         crop_xyf = np.ascontiguousarray(crop_xyf, dtype=np.int32)
@@ -191,7 +337,7 @@ class FrameStream:
         for s in self._indices(streams):
             self.frames_seen[s] = self.frames_taken[s] = 0
 
-    def check_push(self, frames_u8, counts):
+    def check_push(self, frames_u8, counts, boxes=None):
         """Everything ``push`` refuses, without a launch or a change of state.  Returns the counts as ints."""
         try:
             counts = [int(c) for c in counts]
@@ -204,6 +350,8 @@ class FrameStream:
                 raise ValueError(f"counts: stream {s} brings {c} frames, outside 0 .. max_new = {self.max_new}")
             if self.held[s] + c > self.hold:
                 raise ValueError(f"stream {s}: {self.held[s]} frames wait and {c} more exceed hold = {self.hold}; take some first")
+        if boxes is not None:
+            check_boxes(boxes, sum(counts), self.max_side)
         f = frames_u8
         if not (torch.is_tensor(f) and f.is_cuda and f.dtype == torch.uint8 and f.dim() == 4 and f.shape[3] == 3):
             raise ValueError("frames: expected raw RGB frames as a uint8 GPU tensor [M, H, W, 3] (there is no CPU fallback), got "
@@ -217,21 +365,28 @@ class FrameStream:
         return counts
 
     @torch.no_grad()
-    def push(self, frames_u8, counts):
+    def push(self, frames_u8, counts, boxes=None):
         from . import ops
-        counts = self.check_push(frames_u8, counts)
+        counts = self.check_push(frames_u8, counts, boxes)
         if not sum(counts):
             return
         frames = frames_u8.contiguous()
         _, h, w, _ = frames.shape
-        tables, _, _, span = self._xf._get_tables(h, w, frames.device)
+        if boxes is None:
+            tables, _, _, span = self._xf._get_tables(h, w, frames.device)
+        else:
+            boxes, store = check_boxes(boxes, sum(counts), self.max_side), box_tables(self.size, self.max_side)
         if self.ring is None:
             self.ring = torch.zeros((self.streams, self.ring_frames, self.crop, self.crop, 3), device=self.device,
                                     dtype=torch.uint8)
             self._cx = torch.from_numpy(self.crop_xyf).to(self.device)
         first = [b + n for b, n in zip(self._base, self.frames_seen)]
-        row_stream, row_pos = ops.stream_row_table(first, counts, self.device)
-        ops.frames_stream_append(frames, tables, span, self.size, self._cx, row_stream, row_pos, max(counts), self.ring)
+        if boxes is None:
+            row_stream, row_pos = ops.stream_row_table(first, counts, self.device)
+            ops.frames_stream_append(frames, tables, span, self.size, self._cx, row_stream, row_pos, max(counts), self.ring)
+        else:
+            row_stream, row_pos, bx = ops.stream_row_box_table(first, counts, boxes, self.device)
+            ops.frames_stream_append_boxes(frames, bx, store, self.size, self._cx, row_stream, row_pos, max(counts), self.ring)
         self.frames_seen = [n + c for n, c in zip(self.frames_seen, counts)]
 
     def check_take(self, pairs):

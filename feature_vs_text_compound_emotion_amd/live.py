@@ -67,10 +67,12 @@ def check_waiting(frames, examples, paired, new_frames, examples_after, hold, le
 class AVStream:
     """An eval-mode LFAN or CAN on ``streams`` live audio-visual streams at ``fps`` frames per second.
 
-      push(video=None, video_counts=None, audio=None, audio_counts=None, extra=None)
+      push(video=None, video_counts=None, audio=None, audio_counts=None, extra=None, video_boxes=None)
             video [M, H, W, 3] uint8 raw frames, ``video_counts[s]`` (0 .. max_new) of stream s, packed stream-major; audio
             int16 PCM as ``LogMelStream.push`` takes it with ``audio_counts``; either side may be absent.  ``extra[m]``
             [M, embedding_dim[m]] float32: the rows of every further modality of the model (``bert``) for the new frames.
+            ``video_boxes`` [M, 4] host integers: ``video`` holds full camera frames and frame m is cropped to its face box
+            (x0, y0, x1, y1) first, as ``FrameStream.push(..., boxes=)`` does (sides up to ``max_side``).
             -> (logits [P, n_cls], counts): every frame that became paired in this call, stream-major, each stream's frames in
             time order (the row order of ``push_ragged``); counts[s] of them belong to stream s.  Nothing paired: an empty
             [0, n_cls] and no model launch.
@@ -96,7 +98,8 @@ class AVStream:
     call reach the model in several pushes, in time order."""
 
     def __init__(self, model, streams, fps, *, sample_rate=16000, channels=1, resample=None, size=48, crop=40, hold=64, lead=8,
-                 max_new=32, max_samples=4096, encoder_batch=8, audio_backbone=None, decisions=None):
+                 max_new=32, max_samples=4096, encoder_batch=8, audio_backbone=None, decisions=None,
+                 max_side=1024):
         cls = CANStream if isinstance(model, CAN) else LFANStream
         if not isinstance(model, cls._model_class):
             raise TypeError(f"AVStream needs an LFAN or a CAN (JMT / MT attend over time and are not causal), got "
@@ -121,7 +124,8 @@ class AVStream:
                 raise ValueError("AVStream: the model takes 'vggish' rows and has no audio backbone of its own: pass audio_backbone=")
         self.model, self.streams, self.fps, self.hold, self.lead, self.max_new = model, int(streams), fps, int(hold), int(lead), int(max_new)
         device = next(model.parameters()).device
-        self.frame_stream = FrameStream(streams, size=size, crop=crop, hold=hold, max_new=max_new, device=device)
+        self.frame_stream = FrameStream(streams, size=size, crop=crop, hold=hold, max_new=max_new, device=device,
+                                        max_side=max_side)
         self.audio_stream = LogMelStream(streams, 1.0 / fps, max_samples=max_samples, device=device, sample_rate=sample_rate,
                                          channels=channels, resample=resample)   # hop_sec: the expression of audio_features
         self.model_stream = cls(model, streams, max_new=max_new, encoder_batch=encoder_batch)
@@ -216,12 +220,14 @@ class AVStream:
 
     # ------------------------------------------------------------------------------------------------ the session
     @torch.no_grad()
-    def push(self, video=None, video_counts=None, audio=None, audio_counts=None, extra=None):
+    def push(self, video=None, video_counts=None, audio=None, audio_counts=None, extra=None, video_boxes=None):
         zeros = [0] * self.streams
         if (video is None) != (video_counts is None) or (audio is None) != (audio_counts is None):
             raise ValueError("push: video and video_counts come together, and so do audio and audio_counts")
+        if video is None and video_boxes is not None:
+            raise ValueError("push: video_boxes without video")
         self.model_stream._check_keys(dict.fromkeys(self.model_stream.modalities))   # the model may have left eval mode
-        vcounts = self.frame_stream.check_push(video, video_counts) if video is not None else zeros
+        vcounts = self.frame_stream.check_push(video, video_counts, video_boxes) if video is not None else zeros
         extra = self._check_extra(extra, sum(vcounts))
         pcm, acounts = self.audio_stream.check_push(audio, audio_counts) if audio is not None else (None, zeros)
         for s in range(self.streams):
@@ -238,7 +244,7 @@ class AVStream:
                 self._hold_rows(examples.view(-1, self.win * 64), self._exring, self.examples_seen, got)
                 self.examples_seen = [e + g for e, g in zip(self.examples_seen, got)]
         if sum(vcounts):
-            self.frame_stream.push(video, vcounts)
+            self.frame_stream.push(video, vcounts, video_boxes)
             for m in self.extra_keys:
                 self._hold_rows(extra[m], self._extra[m], self.frames_seen, vcounts)
             self.frames_seen = [f + c for f, c in zip(self.frames_seen, vcounts)]

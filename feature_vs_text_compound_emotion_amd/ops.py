@@ -6,6 +6,7 @@ one C call.  No arithmetic happens in Python.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1709,11 +1710,8 @@ def tcn_stream_conv(ring, head, c, w_packed, bias, k, dil, *, res_ring=None, res
 ROW_POS_MOD = 1 << 30   # row positions travel modulo 2^30: every ring length divides it, so each launch's mask sees the same slot
 
 
-def stream_row_table(positions, counts, device):
-    """The row table of one ragged push: stream s brings ``counts[s]`` frames, the first at position ``positions[s]`` (frames
-    that stream has been pushed so far).  Returns (row_stream, row_pos), int32 [M] each on ``device``: rows stream-major in
-    ascending stream order, a stream's frames in time order, positions modulo 2^30; a stream with count 0 has no row.
-    Built from Python ints and uploaded in one fresh tensor per call (no staging buffer an unfinished copy could still read)."""
+def _stream_rows(positions, counts):
+    """The rows of one ragged push as two lists of Python ints: (stream of row m, position of row m modulo 2^30)."""
     positions, counts = [int(p) for p in positions], [int(c) for c in counts]
     if len(positions) != len(counts):
         raise ValueError(f"stream_row_table: {len(positions)} positions for {len(counts)} counts")
@@ -1721,7 +1719,15 @@ def stream_row_table(positions, counts, device):
         if c < 0 or p < 0:
             raise ValueError(f"stream_row_table: stream {s} has count {c} at position {p}: both must be >= 0")
     streams = [s for s, c in enumerate(counts) for _ in range(c)]
-    pos = [(p + i) % ROW_POS_MOD for p, c in zip(positions, counts) for i in range(c)]
+    return streams, [(p + i) % ROW_POS_MOD for p, c in zip(positions, counts) for i in range(c)]
+
+
+def stream_row_table(positions, counts, device):
+    """The row table of one ragged push: stream s brings ``counts[s]`` frames, the first at position ``positions[s]`` (frames
+    that stream has been pushed so far).  Returns (row_stream, row_pos), int32 [M] each on ``device``: rows stream-major in
+    ascending stream order, a stream's frames in time order, positions modulo 2^30; a stream with count 0 has no row.
+    Built from Python ints and uploaded in one fresh tensor per call (no staging buffer an unfinished copy could still read)."""
+    streams, pos = _stream_rows(positions, counts)
     table = torch.tensor([streams, pos], dtype=torch.int32, device=device).view(2, len(streams))
     return table[0], table[1]
 
@@ -2047,6 +2053,77 @@ def frames_stream_append(frames, tables, span, size, crop_xyf, row_stream, row_p
                                                int(max_count), ptr(u8ring), s, rf, current_stream()), "cer_frames_stream_append")
     if STREAM_TRACE is not None:
         STREAM_TRACE.append(("frames_append", 0))
+
+
+# ------------------------------------------------------------------ per-frame face boxes (csrc/frames_box.hip)
+def stream_row_box_table(positions, counts, boxes, device):
+    """``stream_row_table`` and the boxes of the same rows in ONE upload: ``boxes`` int [M, 4] on the host, row m the box of
+    packed frame m -> (row_stream [M], row_pos [M], boxes [M, 4]), int32 views of one fresh tensor on ``device``."""
+    streams, pos = _stream_rows(positions, counts)
+    m = len(streams)
+    boxes = np.ascontiguousarray(boxes, dtype=np.int32)
+    if boxes.shape != (m, 4):
+        raise ValueError(f"stream_row_box_table: expected one box per row [{m}, 4], got {boxes.shape}")
+    host = np.empty(6 * m, np.int32)
+    host[:m], host[m:2 * m], host[2 * m:] = streams, pos, boxes.ravel()
+    table = torch.from_numpy(host).to(device)
+    return table[:m], table[m:2 * m], table[2 * m:].view(m, 4)
+
+
+def _box_args(frames, boxes, store, size, like):
+    """The checks the two boxed entries share.  Returns (n, H, W, meta, data)."""
+    if not (torch.is_tensor(frames) and frames.is_cuda and frames.device == like.device and frames.dtype == torch.uint8
+            and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
+        raise ValueError(f"frames: expected a contiguous uint8 [n >= 1, H, W, 3] tensor on the GPU ({like.device}), got "
+                         f"{(frames.dtype, frames.device, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
+    if store.size != int(size):
+        raise ValueError(f"store: built for size {store.size}, not {size}")
+    if not torch.is_tensor(boxes) or boxes.dim() != 2:
+        raise ValueError("boxes: expected an int32 [rows, 4] GPU tensor")
+    _i32_table(boxes, "boxes", (boxes.shape[0], 4), like)
+    meta, data = store.on(like.device)
+    return frames.shape[0], frames.shape[1], frames.shape[2], meta, data
+
+
+def frames_transform_boxes(frames, boxes, store, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None):
+    """``Image.crop(boxes[f])`` -> GroupScale(size) -> crop -> flip -> ToTensor -> Normalize of full frames ``frames``
+    [n, H, W, 3] uint8 into ``out`` [n, 3, crop, crop] float32 (and ``out_u8`` [n, crop, crop, 3]).  ``boxes`` int32 [n, 4]
+    on the GPU = (x0, y0, x1, y1), right and lower exclusive, zero outside the frame; the kernel clamps what it is given
+    (coordinates into +-2^20, sides into 1 .. ``store.max_side``), so a table nobody vetted gives wrong numbers and no
+    access outside ``frames``.  ``store``: ``frames.box_tables(size, max_side)``; ``crop_xyf`` int32 [groups, 3] on the GPU,
+    one entry per ``frames_per_group`` frames."""
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4
+            and out.shape[1] == 3 and out.shape[2] == out.shape[3]):
+        raise ValueError("out: expected a contiguous float32 [n, 3, crop, crop] GPU tensor")
+    n, h, w, meta, data = _box_args(frames, boxes, store, size, out)
+    crop, g = out.shape[2], int(frames_per_group)
+    if out.shape[0] != n or boxes.shape[0] != n or g < 1:
+        raise ValueError(f"out / boxes: expected {n} rows, got {out.shape[0]} and {boxes.shape[0]}")
+    _i32_table(crop_xyf, "crop_xyf", ((n + g - 1) // g, 3), out)
+    if out_u8 is not None and not (torch.is_tensor(out_u8) and out_u8.is_cuda and out_u8.device == out.device and out_u8.dtype == torch.uint8
+                                   and out_u8.is_contiguous() and tuple(out_u8.shape) == (n, crop, crop, 3)):
+        raise ValueError(f"out_u8: expected a contiguous uint8 [{n}, {crop}, {crop}, 3] tensor on the GPU of out")
+    check(_lib.load().cer_frames_transform_boxes(ptr(frames), n, h, w, ptr(boxes), ptr(meta), ptr(data), store.max_side,
+                                                 store.max_rows, store.max_ks, int(size), crop, ptr(crop_xyf), g, float(mean),
+                                                 float(std), ptr(out), ptr(out_u8), current_stream()), "cer_frames_transform_boxes")
+
+
+def frames_stream_append_boxes(frames, boxes, store, size, crop_xyf, row_stream, row_pos, max_count, u8ring):
+    """``frames_stream_append`` of full frames with one box per row: row m of the row table is packed frame m, cropped to
+    ``boxes[m]`` as ``frames_transform_boxes`` does, and lands in slot (row_stream[m], row_pos[m] % Rf).  The bytes are
+    ``return_u8`` of ``FrameTransform(..., boxes=)`` for the same frame, box and crop entry."""
+    s, rf, crop = _u8_ring(u8ring)
+    n, h, w, meta, data = _box_args(frames, boxes, store, size, u8ring)
+    m = _row_table(row_stream, row_pos, u8ring)
+    if boxes.shape[0] != m:
+        raise ValueError(f"boxes: expected one box per row [{m}, 4], got {tuple(boxes.shape)}")
+    _i32_table(crop_xyf, "crop_xyf", (s, 3), u8ring)
+    check(_lib.load().cer_frames_stream_append_boxes(ptr(frames), n, h, w, ptr(boxes), ptr(meta), ptr(data), store.max_side,
+                                                     store.max_rows, store.max_ks, int(size), crop, ptr(crop_xyf),
+                                                     ptr(row_stream), ptr(row_pos), m, int(max_count), ptr(u8ring), s, rf,
+                                                     current_stream()), "cer_frames_stream_append_boxes")
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("frames_append_boxes", 0))
 
 
 def frames_stream_gather(u8ring, row_stream, row_pos, mean=0.5, std=0.5):

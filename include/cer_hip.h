@@ -809,6 +809,42 @@ int cer_frames_stream_gather(const uint8_t *u8ring, int S, int Rf, int crop, con
                              int num_rows, float mean, float stdv, float *out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Per-frame face boxes on full camera frames (csrc/frames_box.hip): PIL's Image.crop(box) -> cer_frames_transform, per frame.
+ *
+ * boxes [rows][4] int32 = (x0, y0, x1, y1) per launch row, PIL's (left, upper, right, lower), right and lower exclusive; the
+ * part of a box outside the H x W frame reads as 0.  Row f gives the bytes (and floats) cer_frames_transform gives the
+ * contiguous zero-padded slice of its frame; a box equal to the whole frame gives the bits of the unboxed entries.
+ *
+ * The coefficients of every side n = 1 .. max_side come from one table store, built once per (size, max_side):
+ *   box_meta [max_side + 1][4] int32 = (offset of the bounds, offset of the coefficients, ksize, band span) of side n, the
+ *     offsets counted in int32 from box_data (row 0 repeats row 1);
+ *   box_data: for each n the bounds [size][2] and coefficients [size][ksize] of cer_frames_transform for n -> size.
+ * max_band_rows = the largest band span and max_ksize = the largest ksize of any n <= max_side: they size the LDS, which is
+ * bounded by (size, crop, max_side) and does not depend on H x W.
+ *
+ * cer_frames_transform_boxes: the clip form; rows = n_frames, the other arguments as in cer_frames_transform.
+ * cer_frames_stream_append_boxes: the ring form; row m reads packed frame m (clamped below n_frames) and box m, the other
+ *   arguments as in cer_frames_stream_append.
+ *
+ * The box table is never trusted with an address: a coordinate is clamped into +-2^20, width and height into
+ * [1, max_side], every input pixel is fetched through a range check against the frame, and the streamed tables are treated
+ * as in cer_frames_stream_append.  A wrong table gives wrong numbers, never an access outside the packed frames or the ring.
+ * Refused before any launch, with a cer_last_error() text that begins with the entry's name: a null pointer; a count or a
+ * dimension below 1; crop > size; max_side outside 1 .. 2^20; max_band_rows > max_side; Rf not a power of two up to 2^30;
+ * max_count > Rf; more than 65535 rows or frames per call (CER_ERR_INVALID_ARG); an LDS need above 160 KiB
+ * (CER_ERR_UNSUPPORTED).
+ * ---------------------------------------------------------------------- */
+int cer_frames_transform_boxes(const uint8_t *frames, int n_frames, int H, int W, const int32_t *boxes, const int32_t *box_meta,
+                               const int32_t *box_data, int max_side, int max_band_rows, int max_ksize, int size, int crop,
+                               const int32_t *crop_xyf, int frames_per_group, float mean, float stdv, float *out,
+                               uint8_t *out_u8, void *stream);
+int cer_frames_stream_append_boxes(const uint8_t *frames, int n_frames, int H, int W, const int32_t *boxes,
+                                   const int32_t *box_meta, const int32_t *box_data, int max_side, int max_band_rows,
+                                   int max_ksize, int size, int crop, const int32_t *crop_xyf, const int32_t *row_stream,
+                                   const int32_t *row_pos, int num_rows, int max_count, uint8_t *u8ring, int S, int Rf,
+                                   void *stream);
+
+/* ------------------------------------------------------------------------
  * Running video-level decisions of S live streams (csrc/decision_stream.hip): logit rows in, the three decisions of
  * metrics.py:118-139 out -- majority vote over the frame predictions, argmax of the mean logits, argmax of the mean softmax
  * probabilities -- over the first nc = C - (drop_last ? 1 : 0) columns.
