@@ -52,6 +52,15 @@ class DecisionStreamDesc(Structure):
     _fields_ = [(n, c_int32) for n in ("S", "C", "M", "max_count", "W", "R", "drop_last", "classify")]
 
 
+YUV_NV12, YUV_I420 = 0, 1   # cer_yuv420.layout
+YUV_PREC = 14
+
+
+class Yuv420Desc(Structure):
+    """cer_yuv420 (see include/cer_hip.h)."""
+    _fields_ = [(n, c_int32) for n in ("layout", "cy", "crv", "cgu", "cgv", "cbu", "yoff")]
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "cer_last_error": (c_char_p, []),
@@ -171,6 +180,14 @@ _SIGNATURES = {
                                            c_float, c_float, _P, _P, _P]),
     "cer_frames_stream_append_boxes": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P,
                                                c_int, c_int, _P, c_int, c_int, _P]),
+    "cer_frames_transform_yuv": (c_int, [_P, POINTER(Yuv420Desc), c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P,
+                                         c_int, c_int, c_float, c_float, _P, _P, _P]),
+    "cer_frames_stream_append_yuv": (c_int, [_P, POINTER(Yuv420Desc), c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int,
+                                             _P, c_int, _P, _P, c_int, c_int, _P, c_int, c_int, _P]),
+    "cer_frames_transform_boxes_yuv": (c_int, [_P, POINTER(Yuv420Desc), c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int,
+                                               c_int, _P, c_int, c_float, c_float, _P, _P, _P]),
+    "cer_frames_stream_append_boxes_yuv": (c_int, [_P, POINTER(Yuv420Desc), c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int,
+                                                   c_int, c_int, _P, _P, _P, c_int, c_int, _P, c_int, c_int, _P]),
     "cer_decision_stream_push": (c_int, [POINTER(DecisionStreamDesc), _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cer_decision_stream_read": (c_int, [POINTER(DecisionStreamDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }

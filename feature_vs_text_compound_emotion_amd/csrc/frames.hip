@@ -13,6 +13,9 @@
 // output rows of one frame: the input rows the band needs are fetched ONCE with 16-byte coalesced
 // loads into LDS, resampled horizontally (only the cropped columns, already flipped) into a uint8 LDS
 // image, then vertically into the normalised fp32 output.
+//
+// cer_frames_transform_yuv is the same launch on NV12 / I420 frames: the band is converted to RGB bytes while it is staged
+// (px_yuv420, frames_kernel.h), and everything after that is the code above on the same bytes.
 #include <stdint.h>
 
 #include "frames_kernel.h"
@@ -42,11 +45,12 @@ struct FramesClipPlace {
 
 using namespace cer;
 
-extern "C" int cer_frames_transform(const uint8_t *frames, int n_frames, int H, int W, const int32_t *hbounds,
-                                    const int32_t *hcoef, int hksize, const int32_t *vbounds, const int32_t *vcoef,
-                                    int vksize, int size, int crop, const int32_t *crop_xyf, int frames_per_group,
-                                    int max_band_rows, float mean, float stdv, float *out, uint8_t *out_u8,
-                                    void *stream) {
+// the one body of both entries; `pix` says how a pixel is read
+template <class Pixel>
+static int frames_transform_launch(const uint8_t *frames, int n_frames, int H, int W, const int32_t *hbounds, const int32_t *hcoef,
+                                   int hksize, const int32_t *vbounds, const int32_t *vcoef, int vksize, int size, int crop,
+                                   const int32_t *crop_xyf, int frames_per_group, int max_band_rows, float mean, float stdv,
+                                   float *out, uint8_t *out_u8, void *stream, Pixel pix) {
     if (!frames || !hbounds || !hcoef || !vbounds || !vcoef || !crop_xyf || !out)
         return cer_set_error(CER_ERR_INVALID_ARG, "frames_transform: NULL pointer");
     if (n_frames <= 0 || H <= 0 || W <= 0 || size <= 0 || crop <= 0 || crop > size || hksize <= 0 || vksize <= 0 ||
@@ -59,11 +63,32 @@ extern "C" int cer_frames_transform(const uint8_t *frames, int n_frames, int H, 
     a.frames = frames; a.hb = hbounds; a.hk = hcoef; a.vb = vbounds; a.vk = vcoef;
     a.H = H; a.W = W; a.hks = hksize; a.vks = vksize; a.size = size; a.crop = crop; a.max_rows = max_band_rows;
     const FramesClipPlace place{crop_xyf, out, out_u8, frames_per_group, crop, mean, stdv};
-    auto k = frames_transform_kernel<FramesClipPlace>;
+    auto k = frames_transform_kernel<FramesClipPlace, Pixel>;
     if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    CER_LAUNCH(k, dim3((crop + FR_BAND - 1) / FR_BAND, n_frames), dim3(256), lds, (hipStream_t)stream, a, place);
+    CER_LAUNCH(k, dim3((crop + FR_BAND - 1) / FR_BAND, n_frames), dim3(256), lds, (hipStream_t)stream, a, place, pix);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
+}
+
+extern "C" int cer_frames_transform(const uint8_t *frames, int n_frames, int H, int W, const int32_t *hbounds,
+                                    const int32_t *hcoef, int hksize, const int32_t *vbounds, const int32_t *vcoef,
+                                    int vksize, int size, int crop, const int32_t *crop_xyf, int frames_per_group,
+                                    int max_band_rows, float mean, float stdv, float *out, uint8_t *out_u8,
+                                    void *stream) {
+    return frames_transform_launch(frames, n_frames, H, W, hbounds, hcoef, hksize, vbounds, vcoef, vksize, size, crop, crop_xyf,
+                                   frames_per_group, max_band_rows, mean, stdv, out, out_u8, stream, px_rgb24{});
+}
+
+extern "C" int cer_frames_transform_yuv(const uint8_t *frames, const cer_yuv420 *yuv, int n_frames, int H, int W,
+                                        const int32_t *hbounds, const int32_t *hcoef, int hksize, const int32_t *vbounds,
+                                        const int32_t *vcoef, int vksize, int size, int crop, const int32_t *crop_xyf,
+                                        int frames_per_group, int max_band_rows, float mean, float stdv, float *out,
+                                        uint8_t *out_u8, void *stream) {
+    px_yuv420 pix;
+    const int rc = yuv420_pixel("frames_transform_yuv", yuv, H, W, &pix);
+    if (rc != CER_OK) return rc;
+    return frames_transform_launch(frames, n_frames, H, W, hbounds, hcoef, hksize, vbounds, vcoef, vksize, size, crop, crop_xyf,
+                                   frames_per_group, max_band_rows, mean, stdv, out, out_u8, stream, pix);
 }
 
 extern "C" int cer_frames_band_rows(void) { return FR_BAND; }

@@ -14,6 +14,8 @@
 // One path, two ways to name a frame (the idiom of frames_kernel.h): frames_box_kernel is a template over a Place.
 //   cer_frames_transform_boxes       clip form: fp32 NCHW (and the optional uint8 NHWC), a crop entry per clip.
 //   cer_frames_stream_append_boxes   ring form: the byte into u8ring at row_pos & (Rf - 1), row_stream clamped.
+// And two ways to read a pixel (Pixel, frames_kernel.h): the _yuv siblings of both take NV12 / I420 frames and convert the
+// pixels of the box, and nothing else, in registers.
 //
 // LDS does not grow with the camera frame: the horizontal pass reads the frame from global memory (a band of a 1024-pixel box
 // would be 590 KB of staged rows) and writes an LDS tile [band rows][crop][3]; the coefficient rows of the block's columns and
@@ -37,7 +39,7 @@ constexpr int FB_POS_BITS = 30;
 __device__ __forceinline__ int fb_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 struct FramesBoxArgs {
-    const uint8_t *frames;  // [n_frames][H][W][3]
+    const uint8_t *frames;  // [n_frames] packed frames of the Pixel's layout
     const int32_t *boxes;   // [rows][4] = (x0, y0, x1, y1)
     const int32_t *meta;    // [max_side + 1][4]
     const int32_t *data;
@@ -52,8 +54,9 @@ inline size_t frames_box_lds_bytes(int max_rows, int crop, int max_ks) {
 // Place:  int  source(int f)                                   the packed input frame that launch row f reads (any int)
 //         void entry(int f, int &x1, int &y1, int &flip)       its crop entry (any ints)
 //         void store(int f, int c, int yy, int xc, int v)      where byte v of channel c, cropped row yy, column xc goes
-template <class Place>
-__global__ __launch_bounds__(256) void frames_box_kernel(FramesBoxArgs p, Place place) {
+// Pixel:  px_rgb24 or px_yuv420 (frames_kernel.h), asked at the clamped (fx, fy) only
+template <class Place, class Pixel>
+__global__ __launch_bounds__(256) void frames_box_kernel(FramesBoxArgs p, Place place, Pixel pix) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fb_smem[];
     const int f = blockIdx.y, band = blockIdx.x, tid = threadIdx.x;
     int x1, y1, flip;
@@ -93,23 +96,25 @@ __global__ __launch_bounds__(256) void frames_box_kernel(FramesBoxArgs p, Place 
     __syncthreads();
     // horizontal pass from global memory, column already flipped: one thread per (box row, cropped column) does the three
     // channels.  Every load is issued, at an index clamped into the frame; a tap outside the frame gets coefficient 0 (the
-    // pixel Image.crop pads with), so no value is loaded under a condition.
-    const uint8_t *img = p.frames + (size_t)fb_clamp(place.source(f), 0, p.n_frames - 1) * p.H * p.W * 3;
+    // pixel Image.crop pads with), so no value is loaded under a condition -- and the padding is RGB 0 whatever the Pixel
+    // makes of the bytes it found at the clamped index.
+    const uint8_t *img = p.frames + (size_t)fb_clamp(place.source(f), 0, p.n_frames - 1) * pix.frame_bytes(p.H, p.W);
     for (int i = tid; i < rows * p.crop; i += 256) {
         const int r = i / p.crop, xc = i - r * p.crop;
         const int fy = by0 + r0 + r;
         const bool yin = fy >= 0 && fy < p.H;
-        const uint8_t *row = img + (size_t)fb_clamp(fy, 0, p.H - 1) * p.W * 3;
+        const typename Pixel::Row row = pix.row(img, p.W, fb_clamp(fy, 0, p.H - 1));
         const int fx0 = bx0 + hbl[2 * xc], cnt = yin ? hbl[2 * xc + 1] : 0;  // a row outside the frame is all zero
         const int32_t *k = hkl + xc * p.max_ks;
         int a0 = 1 << (FR_PREC - 1), a1 = a0, a2 = a0;
         for (int j = 0; j < cnt; ++j) {
             const int fx = fx0 + j;
-            const uint8_t *px = row + (size_t)fb_clamp(fx, 0, p.W - 1) * 3;
+            int px[3];
+            pix.get(row, fb_clamp(fx, 0, p.W - 1), px);
             const int kj = (fx >= 0 && fx < p.W) ? k[j] : 0;
-            a0 += (int)px[0] * kj;
-            a1 += (int)px[1] * kj;
-            a2 += (int)px[2] * kj;
+            a0 += px[0] * kj;
+            a1 += px[1] * kj;
+            a2 += px[2] * kj;
         }
         uint8_t *t = tmp + (size_t)i * 3;
         t[0] = (uint8_t)clip8(a0 >> FR_PREC);
@@ -197,11 +202,12 @@ static int fb_check(const char *name, int n_frames, int rows, int H, int W, int 
     return CER_OK;
 }
 
-extern "C" int cer_frames_transform_boxes(const uint8_t *frames, int n_frames, int H, int W, const int32_t *boxes,
-                                          const int32_t *box_meta, const int32_t *box_data, int max_side, int max_band_rows,
-                                          int max_ksize, int size, int crop, const int32_t *crop_xyf, int frames_per_group,
-                                          float mean, float stdv, float *out, uint8_t *out_u8, void *stream) {
-    const char *name = "frames_transform_boxes";
+// the bodies of the clip and the ring entries; `name` is the entry's and `pix` says how a pixel is read
+template <class Pixel>
+static int fb_clip_launch(const char *name, const uint8_t *frames, int n_frames, int H, int W, const int32_t *boxes,
+                          const int32_t *box_meta, const int32_t *box_data, int max_side, int max_band_rows, int max_ksize, int size,
+                          int crop, const int32_t *crop_xyf, int frames_per_group, float mean, float stdv, float *out,
+                          uint8_t *out_u8, void *stream, Pixel pix) {
     if (!frames || !boxes || !box_meta || !box_data || !crop_xyf || !out)
         return cer_set_error(CER_ERR_INVALID_ARG, "%s: null pointer", name);
     if (frames_per_group < 1 || stdv == 0.f)
@@ -211,19 +217,18 @@ extern "C" int cer_frames_transform_boxes(const uint8_t *frames, int n_frames, i
     if (rc != CER_OK) return rc;
     FramesBoxArgs a{frames, boxes, box_meta, box_data, n_frames, H, W, size, crop, max_side, max_band_rows, max_ksize};
     const BoxClipPlace place{crop_xyf, out, out_u8, frames_per_group, crop, mean, stdv};
-    auto k = frames_box_kernel<BoxClipPlace>;
+    auto k = frames_box_kernel<BoxClipPlace, Pixel>;
     if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    CER_LAUNCH(k, dim3((crop + FR_BAND - 1) / FR_BAND, n_frames), dim3(256), lds, (hipStream_t)stream, a, place);
+    CER_LAUNCH(k, dim3((crop + FR_BAND - 1) / FR_BAND, n_frames), dim3(256), lds, (hipStream_t)stream, a, place, pix);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
 }
 
-extern "C" int cer_frames_stream_append_boxes(const uint8_t *frames, int n_frames, int H, int W, const int32_t *boxes,
-                                              const int32_t *box_meta, const int32_t *box_data, int max_side,
-                                              int max_band_rows, int max_ksize, int size, int crop, const int32_t *crop_xyf,
-                                              const int32_t *row_stream, const int32_t *row_pos, int num_rows, int max_count,
-                                              uint8_t *u8ring, int S, int Rf, void *stream) {
-    const char *name = "frames_stream_append_boxes";
+template <class Pixel>
+static int fb_ring_launch(const char *name, const uint8_t *frames, int n_frames, int H, int W, const int32_t *boxes,
+                          const int32_t *box_meta, const int32_t *box_data, int max_side, int max_band_rows, int max_ksize, int size,
+                          int crop, const int32_t *crop_xyf, const int32_t *row_stream, const int32_t *row_pos, int num_rows,
+                          int max_count, uint8_t *u8ring, int S, int Rf, void *stream, Pixel pix) {
     if (!frames || !boxes || !box_meta || !box_data || !crop_xyf || !row_stream || !row_pos || !u8ring)
         return cer_set_error(CER_ERR_INVALID_ARG, "%s: null pointer", name);
     if (S < 1 || max_count < 1)
@@ -235,9 +240,53 @@ extern "C" int cer_frames_stream_append_boxes(const uint8_t *frames, int n_frame
     if (rc != CER_OK) return rc;
     FramesBoxArgs a{frames, boxes, box_meta, box_data, n_frames, H, W, size, crop, max_side, max_band_rows, max_ksize};
     const BoxRingPlace place{crop_xyf, row_stream, row_pos, u8ring, S, Rf, crop};
-    auto k = frames_box_kernel<BoxRingPlace>;
+    auto k = frames_box_kernel<BoxRingPlace, Pixel>;
     if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    CER_LAUNCH(k, dim3((crop + FR_BAND - 1) / FR_BAND, num_rows), dim3(256), lds, (hipStream_t)stream, a, place);
+    CER_LAUNCH(k, dim3((crop + FR_BAND - 1) / FR_BAND, num_rows), dim3(256), lds, (hipStream_t)stream, a, place, pix);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
+}
+
+extern "C" int cer_frames_transform_boxes(const uint8_t *frames, int n_frames, int H, int W, const int32_t *boxes,
+                                          const int32_t *box_meta, const int32_t *box_data, int max_side, int max_band_rows,
+                                          int max_ksize, int size, int crop, const int32_t *crop_xyf, int frames_per_group,
+                                          float mean, float stdv, float *out, uint8_t *out_u8, void *stream) {
+    return fb_clip_launch("frames_transform_boxes", frames, n_frames, H, W, boxes, box_meta, box_data, max_side, max_band_rows,
+                          max_ksize, size, crop, crop_xyf, frames_per_group, mean, stdv, out, out_u8, stream, px_rgb24{});
+}
+
+extern "C" int cer_frames_stream_append_boxes(const uint8_t *frames, int n_frames, int H, int W, const int32_t *boxes,
+                                              const int32_t *box_meta, const int32_t *box_data, int max_side,
+                                              int max_band_rows, int max_ksize, int size, int crop, const int32_t *crop_xyf,
+                                              const int32_t *row_stream, const int32_t *row_pos, int num_rows, int max_count,
+                                              uint8_t *u8ring, int S, int Rf, void *stream) {
+    return fb_ring_launch("frames_stream_append_boxes", frames, n_frames, H, W, boxes, box_meta, box_data, max_side, max_band_rows,
+                          max_ksize, size, crop, crop_xyf, row_stream, row_pos, num_rows, max_count, u8ring, S, Rf, stream,
+                          px_rgb24{});
+}
+
+extern "C" int cer_frames_transform_boxes_yuv(const uint8_t *frames, const cer_yuv420 *yuv, int n_frames, int H, int W,
+                                              const int32_t *boxes, const int32_t *box_meta, const int32_t *box_data, int max_side,
+                                              int max_band_rows, int max_ksize, int size, int crop, const int32_t *crop_xyf,
+                                              int frames_per_group, float mean, float stdv, float *out, uint8_t *out_u8,
+                                              void *stream) {
+    const char *name = "frames_transform_boxes_yuv";
+    px_yuv420 pix;
+    const int rc = yuv420_pixel(name, yuv, H, W, &pix);
+    if (rc != CER_OK) return rc;
+    return fb_clip_launch(name, frames, n_frames, H, W, boxes, box_meta, box_data, max_side, max_band_rows, max_ksize, size, crop,
+                          crop_xyf, frames_per_group, mean, stdv, out, out_u8, stream, pix);
+}
+
+extern "C" int cer_frames_stream_append_boxes_yuv(const uint8_t *frames, const cer_yuv420 *yuv, int n_frames, int H, int W,
+                                                  const int32_t *boxes, const int32_t *box_meta, const int32_t *box_data,
+                                                  int max_side, int max_band_rows, int max_ksize, int size, int crop,
+                                                  const int32_t *crop_xyf, const int32_t *row_stream, const int32_t *row_pos,
+                                                  int num_rows, int max_count, uint8_t *u8ring, int S, int Rf, void *stream) {
+    const char *name = "frames_stream_append_boxes_yuv";
+    px_yuv420 pix;
+    const int rc = yuv420_pixel(name, yuv, H, W, &pix);
+    if (rc != CER_OK) return rc;
+    return fb_ring_launch(name, frames, n_frames, H, W, boxes, box_meta, box_data, max_side, max_band_rows, max_ksize, size, crop,
+                          crop_xyf, row_stream, row_pos, num_rows, max_count, u8ring, S, Rf, stream, pix);
 }

@@ -27,6 +27,65 @@ struct FramesArgs {
     int H, W, hks, vks, size, crop, max_rows;
 };
 
+// Pixel:  size_t frame_bytes(int H, int W)                     bytes of one packed H x W frame
+//         Row    row(const uint8_t *img, int W, int y)         row y of the frame at img, 0 <= y < H
+//         void   get(const Row &r, int x, int (&px)[3])        R, G, B of its pixel x, 0 <= x < W: loads at x itself and
+//                                                              at addresses derived from it, so a clamped x reads in bounds
+struct px_rgb24 {
+    static constexpr bool packed_rgb = true;  // [H][W][3] as the LDS tile wants it: staged with 16-byte copies
+    struct Row {
+        const uint8_t *p;
+    };
+    __device__ __forceinline__ size_t frame_bytes(int H, int W) const { return (size_t)H * W * 3; }
+    __device__ __forceinline__ Row row(const uint8_t *img, int W, int y) const { return Row{img + (size_t)y * W * 3}; }
+    __device__ __forceinline__ void get(const Row &r, int x, int (&px)[3]) const {
+        const uint8_t *s = r.p + (size_t)x * 3;
+        px[0] = s[0]; px[1] = s[1]; px[2] = s[2];
+    }
+};
+
+// 8-bit 4:2:0, H * 3 / 2 rows of W bytes: the Y plane [H][W], then the chroma of sample (x >> 1, y >> 1) at
+// uoff / voff + (y >> 1) * crow + (x >> 1) * cpx.  NV12: (H W, H W + 1, W, 2); I420: (H W, H W + H W / 4, W / 2, 1).
+struct px_yuv420 {
+    static constexpr bool packed_rgb = false;
+    int uoff, voff, crow, cpx;
+    int cy, crv, cgu, cgv, cbu, yoff;
+    struct Row {
+        const uint8_t *y, *u, *v;
+    };
+    __device__ __forceinline__ size_t frame_bytes(int H, int W) const { return (size_t)H * W / 2 * 3; }
+    __device__ __forceinline__ Row row(const uint8_t *img, int W, int y) const {
+        const uint8_t *c = img + (size_t)(y >> 1) * crow;
+        return Row{img + (size_t)y * W, c + uoff, c + voff};
+    }
+    __device__ __forceinline__ void get(const Row &r, int x, int (&px)[3]) const {
+        const int ci = (x >> 1) * cpx;
+        const int c = cy * ((int)r.y[x] - yoff) + (1 << (CER_YUV_PREC - 1)), u = (int)r.u[ci] - 128, v = (int)r.v[ci] - 128;
+        px[0] = clip8((c + crv * v) >> CER_YUV_PREC);
+        px[1] = clip8((c + cgu * u + cgv * v) >> CER_YUV_PREC);
+        px[2] = clip8((c + cbu * u) >> CER_YUV_PREC);
+    }
+};
+
+// What the 4:2:0 entries refuse about the picture and the conversion, and the functor of what they accept.
+inline int yuv420_pixel(const char *name, const cer_yuv420 *d, int H, int W, px_yuv420 *px) {
+    if (!d) return cer_set_error(CER_ERR_INVALID_ARG, "%s: null pointer", name);
+    if (H < 2 || W < 2 || (H & 1) || (W & 1))
+        return cer_set_error(CER_ERR_INVALID_ARG, "%s: a 4:2:0 picture needs even H and W, got %d x %d", name, H, W);
+    if ((size_t)H * W > (size_t)1 << 29)
+        return cer_set_error(CER_ERR_INVALID_ARG, "%s: a 4:2:0 picture of %d x %d exceeds 2^29 pixels", name, H, W);
+    if (d->layout != CER_YUV_NV12 && d->layout != CER_YUV_I420)
+        return cer_set_error(CER_ERR_INVALID_ARG, "%s: layout = %d is neither CER_YUV_NV12 nor CER_YUV_I420", name, d->layout);
+    const int32_t k[5] = {d->cy, d->crv, d->cgu, d->cgv, d->cbu};
+    for (int i = 0; i < 5; ++i)
+        if (k[i] < -(1 << 20) || k[i] > (1 << 20))
+            return cer_set_error(CER_ERR_INVALID_ARG, "%s: a conversion coefficient of %d lies beyond +-2^20 (int32 sums)", name, k[i]);
+    if (d->yoff < 0 || d->yoff > 255) return cer_set_error(CER_ERR_INVALID_ARG, "%s: yoff = %d is outside 0 .. 255", name, d->yoff);
+    const int nv12 = d->layout == CER_YUV_NV12, hw = H * W;
+    *px = px_yuv420{hw, nv12 ? hw + 1 : hw + hw / 4, nv12 ? W : W / 2, nv12 ? 2 : 1, d->cy, d->crv, d->cgu, d->cgv, d->cbu, d->yoff};
+    return CER_OK;
+}
+
 // LDS of one block: the staged input rows, the horizontally resampled rows, the two coefficient tiles
 inline size_t frames_lds_bytes(int max_band_rows, int W, int crop) {
     return (((size_t)max_band_rows * W * 3 + 15) & ~(size_t)15) + (((size_t)max_band_rows * crop * 3 + 15) & ~(size_t)15) +
@@ -36,8 +95,8 @@ inline size_t frames_lds_bytes(int max_band_rows, int W, int crop) {
 // Place:  int  source(int f)                                   the packed input frame that launch frame f reads
 //         void entry(int f, int &x1, int &y1, int &flip)       its crop entry
 //         void store(int f, int c, int yy, int xc, int v)      where byte v of channel c, cropped row yy, column xc goes
-template <class Place>
-__global__ __launch_bounds__(256) void frames_transform_kernel(FramesArgs p, Place place) {
+template <class Place, class Pixel>
+__global__ __launch_bounds__(256) void frames_transform_kernel(FramesArgs p, Place place, Pixel pix) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fr_smem[];
     const int f = blockIdx.y, band = blockIdx.x, tid = threadIdx.x;
     int x1, y1, flip;
@@ -64,25 +123,47 @@ __global__ __launch_bounds__(256) void frames_transform_kernel(FramesArgs p, Pla
             vkl[i] = j < p.vks ? p.vk[(size_t)(y1 + yy0 + ry) * p.vks + j] : 0;
         }
     }
-    const uint8_t *g = p.frames + ((size_t)place.source(f) * p.H + r0) * rowb;
-    const size_t nbytes = (size_t)rows * rowb;
-    if (((reinterpret_cast<uintptr_t>(g) | nbytes) & 15) == 0) {
-        // four loads in flight per thread before the first LDS store (a load-store-per-iteration loop serialises the
-        // HBM latency: one band is only ~10 loads per thread).  Every load is issued, at an index clamped into the band, and
-        // only the stores are predicated: values that are loaded under a condition end up in scratch memory.
-        const uint4 *g4 = reinterpret_cast<const uint4 *>(g);
-        uint4 *s4 = reinterpret_cast<uint4 *>(src);
-        const size_t n16 = nbytes / 16;
-        for (size_t i = tid; i < n16; i += 4 * 256) {
-            uint4 v[4];
+    if constexpr (Pixel::packed_rgb) {
+        const uint8_t *g = p.frames + ((size_t)place.source(f) * p.H + r0) * rowb;
+        const size_t nbytes = (size_t)rows * rowb;
+        if (((reinterpret_cast<uintptr_t>(g) | nbytes) & 15) == 0) {
+            // four loads in flight per thread before the first LDS store (a load-store-per-iteration loop serialises the
+            // HBM latency: one band is only ~10 loads per thread).  Every load is issued, at an index clamped into the
+            // band, and only the stores are predicated: values that are loaded under a condition end up in scratch memory.
+            const uint4 *g4 = reinterpret_cast<const uint4 *>(g);
+            uint4 *s4 = reinterpret_cast<uint4 *>(src);
+            const size_t n16 = nbytes / 16;
+            for (size_t i = tid; i < n16; i += 4 * 256) {
+                uint4 v[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = g4[min(i + u * 256, n16 - 1)];
+                for (int u = 0; u < 4; ++u) v[u] = g4[min(i + u * 256, n16 - 1)];
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (i + u * 256 < n16) s4[i + u * 256] = v[u];
+                for (int u = 0; u < 4; ++u)
+                    if (i + u * 256 < n16) s4[i + u * 256] = v[u];
+            }
+        } else {
+            for (size_t i = tid; i < nbytes; i += 256) src[i] = g[i];
         }
     } else {
-        for (size_t i = tid; i < nbytes; i += 256) src[i] = g[i];
+        // the same tile, converted on the way in: one thread per pixel of the band's rows, four in flight.  Every load is
+        // issued, at a pixel clamped into the band (and its row into the frame), and only the LDS stores are predicated.
+        const uint8_t *img = p.frames + (size_t)place.source(f) * pix.frame_bytes(p.H, p.W);
+        const int npx = rows * p.W;
+        for (int i = tid; i < npx; i += 4 * 256) {
+            int v[4][3];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int q = min(i + u * 256, npx - 1);
+                const int r = q / p.W, x = q - r * p.W;
+                pix.get(pix.row(img, p.W, min(r0 + r, p.H - 1)), x, v[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (i + u * 256 < npx) {
+                    uint8_t *d = src + (size_t)(i + u * 256) * 3;
+                    d[0] = (uint8_t)v[u][0]; d[1] = (uint8_t)v[u][1]; d[2] = (uint8_t)v[u][2];
+                }
+        }
     }
     __syncthreads();
     // horizontal pass, column already flipped

@@ -9,6 +9,7 @@
 //   cer_frames_stream_append   packed raw frames [n][H][W][3] -> GroupScale -> crop -> flip -> ring slot.  This is
 //                              frames_transform_kernel (frames_kernel.h) with the streamed way to name a frame: the same band
 //                              staging, dword fast path and generic path as cer_frames_transform, so the same bytes.
+//                              cer_frames_stream_append_yuv: the same on NV12 / I420 frames, as cer_frames_transform_yuv.
 //   cer_frames_stream_gather   ring slots -> fp32 [M][3][crop][crop] = frame_px(byte), the tensor the visual backbone takes.
 //                              HBM-bound (3 crop^2 bytes in, 12 crop^2 out per frame); no LDS: a thread turns 16 pixels (three
 //                              16-byte loads) into four float4 stores per channel plane, and a block's stores of one plane
@@ -90,11 +91,13 @@ using namespace cer;
 
 #define FS_REFUSE(...) return cer_set_error(CER_ERR_INVALID_ARG, __VA_ARGS__)
 
-extern "C" int cer_frames_stream_append(const uint8_t *frames, int n_frames, int H, int W, const int32_t *hbounds,
-                                        const int32_t *hcoef, int hksize, const int32_t *vbounds, const int32_t *vcoef,
-                                        int vksize, int size, int crop, const int32_t *crop_xyf, int max_band_rows,
-                                        const int32_t *row_stream, const int32_t *row_pos, int num_rows, int max_count,
-                                        uint8_t *u8ring, int S, int Rf, void *stream) {
+// the one body of both append entries; `pix` says how a pixel is read
+template <class Pixel>
+static int frames_stream_append_launch(const uint8_t *frames, int n_frames, int H, int W, const int32_t *hbounds,
+                                       const int32_t *hcoef, int hksize, const int32_t *vbounds, const int32_t *vcoef, int vksize,
+                                       int size, int crop, const int32_t *crop_xyf, int max_band_rows, const int32_t *row_stream,
+                                       const int32_t *row_pos, int num_rows, int max_count, uint8_t *u8ring, int S, int Rf,
+                                       void *stream, Pixel pix) {
     if (!frames || !hbounds || !hcoef || !vbounds || !vcoef || !crop_xyf || !row_stream || !row_pos || !u8ring)
         FS_REFUSE("frames_stream_append: null pointer");
     if (n_frames < 1 || num_rows < 1 || max_count < 1 || S < 1 || H < 1 || W < 1 || size < 1 || crop < 1 || hksize < 1 ||
@@ -113,11 +116,34 @@ extern "C" int cer_frames_stream_append(const uint8_t *frames, int n_frames, int
     a.frames = frames; a.hb = hbounds; a.hk = hcoef; a.vb = vbounds; a.vk = vcoef;
     a.H = H; a.W = W; a.hks = hksize; a.vks = vksize; a.size = size; a.crop = crop; a.max_rows = max_band_rows;
     const FramesRingPlace place{crop_xyf, row_stream, row_pos, u8ring, n_frames, S, Rf, size, crop};
-    auto k = frames_transform_kernel<FramesRingPlace>;
+    auto k = frames_transform_kernel<FramesRingPlace, Pixel>;
     if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    CER_LAUNCH(k, dim3((crop + FR_BAND - 1) / FR_BAND, num_rows), dim3(256), lds, (hipStream_t)stream, a, place);
+    CER_LAUNCH(k, dim3((crop + FR_BAND - 1) / FR_BAND, num_rows), dim3(256), lds, (hipStream_t)stream, a, place, pix);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
+}
+
+extern "C" int cer_frames_stream_append(const uint8_t *frames, int n_frames, int H, int W, const int32_t *hbounds,
+                                        const int32_t *hcoef, int hksize, const int32_t *vbounds, const int32_t *vcoef,
+                                        int vksize, int size, int crop, const int32_t *crop_xyf, int max_band_rows,
+                                        const int32_t *row_stream, const int32_t *row_pos, int num_rows, int max_count,
+                                        uint8_t *u8ring, int S, int Rf, void *stream) {
+    return frames_stream_append_launch(frames, n_frames, H, W, hbounds, hcoef, hksize, vbounds, vcoef, vksize, size, crop,
+                                       crop_xyf, max_band_rows, row_stream, row_pos, num_rows, max_count, u8ring, S, Rf, stream,
+                                       px_rgb24{});
+}
+
+extern "C" int cer_frames_stream_append_yuv(const uint8_t *frames, const cer_yuv420 *yuv, int n_frames, int H, int W,
+                                            const int32_t *hbounds, const int32_t *hcoef, int hksize, const int32_t *vbounds,
+                                            const int32_t *vcoef, int vksize, int size, int crop, const int32_t *crop_xyf,
+                                            int max_band_rows, const int32_t *row_stream, const int32_t *row_pos, int num_rows,
+                                            int max_count, uint8_t *u8ring, int S, int Rf, void *stream) {
+    px_yuv420 pix;
+    const int rc = yuv420_pixel("frames_stream_append_yuv", yuv, H, W, &pix);
+    if (rc != CER_OK) return rc;
+    return frames_stream_append_launch(frames, n_frames, H, W, hbounds, hcoef, hksize, vbounds, vcoef, vksize, size, crop,
+                                       crop_xyf, max_band_rows, row_stream, row_pos, num_rows, max_count, u8ring, S, Rf, stream,
+                                       pix);
 }
 
 extern "C" int cer_frames_stream_gather(const uint8_t *u8ring, int S, int Rf, int crop, const int32_t *row_stream,

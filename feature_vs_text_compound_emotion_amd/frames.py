@@ -8,6 +8,7 @@ frames that are already resident in HBM.  The resize is bit-identical to ``PIL.I
 (``precompute_coeffs`` + ``normalize_coeffs_8bpc`` of Pillow's Resample.c, third-party, restated) once per
 geometry and the kernel does the two fixed-point passes.
 """
+import ctypes
 import math
 import random
 
@@ -154,6 +155,49 @@ def check_boxes(boxes, rows, max_side):
     return arr.astype(np.int32)
 
 
+PIXEL_FORMATS = ("rgb24", "nv12", "i420")
+YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}                    # (kr, kb)
+YUV_RANGES = {"limited": (255.0 / 219.0, 255.0 / 224.0, 16), "full": (1.0, 1.0, 0)}      # (luma scale, chroma scale, yoff)
+
+
+def yuv_coefficients(matrix="bt601", range="limited"):
+    """(cy, crv, cgu, cgv, cbu, yoff) of the 4:2:0 pixel formats: the YCbCr -> RGB matrix of (kr, kb) and the range's scales
+    in Python floats, each entry rounded to 2^14 fixed point.  With c = Y - yoff, u = U - 128, v = V - 128 and int32
+    arithmetic, R = clip8((cy c + crv v + 2^13) >> 14), G = clip8((cy c + cgu u + cgv v + 2^13) >> 14),
+    B = clip8((cy c + cbu u + 2^13) >> 14); every sum stays below 9.3e6 in magnitude."""
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"matrix = {matrix!r}: expected one of {sorted(YUV_MATRICES)}")
+    if range not in YUV_RANGES:
+        raise ValueError(f"range = {range!r}: expected one of {sorted(YUV_RANGES)}")
+    (kr, kb), (ys, cs, yoff) = YUV_MATRICES[matrix], YUV_RANGES[range]
+    kg = 1 - kr - kb
+    floats = (ys, 2 * (1 - kr) * cs, -2 * (1 - kb) * kb / kg * cs, -2 * (1 - kr) * kr / kg * cs, 2 * (1 - kb) * cs)
+    return tuple(round(x * 2 ** _lib.YUV_PREC) for x in floats) + (yoff,)
+
+
+def yuv_desc(pixel_format="rgb24", matrix="bt601", range="limited"):
+    """What a stream or transform keeps of its pixel format: None for packed RGB, the ``cer_yuv420`` of the C entries for
+    ``nv12`` / ``i420``.  Unknown names raise ValueError, whatever the format."""
+    if pixel_format not in PIXEL_FORMATS:
+        raise ValueError(f"pixel_format = {pixel_format!r}: expected one of {list(PIXEL_FORMATS)}")
+    coef = yuv_coefficients(matrix, range)
+    if pixel_format == "rgb24":
+        return None
+    return _lib.Yuv420Desc(_lib.YUV_NV12 if pixel_format == "nv12" else _lib.YUV_I420, *coef)
+
+
+def yuv_picture(rows, width):
+    """(H, W) of the picture a 4:2:0 frame of ``rows`` rows of ``width`` bytes holds: rows = H * 3 / 2, H and W even (an odd
+    H has no whole number of rows, so it shows as a row count that 3 does not divide)."""
+    rows, width = int(rows), int(width)
+    if rows < 3 or rows % 3:
+        raise ValueError(f"frames: {rows} rows are not H * 3 / 2 of a 4:2:0 picture with even H (the Y plane, then half as many "
+                         "chroma rows)")
+    if width < 2 or width % 2:
+        raise ValueError(f"frames: a 4:2:0 picture needs an even W, got {width}")
+    return rows // 3 * 2, width
+
+
 class FrameTransform:
     """``FrameTransform(size=48, crop=40, train=True)(frames_u8[B,L,H,W,3]) -> float32 [B,L,3,crop,crop]``.
 
@@ -164,10 +208,20 @@ class FrameTransform:
     box (x0, y0, x1, y1) as ``PIL.Image.crop`` does -- right and lower exclusive, zero outside the frame -- so the result is
     what the unboxed call gives the contiguous zero-padded slice; a box equal to the whole frame gives the unboxed bits.
     One launch for any mix of boxes (csrc/frames_box.hip); sides up to ``max_side``.
+
+    ``pixel_format``: ``"rgb24"`` (packed RGB, above) or the 8-bit 4:2:0 a decoder hands out, converted where the kernel
+    reads a pixel.  A frame of an H x W picture, H and W even, is then H * 3 / 2 rows of W bytes, uint8 [B, L, H * 3 / 2, W]:
+    the Y plane [H][W], then for ``"nv12"`` the interleaved chroma [H / 2][W / 2][2], U first, for ``"i420"`` the U plane
+    [H / 2][W / 2] and the V plane.  Pixel (x, y) takes the chroma sample (x >> 1, y >> 1) -- nearest siting -- and the
+    integers of ``yuv_coefficients(matrix, range)``; the result is the bits the RGB call gives the converted frames.  Boxes
+    stay in luma pixels.  An odd H or W, a wrong rank and unknown names raise ValueError before any launch.
     """
 
-    def __init__(self, size=48, crop=40, train=True, mean=0.5, std=0.5, max_side=BOX_MAX_SIDE):
+    def __init__(self, size=48, crop=40, train=True, mean=0.5, std=0.5, max_side=BOX_MAX_SIDE, pixel_format="rgb24",
+                 matrix="bt601", range="limited"):
         self.size, self.crop, self.train, self.mean, self.std = size, crop, train, float(mean), float(std)
+        self.pixel_format, self.matrix, self.range = pixel_format, matrix, range
+        self.yuv = yuv_desc(pixel_format, matrix, range)
         if isinstance(max_side, bool) or int(max_side) != max_side or not 1 <= max_side <= BOX_COORD:
             raise ValueError(f"max_side = {max_side!r}: must be an integer in 1 .. {BOX_COORD}")
         self.max_side = int(max_side)
@@ -202,7 +256,18 @@ class FrameTransform:
                 out[i, 0] = out[i, 1] = int(round((self.size - self.crop) / 2.0))
         return out
 
-    def __call__(self, frames, crop_xyf=None, return_u8=False, boxes=None):
+    def _clip(self, frames):
+        """The clip as a contiguous [B, L, ...] tensor and (B, L, H, W) of its pictures."""
+        if self.yuv is not None:      # the shape is looked at first, then the device
+            if not (torch.is_tensor(frames) and frames.dtype == torch.uint8 and frames.dim() in (3, 4)):
+                raise ValueError(f"FrameTransform: {self.pixel_format} frames are a uint8 tensor [B, L, H * 3 / 2, W], got "
+                                 f"{(frames.dtype, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
+            if frames.dim() == 3:
+                frames = frames.unsqueeze(0)
+            h, w = yuv_picture(frames.shape[2], frames.shape[3])
+            if not frames.is_cuda:
+                raise ValueError(f"FrameTransform: frames on {frames.device}; they must be on the GPU (there is no CPU fallback)")
+            return (frames.contiguous(), *frames.shape[:2], h, w)
         if not frames.is_cuda or frames.dtype != torch.uint8:
             raise RuntimeError("FrameTransform needs a uint8 CUDA tensor [B,L,H,W,3] (there is no CPU fallback)")
         if frames.dim() == 4:
@@ -210,7 +275,10 @@ class FrameTransform:
         b, l, h, w, c = frames.shape
         if c != 3:
             raise RuntimeError("FrameTransform: frames must be RGB, channels last")
-        frames = frames.contiguous()
+        return frames.contiguous(), b, l, h, w
+
+    def __call__(self, frames, crop_xyf=None, return_u8=False, boxes=None):
+        frames, b, l, h, w = self._clip(frames)
         if crop_xyf is None:
             crop_xyf = self.draw(b)
         crop_xyf = np.ascontiguousarray(crop_xyf, dtype=np.int32).reshape(b, 3)
@@ -227,19 +295,20 @@ class FrameTransform:
         step = 65535 // l * l if l <= 65535 else 0
         if step == 0:
             raise RuntimeError("FrameTransform: clip longer than 65535 frames")
-        flat_in, flat_out = frames.view(n, h, w, 3), out.view(n, 3, self.crop, self.crop)
+        flat_in, flat_out = frames.view(n, *frames.shape[2:]), out.view(n, 3, self.crop, self.crop)
         flat_u8 = u8.view(n, self.crop, self.crop, 3) if return_u8 else None
+        entry, how = (lib.cer_frames_transform, ()) if self.yuv is None else (lib.cer_frames_transform_yuv, (ctypes.byref(self.yuv),))
         for s in range(0, n, step):
             e = min(n, s + step)
-            check(lib.cer_frames_transform(ptr(flat_in[s:e]), e - s, h, w, ptr(hb), ptr(hk), hks, ptr(vb), ptr(vk), vks,
-                                           self.size, self.crop, ptr(cx[s // l:]), l, span, self.mean, self.std,
-                                           ptr(flat_out[s:e]), ptr(flat_u8[s:e]) if return_u8 else None,
-                                           current_stream()), "cer_frames_transform")
+            check(entry(ptr(flat_in[s:e]), *how, e - s, h, w, ptr(hb), ptr(hk), hks, ptr(vb), ptr(vk), vks,
+                        self.size, self.crop, ptr(cx[s // l:]), l, span, self.mean, self.std,
+                        ptr(flat_out[s:e]), ptr(flat_u8[s:e]) if return_u8 else None,
+                        current_stream()), "cer_frames_transform" + ("_yuv" if how else ""))
         return (out, u8) if return_u8 else out
 
     def _boxed(self, frames, crop_xyf, return_u8, boxes):
         from . import ops
-        b, l, h, w, _ = frames.shape
+        b, l = frames.shape[:2]
         if l > 65535:
             raise RuntimeError("FrameTransform: clip longer than 65535 frames")
         store = box_tables(self.size, self.max_side)
@@ -247,12 +316,12 @@ class FrameTransform:
         out = torch.empty((b, l, 3, self.crop, self.crop), dtype=torch.float32, device=frames.device)
         u8 = torch.empty((b, l, self.crop, self.crop, 3), dtype=torch.uint8, device=frames.device) if return_u8 else None
         n, step = b * l, 65535 // l * l
-        flat_in, flat_out = frames.view(n, h, w, 3), out.view(n, 3, self.crop, self.crop)
+        flat_in, flat_out = frames.view(n, *frames.shape[2:]), out.view(n, 3, self.crop, self.crop)
         flat_u8 = u8.view(n, self.crop, self.crop, 3) if return_u8 else None
         for s in range(0, n, step):
             e = min(n, s + step)
             ops.frames_transform_boxes(flat_in[s:e], bx[s:e], store, self.size, cx[s // l:e // l], l, self.mean, self.std,
-                                       flat_out[s:e], flat_u8[s:e] if return_u8 else None)
+                                       flat_out[s:e], flat_u8[s:e] if return_u8 else None, yuv=self.yuv)
         return (out, u8) if return_u8 else out
 
 
@@ -288,11 +357,16 @@ class FrameStream:
     one launch, a take one more of each, whatever the number of streams.  The crop is GroupCenterCrop's offset for every stream
     unless ``crop_xyf`` [S, 3] = (x1, y1, flip) per stream says otherwise.
 
+    ``pixel_format`` / ``matrix`` / ``range``: as for ``FrameTransform``.  Under ``"nv12"`` or ``"i420"`` a push brings
+    uint8 [M, H * 3 / 2, W], H and W even; everything else is as under ``"rgb24"``, and so are the ring's bytes for the
+    converted frames.  The format is the stream's, not a push's.
+
     A push that would leave more than ``hold`` untaken frames in a stream, bad counts, and a tensor that is not uint8 RGB on
-    the GPU raise ValueError before any launch and leave the state as it was."""
+    the GPU (or not a 4:2:0 frame of an even-sized picture, under those formats) raise ValueError before any launch and leave
+    the state as it was."""
 
     def __init__(self, streams, size=48, crop=40, hold=64, max_new=32, mean=0.5, std=0.5, device="cuda", crop_xyf=None,
-                 max_side=BOX_MAX_SIDE):
+                 max_side=BOX_MAX_SIDE, pixel_format="rgb24", matrix="bt601", range="limited"):
         for name, v in (("streams", streams), ("size", size), ("crop", crop), ("hold", hold), ("max_new", max_new),
                         ("max_side", max_side)):
             if isinstance(v, bool) or int(v) != v or v < 1:
@@ -306,7 +380,9 @@ class FrameStream:
             raise ValueError(f"FrameStream runs on the HIP kernels only (no CPU fallback), got device {device!r}")
         self.streams, self.size, self.crop, self.hold, self.max_new = int(streams), int(size), int(crop), int(hold), int(max_new)
         self.ring_frames = hold_ring(self.hold, self.max_new)
-        self._xf = FrameTransform(self.size, self.crop, train=False, mean=mean, std=std, max_side=max_side)
+        self._xf = FrameTransform(self.size, self.crop, train=False, mean=mean, std=std, max_side=max_side,
+                                  pixel_format=pixel_format, matrix=matrix, range=range)
+        self.pixel_format = pixel_format
         self.max_side = self._xf.max_side
         if crop_xyf is None:
             crop_xyf = self._xf.draw(self.streams)
@@ -353,7 +429,15 @@ class FrameStream:
         if boxes is not None:
             check_boxes(boxes, sum(counts), self.max_side)
         f = frames_u8
-        if not (torch.is_tensor(f) and f.is_cuda and f.dtype == torch.uint8 and f.dim() == 4 and f.shape[3] == 3):
+        if self._xf.yuv is not None:      # the shape is looked at first, then the device
+            if not (torch.is_tensor(f) and f.dtype == torch.uint8 and f.dim() == 3):
+                raise ValueError(f"frames: expected raw {self.pixel_format} frames as a uint8 tensor [M, H * 3 / 2, W], got "
+                                 f"{(f.dtype, tuple(f.shape)) if torch.is_tensor(f) else type(f)}")
+            if f.shape[0]:
+                yuv_picture(f.shape[1], f.shape[2])
+            if not f.is_cuda:
+                raise ValueError(f"frames: on {f.device}; they must be on the GPU (there is no CPU fallback)")
+        elif not (torch.is_tensor(f) and f.is_cuda and f.dtype == torch.uint8 and f.dim() == 4 and f.shape[3] == 3):
             raise ValueError("frames: expected raw RGB frames as a uint8 GPU tensor [M, H, W, 3] (there is no CPU fallback), got "
                              f"{(f.dtype, f.device, tuple(f.shape)) if torch.is_tensor(f) else type(f)}")
         if f.shape[0] != sum(counts):
@@ -370,8 +454,8 @@ class FrameStream:
         counts = self.check_push(frames_u8, counts, boxes)
         if not sum(counts):
             return
-        frames = frames_u8.contiguous()
-        _, h, w, _ = frames.shape
+        frames, yuv = frames_u8.contiguous(), self._xf.yuv
+        h, w = frames.shape[1:3] if yuv is None else yuv_picture(frames.shape[1], frames.shape[2])
         if boxes is None:
             tables, _, _, span = self._xf._get_tables(h, w, frames.device)
         else:
@@ -383,10 +467,12 @@ class FrameStream:
         first = [b + n for b, n in zip(self._base, self.frames_seen)]
         if boxes is None:
             row_stream, row_pos = ops.stream_row_table(first, counts, self.device)
-            ops.frames_stream_append(frames, tables, span, self.size, self._cx, row_stream, row_pos, max(counts), self.ring)
+            ops.frames_stream_append(frames, tables, span, self.size, self._cx, row_stream, row_pos, max(counts), self.ring,
+                                     yuv=yuv)
         else:
             row_stream, row_pos, bx = ops.stream_row_box_table(first, counts, boxes, self.device)
-            ops.frames_stream_append_boxes(frames, bx, store, self.size, self._cx, row_stream, row_pos, max(counts), self.ring)
+            ops.frames_stream_append_boxes(frames, bx, store, self.size, self._cx, row_stream, row_pos, max(counts), self.ring,
+                                           yuv=yuv)
         self.frames_seen = [n + c for n, c in zip(self.frames_seen, counts)]
 
     def check_take(self, pairs):

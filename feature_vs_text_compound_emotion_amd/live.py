@@ -72,7 +72,9 @@ class AVStream:
             int16 PCM as ``LogMelStream.push`` takes it with ``audio_counts``; either side may be absent.  ``extra[m]``
             [M, embedding_dim[m]] float32: the rows of every further modality of the model (``bert``) for the new frames.
             ``video_boxes`` [M, 4] host integers: ``video`` holds full camera frames and frame m is cropped to its face box
-            (x0, y0, x1, y1) first, as ``FrameStream.push(..., boxes=)`` does (sides up to ``max_side``).
+            (x0, y0, x1, y1) first, as ``FrameStream.push(..., boxes=)`` does (sides up to ``max_side``).  A session built
+            with ``video_format="nv12"`` or ``"i420"`` (and ``video_matrix``, ``video_range``: ``FrameStream``'s
+            ``pixel_format``, ``matrix``, ``range``) takes the decoder's 4:2:0 frames instead, uint8 [M, H * 3 / 2, W].
             -> (logits [P, n_cls], counts): every frame that became paired in this call, stream-major, each stream's frames in
             time order (the row order of ``push_ragged``); counts[s] of them belong to stream s.  Nothing paired: an empty
             [0, n_cls] and no model launch.
@@ -99,7 +101,7 @@ class AVStream:
 
     def __init__(self, model, streams, fps, *, sample_rate=16000, channels=1, resample=None, size=48, crop=40, hold=64, lead=8,
                  max_new=32, max_samples=4096, encoder_batch=8, audio_backbone=None, decisions=None,
-                 max_side=1024):
+                 max_side=1024, video_format="rgb24", video_matrix="bt601", video_range="limited"):
         cls = CANStream if isinstance(model, CAN) else LFANStream
         if not isinstance(model, cls._model_class):
             raise TypeError(f"AVStream needs an LFAN or a CAN (JMT / MT attend over time and are not causal), got "
@@ -125,7 +127,7 @@ class AVStream:
         self.model, self.streams, self.fps, self.hold, self.lead, self.max_new = model, int(streams), fps, int(hold), int(lead), int(max_new)
         device = next(model.parameters()).device
         self.frame_stream = FrameStream(streams, size=size, crop=crop, hold=hold, max_new=max_new, device=device,
-                                        max_side=max_side)
+                                        max_side=max_side, pixel_format=video_format, matrix=video_matrix, range=video_range)
         self.audio_stream = LogMelStream(streams, 1.0 / fps, max_samples=max_samples, device=device, sample_rate=sample_rate,
                                          channels=channels, resample=resample)   # hop_sec: the expression of audio_features
         self.model_stream = cls(model, streams, max_new=max_new, encoder_batch=encoder_batch)

@@ -2027,19 +2027,37 @@ def _i32_table(t, name, shape, like):
                          f"{(t.dtype, t.device, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
 
 
-def frames_stream_append(frames, tables, span, size, crop_xyf, row_stream, row_pos, max_count, u8ring):
+def _yuv_frames(frames, yuv, like):
+    """The check of 4:2:0 frames that the ``yuv=`` forms of the frame wrappers share: ``frames`` uint8 [n, H * 3 / 2, W] of
+    an H x W picture, H and W even, on the GPU of ``like``; ``yuv`` the ``cer_yuv420`` of ``frames.yuv_desc``.
+    Returns (n, H, W)."""
+    from .frames import yuv_picture
+    if not isinstance(yuv, _lib.Yuv420Desc):
+        raise ValueError(f"yuv: expected the descriptor of frames.yuv_desc, got {type(yuv).__name__}")
+    if not (torch.is_tensor(frames) and frames.is_cuda and frames.device == like.device and frames.dtype == torch.uint8
+            and frames.is_contiguous() and frames.dim() == 3 and frames.shape[0] >= 1):
+        raise ValueError(f"frames: expected a contiguous uint8 [n >= 1, H * 3 / 2, W] tensor on the GPU ({like.device}), got "
+                         f"{(frames.dtype, frames.device, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
+    return (frames.shape[0], *yuv_picture(frames.shape[1], frames.shape[2]))
+
+
+def frames_stream_append(frames, tables, span, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None):
     """GroupScale(size) -> crop -> flip of the raw frames ``frames`` [n, H, W, 3] uint8 into the ring ``u8ring``
     [S, Rf, crop, crop, 3]: row m of the row table (``stream_row_table``) is frame m and lands in slot
     (row_stream[m], row_pos[m] % Rf).  ``tables``: (hbounds, hcoef, vbounds, vcoef) of ``frames.resample_tables`` for
     (W -> size, H -> size) as int32 GPU tensors; ``span``: the most input rows one band of output rows needs;
     ``crop_xyf`` int32 [S, 3]: (x1, y1, flip) per stream; ``max_count``: the most rows any one stream has in the table.
-    The bytes are ``return_u8`` of ``FrameTransform`` for the same frame and crop entry."""
+    The bytes are ``return_u8`` of ``FrameTransform`` for the same frame and crop entry.  ``yuv``: ``frames`` are 4:2:0
+    frames [n, H * 3 / 2, W] (``_yuv_frames``), converted where the kernel reads them; the tables stay those of H and W."""
     s, rf, crop = _u8_ring(u8ring)
-    if not (torch.is_tensor(frames) and frames.is_cuda and frames.device == u8ring.device and frames.dtype == torch.uint8
-            and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
+    if yuv is not None:
+        n, h, w = _yuv_frames(frames, yuv, u8ring)
+    elif not (torch.is_tensor(frames) and frames.is_cuda and frames.device == u8ring.device and frames.dtype == torch.uint8
+              and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
         raise ValueError("frames: expected a contiguous uint8 [n >= 1, H, W, 3] tensor on the GPU of the ring, got "
                          f"{(frames.dtype, frames.device, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
-    n, h, w, _ = frames.shape
+    else:
+        n, h, w, _ = frames.shape
     m = _row_table(row_stream, row_pos, u8ring)
     hb, hk, vb, vk = tables
     size = int(size)
@@ -2048,9 +2066,10 @@ def frames_stream_append(frames, tables, span, size, crop_xyf, row_stream, row_p
             raise ValueError(f"{name}: expected an int32 [size, k] GPU tensor")
         _i32_table(t, name, (size, rows if rows is not None else t.shape[1]), u8ring)
     _i32_table(crop_xyf, "crop_xyf", (s, 3), u8ring)
-    check(_lib.load().cer_frames_stream_append(ptr(frames), n, h, w, ptr(hb), ptr(hk), hk.shape[1], ptr(vb), ptr(vk), vk.shape[1],
-                                               size, crop, ptr(crop_xyf), int(span), ptr(row_stream), ptr(row_pos), m,
-                                               int(max_count), ptr(u8ring), s, rf, current_stream()), "cer_frames_stream_append")
+    entry, how = _yuv_entry("cer_frames_stream_append", yuv)
+    check(entry(ptr(frames), *how, n, h, w, ptr(hb), ptr(hk), hk.shape[1], ptr(vb), ptr(vk), vk.shape[1], size, crop,
+                ptr(crop_xyf), int(span), ptr(row_stream), ptr(row_pos), m, int(max_count), ptr(u8ring), s, rf, current_stream()),
+          entry.__name__)
     if STREAM_TRACE is not None:
         STREAM_TRACE.append(("frames_append", 0))
 
@@ -2070,32 +2089,42 @@ def stream_row_box_table(positions, counts, boxes, device):
     return table[:m], table[m:2 * m], table[2 * m:].view(m, 4)
 
 
-def _box_args(frames, boxes, store, size, like):
+def _yuv_entry(name, yuv):
+    """The C entry ``name`` or its ``_yuv`` sibling, and the arguments the sibling takes after ``frames``."""
+    return (getattr(_lib.load(), name), ()) if yuv is None else (getattr(_lib.load(), name + "_yuv"), (ctypes.byref(yuv),))
+
+
+def _box_args(frames, boxes, store, size, like, yuv=None):
     """The checks the two boxed entries share.  Returns (n, H, W, meta, data)."""
-    if not (torch.is_tensor(frames) and frames.is_cuda and frames.device == like.device and frames.dtype == torch.uint8
-            and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
+    if yuv is not None:
+        n, h, w = _yuv_frames(frames, yuv, like)
+    elif not (torch.is_tensor(frames) and frames.is_cuda and frames.device == like.device and frames.dtype == torch.uint8
+              and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
         raise ValueError(f"frames: expected a contiguous uint8 [n >= 1, H, W, 3] tensor on the GPU ({like.device}), got "
                          f"{(frames.dtype, frames.device, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
+    else:
+        n, h, w, _ = frames.shape
     if store.size != int(size):
         raise ValueError(f"store: built for size {store.size}, not {size}")
     if not torch.is_tensor(boxes) or boxes.dim() != 2:
         raise ValueError("boxes: expected an int32 [rows, 4] GPU tensor")
     _i32_table(boxes, "boxes", (boxes.shape[0], 4), like)
     meta, data = store.on(like.device)
-    return frames.shape[0], frames.shape[1], frames.shape[2], meta, data
+    return n, h, w, meta, data
 
 
-def frames_transform_boxes(frames, boxes, store, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None):
+def frames_transform_boxes(frames, boxes, store, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None, yuv=None):
     """``Image.crop(boxes[f])`` -> GroupScale(size) -> crop -> flip -> ToTensor -> Normalize of full frames ``frames``
     [n, H, W, 3] uint8 into ``out`` [n, 3, crop, crop] float32 (and ``out_u8`` [n, crop, crop, 3]).  ``boxes`` int32 [n, 4]
     on the GPU = (x0, y0, x1, y1), right and lower exclusive, zero outside the frame; the kernel clamps what it is given
     (coordinates into +-2^20, sides into 1 .. ``store.max_side``), so a table nobody vetted gives wrong numbers and no
     access outside ``frames``.  ``store``: ``frames.box_tables(size, max_side)``; ``crop_xyf`` int32 [groups, 3] on the GPU,
-    one entry per ``frames_per_group`` frames."""
+    one entry per ``frames_per_group`` frames.  ``yuv``: ``frames`` are 4:2:0 frames [n, H * 3 / 2, W] (``_yuv_frames``); the
+    boxes stay in luma pixels and what lies outside the picture is RGB 0."""
     if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4
             and out.shape[1] == 3 and out.shape[2] == out.shape[3]):
         raise ValueError("out: expected a contiguous float32 [n, 3, crop, crop] GPU tensor")
-    n, h, w, meta, data = _box_args(frames, boxes, store, size, out)
+    n, h, w, meta, data = _box_args(frames, boxes, store, size, out, yuv)
     crop, g = out.shape[2], int(frames_per_group)
     if out.shape[0] != n or boxes.shape[0] != n or g < 1:
         raise ValueError(f"out / boxes: expected {n} rows, got {out.shape[0]} and {boxes.shape[0]}")
@@ -2103,25 +2132,26 @@ def frames_transform_boxes(frames, boxes, store, size, crop_xyf, frames_per_grou
     if out_u8 is not None and not (torch.is_tensor(out_u8) and out_u8.is_cuda and out_u8.device == out.device and out_u8.dtype == torch.uint8
                                    and out_u8.is_contiguous() and tuple(out_u8.shape) == (n, crop, crop, 3)):
         raise ValueError(f"out_u8: expected a contiguous uint8 [{n}, {crop}, {crop}, 3] tensor on the GPU of out")
-    check(_lib.load().cer_frames_transform_boxes(ptr(frames), n, h, w, ptr(boxes), ptr(meta), ptr(data), store.max_side,
-                                                 store.max_rows, store.max_ks, int(size), crop, ptr(crop_xyf), g, float(mean),
-                                                 float(std), ptr(out), ptr(out_u8), current_stream()), "cer_frames_transform_boxes")
+    entry, how = _yuv_entry("cer_frames_transform_boxes", yuv)
+    check(entry(ptr(frames), *how, n, h, w, ptr(boxes), ptr(meta), ptr(data), store.max_side, store.max_rows, store.max_ks,
+                int(size), crop, ptr(crop_xyf), g, float(mean), float(std), ptr(out), ptr(out_u8), current_stream()),
+          entry.__name__)
 
 
-def frames_stream_append_boxes(frames, boxes, store, size, crop_xyf, row_stream, row_pos, max_count, u8ring):
+def frames_stream_append_boxes(frames, boxes, store, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None):
     """``frames_stream_append`` of full frames with one box per row: row m of the row table is packed frame m, cropped to
     ``boxes[m]`` as ``frames_transform_boxes`` does, and lands in slot (row_stream[m], row_pos[m] % Rf).  The bytes are
-    ``return_u8`` of ``FrameTransform(..., boxes=)`` for the same frame, box and crop entry."""
+    ``return_u8`` of ``FrameTransform(..., boxes=)`` for the same frame, box and crop entry.  ``yuv``: as there."""
     s, rf, crop = _u8_ring(u8ring)
-    n, h, w, meta, data = _box_args(frames, boxes, store, size, u8ring)
+    n, h, w, meta, data = _box_args(frames, boxes, store, size, u8ring, yuv)
     m = _row_table(row_stream, row_pos, u8ring)
     if boxes.shape[0] != m:
         raise ValueError(f"boxes: expected one box per row [{m}, 4], got {tuple(boxes.shape)}")
     _i32_table(crop_xyf, "crop_xyf", (s, 3), u8ring)
-    check(_lib.load().cer_frames_stream_append_boxes(ptr(frames), n, h, w, ptr(boxes), ptr(meta), ptr(data), store.max_side,
-                                                     store.max_rows, store.max_ks, int(size), crop, ptr(crop_xyf),
-                                                     ptr(row_stream), ptr(row_pos), m, int(max_count), ptr(u8ring), s, rf,
-                                                     current_stream()), "cer_frames_stream_append_boxes")
+    entry, how = _yuv_entry("cer_frames_stream_append_boxes", yuv)
+    check(entry(ptr(frames), *how, n, h, w, ptr(boxes), ptr(meta), ptr(data), store.max_side, store.max_rows, store.max_ks,
+                int(size), crop, ptr(crop_xyf), ptr(row_stream), ptr(row_pos), m, int(max_count), ptr(u8ring), s, rf,
+                current_stream()), entry.__name__)
     if STREAM_TRACE is not None:
         STREAM_TRACE.append(("frames_append_boxes", 0))
 

@@ -845,6 +845,55 @@ int cer_frames_stream_append_boxes(const uint8_t *frames, int n_frames, int H, i
                                    void *stream);
 
 /* ------------------------------------------------------------------------
+ * 8-bit 4:2:0 frames (NV12 from hardware decoders, I420 from software ones), converted to RGB where the kernel reads a pixel.
+ *
+ * A frame of an H x W picture, H and W even, is H * 3 / 2 rows of W bytes: the Y plane [H][W], then
+ *   CER_YUV_NV12: the interleaved chroma [H / 2][W / 2][2], U first;
+ *   CER_YUV_I420: the U plane [H / 2][W / 2], then the V plane [H / 2][W / 2].
+ * Pixel (x, y) takes the chroma sample (x >> 1, y >> 1): nearest siting, no interpolation.  With c = Y - yoff, u = U - 128,
+ * v = V - 128, h = 1 << (CER_YUV_PREC - 1), in int32 with an arithmetic (flooring) shift,
+ *   R = clip8((cy c + crv v + h) >> CER_YUV_PREC)
+ *   G = clip8((cy c + cgu u + cgv v + h) >> CER_YUV_PREC)
+ *   B = clip8((cy c + cbu u + h) >> CER_YUV_PREC)
+ * The five coefficients are the matrix (BT.601, BT.709, limited or full range) times 2^CER_YUV_PREC, rounded by the host.
+ *
+ * The four _yuv entries are their RGB siblings with `frames` [n_frames][H * 3 / 2][W] and a cer_yuv420; H and W stay the
+ * picture's, boxes stay in luma pixels.  Only the pixel fetch differs, so each gives the bits its sibling gives the
+ * converted RGB frames; a box tap outside the picture still contributes RGB 0 (not YUV 0 converted).  The chroma address is
+ * derived from the clamped luma index, so the tables are trusted exactly as little as by the siblings.
+ * Refused before any launch: what the sibling refuses (the unboxed pair in the sibling's words), a null descriptor, odd H or W, a picture above 2^29 pixels, an
+ * unknown layout, a coefficient beyond +-2^20 (the sums must stay in int32) and yoff outside 0 .. 255 (CER_ERR_INVALID_ARG).
+ * ---------------------------------------------------------------------- */
+#define CER_YUV_PREC 14
+#define CER_YUV_NV12 0
+#define CER_YUV_I420 1
+
+typedef struct cer_yuv420 {
+    int32_t layout;                  /* CER_YUV_NV12 or CER_YUV_I420 */
+    int32_t cy, crv, cgu, cgv, cbu;  /* times 2^CER_YUV_PREC */
+    int32_t yoff;                    /* 16 for limited range, 0 for full */
+} cer_yuv420;
+
+int cer_frames_transform_yuv(const uint8_t *frames, const cer_yuv420 *yuv, int n_frames, int H, int W, const int32_t *hbounds,
+                             const int32_t *hcoef, int hksize, const int32_t *vbounds, const int32_t *vcoef, int vksize,
+                             int size, int crop, const int32_t *crop_xyf, int frames_per_group, int max_band_rows, float mean,
+                             float stdv, float *out, uint8_t *out_u8, void *stream);
+int cer_frames_stream_append_yuv(const uint8_t *frames, const cer_yuv420 *yuv, int n_frames, int H, int W,
+                                 const int32_t *hbounds, const int32_t *hcoef, int hksize, const int32_t *vbounds,
+                                 const int32_t *vcoef, int vksize, int size, int crop, const int32_t *crop_xyf,
+                                 int max_band_rows, const int32_t *row_stream, const int32_t *row_pos, int num_rows,
+                                 int max_count, uint8_t *u8ring, int S, int Rf, void *stream);
+int cer_frames_transform_boxes_yuv(const uint8_t *frames, const cer_yuv420 *yuv, int n_frames, int H, int W,
+                                   const int32_t *boxes, const int32_t *box_meta, const int32_t *box_data, int max_side,
+                                   int max_band_rows, int max_ksize, int size, int crop, const int32_t *crop_xyf,
+                                   int frames_per_group, float mean, float stdv, float *out, uint8_t *out_u8, void *stream);
+int cer_frames_stream_append_boxes_yuv(const uint8_t *frames, const cer_yuv420 *yuv, int n_frames, int H, int W,
+                                       const int32_t *boxes, const int32_t *box_meta, const int32_t *box_data, int max_side,
+                                       int max_band_rows, int max_ksize, int size, int crop, const int32_t *crop_xyf,
+                                       const int32_t *row_stream, const int32_t *row_pos, int num_rows, int max_count,
+                                       uint8_t *u8ring, int S, int Rf, void *stream);
+
+/* ------------------------------------------------------------------------
  * Running video-level decisions of S live streams (csrc/decision_stream.hip): logit rows in, the three decisions of
  * metrics.py:118-139 out -- majority vote over the frame predictions, argmax of the mean logits, argmax of the mean softmax
  * probabilities -- over the first nc = C - (drop_last ? 1 : 0) columns.
