@@ -56,6 +56,9 @@ __global__ void l2norm_rows_kernel(const float *__restrict__ x, float *__restric
     for (int c = lane; c < cols; c += 64) yr[c] = xr[c] * inv;
 }
 
+// max that returns NaN when either operand is NaN (fmaxf returns the other one; F.max_pool2d propagates NaN)
+__device__ __forceinline__ float max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
+
 __global__ void maxpool2x2_nhwc_kernel(const float4 *__restrict__ x, float4 *__restrict__ y, int N, int H,
                                        int W, int C4) {
     const int Ho = H >> 1, Wo = W >> 1;
@@ -70,10 +73,10 @@ __global__ void maxpool2x2_nhwc_kernel(const float4 *__restrict__ x, float4 *__r
     const float4 *p = x + (((size_t)n * H + 2 * ho) * W + 2 * wo) * C4 + c;
     float4 a = p[0], b = p[C4], d = p[(size_t)W * C4], e = p[(size_t)W * C4 + C4];
     float4 r;
-    r.x = fmaxf(fmaxf(a.x, b.x), fmaxf(d.x, e.x));
-    r.y = fmaxf(fmaxf(a.y, b.y), fmaxf(d.y, e.y));
-    r.z = fmaxf(fmaxf(a.z, b.z), fmaxf(d.z, e.z));
-    r.w = fmaxf(fmaxf(a.w, b.w), fmaxf(d.w, e.w));
+    r.x = max_nan(max_nan(a.x, b.x), max_nan(d.x, e.x));
+    r.y = max_nan(max_nan(a.y, b.y), max_nan(d.y, e.y));
+    r.z = max_nan(max_nan(a.z, b.z), max_nan(d.z, e.z));
+    r.w = max_nan(max_nan(a.w, b.w), max_nan(d.w, e.w));
     y[idx] = r;
 }
 

@@ -116,7 +116,7 @@ __device__ __forceinline__ float act_apply(float v, int act, float a, float slop
     switch (act) {
         case CER_ACT_PRELU: return v >= 0.f ? v : v * a;
         case CER_ACT_LEAKY: return v >= 0.f ? v : v * slope;
-        case CER_ACT_RELU: return v > 0.f ? v : 0.f;
+        case CER_ACT_RELU: return v <= 0.f ? 0.f : v;   // (spelled so that NaN passes, as torch.relu)
         case CER_ACT_GELU: return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
         default: return v;
     }
@@ -279,7 +279,7 @@ __device__ __forceinline__ void epi_store4(const ConvArgs &p, const EpiCtx &e, i
         for (int t = 0; t < 4; ++t) o[t] = o[t] >= 0.f ? o[t] : o[t] * e.aa[t];
     } else if (p.act1 == CER_ACT_RELU) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) o[t] = o[t] > 0.f ? o[t] : 0.f;
+        for (int t = 0; t < 4; ++t) o[t] = o[t] <= 0.f ? 0.f : o[t];   // NaN passes
     }
     if (p.res || p.res_hi) {
         size_t roff;
@@ -341,7 +341,7 @@ __device__ __forceinline__ void epi_store4_direct(const ConvArgs &p, bool fast, 
         o[2] = o[2] >= 0.f ? o[2] : o[2] * a.z; o[3] = o[3] >= 0.f ? o[3] : o[3] * a.w;
     } else if (p.act1 == CER_ACT_RELU) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) o[t] = o[t] > 0.f ? o[t] : 0.f;
+        for (int t = 0; t < 4; ++t) o[t] = o[t] <= 0.f ? 0.f : o[t];   // NaN passes
     }
     if (p.res || p.res_hi) {
         size_t roff;

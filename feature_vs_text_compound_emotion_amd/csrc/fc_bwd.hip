@@ -1,7 +1,8 @@
 // fc_bwd.hip -- the elementwise part of a fully-connected layer's backward, in ONE pass over the rows (the released VGGish
 // embedding layers, audio_backbone._ReleasedEmbeddings):
 //
-//     dz = da * (a > 0)          (ReLU mask from the SAVED post-ReLU output a; no mask when a is absent: the output layer)
+//     dz = a <= 0 ? 0 : da       (torch's ReLU backward on the SAVED post-ReLU output a: a zero activation stops any gradient,
+//                                 a NaN activation lets it through; no mask when a is absent: the output layer)
 //     dz -> split bf16 planes hi / lo (the operand of the bf16x3 weight / data gradient) and / or fp32 (the fp32 mode)
 //     db = column sums of dz     (per-slab partials here, folded by a second small launch in slab order)
 //
@@ -42,7 +43,7 @@ template <int CPT> __device__ __forceinline__ void store_u16(uint16_t *p, const 
     }
 }
 
-// the saved activation of row r, columns c0 .. c0 + CPT - 1, as fp32 values (only their sign is used)
+// the saved activation of row r, columns c0 .. c0 + CPT - 1, as fp32 values (only a <= 0 is tested: NaN is not)
 template <int CPT, int KIND>
 __device__ __forceinline__ void load_act(const void *a, const uint16_t *alo, size_t off, float v[CPT]) {
     if constexpr (KIND == CER_FC_ACT_F32) {
@@ -109,8 +110,9 @@ __global__ __launch_bounds__(256) void fc_bwd_elem_kernel(const float *__restric
                     float z[CPT];
 #pragma unroll
                     for (int i = 0; i < CPT; ++i) {
-                        // a select, not a product: a zero activation stops a non-finite incoming gradient like ReLU's backward
-                        z[i] = m[u][i] > 0.f ? d[u][i] : 0.f;
+                        // a select, not a product: a zero activation stops a non-finite incoming gradient like ReLU's backward,
+                        // and a NaN activation lets the gradient through (torch's threshold_backward: a <= 0 ? 0 : g)
+                        z[i] = m[u][i] <= 0.f ? 0.f : d[u][i];
                         acc[i] += z[i];
                     }
                     const size_t off = (size_t)r * C + c0;

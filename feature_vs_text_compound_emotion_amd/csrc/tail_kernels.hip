@@ -223,6 +223,14 @@ __global__ __launch_bounds__(256) void col_sum_pair4_kernel(const float *__restr
 }
 
 // ------------------------------------------------------------- TCN glue
+// g * leaky'(.) from the saved OUTPUT o, as torch computes it: leaky_relu_backward is o > 0 ? g : g * slope (a NaN output takes
+// the slope branch); slope == 0 is ReLU, whose backward (threshold_backward) is the select o <= 0 ? 0 : g -- a zero activation
+// stops a non-finite gradient instead of turning it into NaN (inf * 0), and a NaN activation lets the gradient through.
+__device__ __forceinline__ float leaky_bwd(float g, float o, float slope) {
+    if (slope == 0.f) return o <= 0.f ? 0.f : g;
+    return o > 0.f ? g : g * slope;
+}
+
 // dz = dy * mask * leaky'(y)   (y = mask * leaky(z): sign(y) == sign(z) wherever mask != 0)
 __global__ void act_mask_bwd_kernel(const float4 *__restrict__ dy, const float4 *__restrict__ y,
                                     const float4 *__restrict__ mask, float4 *__restrict__ dz, size_t n4,
@@ -231,10 +239,10 @@ __global__ void act_mask_bwd_kernel(const float4 *__restrict__ dy, const float4 
     if (i >= n4) return;
     float4 g = dy[i], o = y[i], m = mask ? mask[i] : make_float4(1, 1, 1, 1);
     float4 r;
-    r.x = g.x * m.x * (o.x > 0.f ? 1.f : slope);
-    r.y = g.y * m.y * (o.y > 0.f ? 1.f : slope);
-    r.z = g.z * m.z * (o.z > 0.f ? 1.f : slope);
-    r.w = g.w * m.w * (o.w > 0.f ? 1.f : slope);
+    r.x = leaky_bwd(g.x * m.x, o.x, slope);
+    r.y = leaky_bwd(g.y * m.y, o.y, slope);
+    r.z = leaky_bwd(g.z * m.z, o.z, slope);
+    r.w = leaky_bwd(g.w * m.w, o.w, slope);
     dz[i] = r;
 }
 
@@ -247,10 +255,10 @@ __global__ void tblock_tail_bwd_kernel(const float4 *__restrict__ dout, const fl
     if (i >= n4) return;
     float4 g = dout[i], o = out[i], a = a2[i], m = mask2 ? mask2[i] : make_float4(1, 1, 1, 1);
     float4 u, z;
-    u.x = g.x * (o.x > 0.f ? 1.f : slope); z.x = u.x * m.x * (a.x > 0.f ? 1.f : slope);
-    u.y = g.y * (o.y > 0.f ? 1.f : slope); z.y = u.y * m.y * (a.y > 0.f ? 1.f : slope);
-    u.z = g.z * (o.z > 0.f ? 1.f : slope); z.z = u.z * m.z * (a.z > 0.f ? 1.f : slope);
-    u.w = g.w * (o.w > 0.f ? 1.f : slope); z.w = u.w * m.w * (a.w > 0.f ? 1.f : slope);
+    u.x = leaky_bwd(g.x, o.x, slope); z.x = leaky_bwd(u.x * m.x, a.x, slope);
+    u.y = leaky_bwd(g.y, o.y, slope); z.y = leaky_bwd(u.y * m.y, a.y, slope);
+    u.z = leaky_bwd(g.z, o.z, slope); z.z = leaky_bwd(u.z * m.z, a.z, slope);
+    u.w = leaky_bwd(g.w, o.w, slope); z.w = leaky_bwd(u.w * m.w, a.w, slope);
     du[i] = u;
     dz2[i] = z;
 }
@@ -445,7 +453,7 @@ __global__ void bn_rows_moments_finish_kernel(const float *__restrict__ x, const
         const double m2 = t2 - t1 * (t1 / (double)R);
         moments[c] = (double)R;
         moments[C + c] = k0 + t1 / (double)R;
-        moments[2 * C + c] = m2 > 0.0 ? m2 : 0.0;
+        moments[2 * C + c] = m2 < 0.0 ? 0.0 : m2;   // (NaN stays NaN)
     }
 }
 
@@ -928,7 +936,7 @@ __global__ void bn_rows_finish_kernel(const float *__restrict__ mean, float *__r
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     float var = ssd_to_invstd[c] / (float)R;   // sum (x - mean)^2
-    var = var > 0.f ? var : 0.f;
+    var = var < 0.f ? 0.f : var;   // (spelled so that a NaN variance stays NaN: a poisoned column's statistics are non-finite)
     ssd_to_invstd[c] = rsqrtf(var + eps);
     if (running_mean) {
         running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean[c];
@@ -944,7 +952,7 @@ __global__ void bn_rows_shifted_finish_kernel(float *__restrict__ s1_to_mean, fl
     if (c >= C) return;
     const double d1 = (double)s1_to_mean[c] / R, d2 = (double)s2_to_invstd[c] / R;
     double var = d2 - d1 * d1;
-    var = var > 0.0 ? var : 0.0;
+    var = var < 0.0 ? 0.0 : var;   // (NaN stays NaN)
     const float mean = (float)((double)shift[c] + d1);
     s1_to_mean[c] = mean;
     s2_to_invstd[c] = rsqrtf((float)var + eps);

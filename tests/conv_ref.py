@@ -53,7 +53,7 @@ def _act(v, act, alpha, slope):
     if act == ACT_LEAKY:
         return torch.where(v >= 0, v, v * slope)
     if act == ACT_RELU:
-        return torch.where(v > 0, v, torch.zeros_like(v))
+        return torch.where(v <= 0, torch.zeros_like(v), v)        # NaN passes, as torch.relu (non-finite values)
     if act == ACT_GELU:
         return 0.5 * v * (1.0 + torch.erf(v * 0.70710678118654752440))
     return v

@@ -48,7 +48,7 @@ def test_fc_bwd_matches_a_float64_restatement(r, c, kind, pitched):
     buf[:, c:] = float("nan")                     # the pitch's padding must never be read into the result
     da = buf[:, :c]                               # ld = c + 12 > c when pitched
     act, af = _act(kind, r, c, g)
-    want = da if af is None else torch.where(af > 0, da, torch.zeros_like(da))
+    want = da if af is None else torch.where(af <= 0, torch.zeros_like(da), da)      # torch's ReLU backward: a NaN activation passes
     res = ops.fc_bwd(da, act, out_split=True, out_f32=True)
     ref = ops.split_bf16(want.contiguous())
     assert torch.equal(res["split"].hi, ref.hi) and torch.equal(res["split"].lo, ref.lo)
@@ -72,7 +72,7 @@ def test_fc_bwd_odd_pitch_and_c_not_multiple_of_8():
     da = buf[:, :36]
     act = torch.relu(torch.randn(300, 36, generator=g)).cuda()
     res = ops.fc_bwd(da, act, out_split=True, out_f32=True)
-    want = torch.where(act > 0, da, torch.zeros_like(da))
+    want = torch.where(act <= 0, torch.zeros_like(da), da)
     assert torch.equal(res["f32"], want)
     assert (res["db"].double() - want.double().sum(0)).abs().max().item() < 1e-6 * want.abs().sum(0).max().item()
     with pytest.raises(ValueError):
