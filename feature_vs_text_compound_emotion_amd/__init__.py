@@ -15,9 +15,9 @@ def __getattr__(name):
     if name == "LogMelStream":
         from . import audio_stream
         return audio_stream.LogMelStream
-    if name == "FrameStream":
+    if name in ("FrameStream", "FrameTransform", "similarity_from_landmarks", "check_affines", "ARCFACE_TEMPLATE"):
         from . import frames
-        return frames.FrameStream
+        return getattr(frames, name)
     if name == "AVStream":
         from . import live
         return live.AVStream

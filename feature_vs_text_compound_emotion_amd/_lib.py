@@ -188,6 +188,15 @@ _SIGNATURES = {
                                                c_int, _P, c_int, c_float, c_float, _P, _P, _P]),
     "cer_frames_stream_append_boxes_yuv": (c_int, [_P, POINTER(Yuv420Desc), c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int,
                                                    c_int, c_int, _P, _P, _P, c_int, c_int, _P, c_int, c_int, _P]),
+    "cer_frames_affine_lds_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "cer_frames_transform_affine": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int,
+                                            c_float, c_float, _P, _P, _P]),
+    "cer_frames_stream_append_affine": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P,
+                                                c_int, c_int, _P, c_int, c_int, _P]),
+    "cer_frames_transform_affine_yuv": (c_int, [_P, POINTER(Yuv420Desc), c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, c_int,
+                                                c_int, _P, c_int, c_float, c_float, _P, _P, _P]),
+    "cer_frames_stream_append_affine_yuv": (c_int, [_P, POINTER(Yuv420Desc), c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int,
+                                                    c_int, c_int, _P, _P, _P, c_int, c_int, _P, c_int, c_int, _P]),
     "cer_decision_stream_push": (c_int, [POINTER(DecisionStreamDesc), _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cer_decision_stream_read": (c_int, [POINTER(DecisionStreamDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }

@@ -155,6 +155,134 @@ def check_boxes(boxes, rows, max_side):
     return arr.astype(np.int32)
 
 
+ALIGN_SIZE = 256        # default of ``align_size``: the side of the reference's aligned faces
+ARCFACE_TEMPLATE = ((38.2946, 51.6963), (73.5318, 51.5014), (56.0252, 71.7366), (41.5493, 92.3655), (70.7299, 92.2041))
+"""The ArcFace five-point template on a 112 x 112 face (left eye, right eye, nose, left mouth, right mouth), (x, y)."""
+
+
+class AffineGeometry:
+    """What the affine entries (csrc/frames_affine.hip) need of (align_size, size): Pillow's bounds and coefficients of
+    ``resample_tables(align_size, size)`` -- one table for both passes, the aligned face is square -- their tap count ``ks``
+    and ``span``, the most rows of the face one band of ``cer_frames_band_rows()`` output rows needs over every crop offset.
+    Built on the host once per (align_size, size) by ``affine_geometry``, uploaded once per device."""
+
+    def __init__(self, align_size, size):
+        self.align_size, self.size = int(align_size), int(size)
+        self.bounds, self.coef = resample_tables(self.align_size, self.size)
+        self.ks = int(self.coef.shape[1])
+        band = _lib.load().cer_frames_band_rows()
+        y0 = np.arange(self.size)
+        y1 = np.minimum(self.size, y0 + band) - 1
+        self.span = int((self.bounds[y1, 0] + self.bounds[y1, 1] - self.bounds[y0, 0]).max())
+        self._dev = {}
+
+    def lds_bytes(self, crop):
+        return int(_lib.load().cer_frames_affine_lds_bytes(self.align_size, self.span, self.ks, int(crop)))
+
+    def check_crop(self, crop):
+        """Refuse, by name, an ``align_size`` whose warped band and coefficient rows exceed the kernel's LDS."""
+        need = self.lds_bytes(crop)
+        if need > AFFINE_LDS_BYTES:
+            raise ValueError(f"align_size = {self.align_size}: the warped band of {self.span} rows and {self.ks}-tap coefficient rows "
+                             f"at size {self.size}, crop {crop} need {need} bytes of the {AFFINE_LDS_BYTES // 1024} KiB LDS")
+
+    def on(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.bounds).to(device), torch.from_numpy(self.coef).to(device))
+        return self._dev[key]
+
+
+AFFINE_LDS_BYTES = 160 * 1024     # what one block of csrc/frames_affine.hip may hold
+AFFINE_MAX_ALIGN = 1 << 14        # FA_MAX_ALIGN
+_AFFINE_GEOMETRY = {}
+
+
+def check_align_size(align_size):
+    if isinstance(align_size, bool) or not isinstance(align_size, (int, np.integer)) or not 1 <= align_size <= AFFINE_MAX_ALIGN:
+        raise ValueError(f"align_size = {align_size!r}: must be an integer in 1 .. {AFFINE_MAX_ALIGN}")
+    return int(align_size)
+
+
+def affine_geometry(align_size, size):
+    """The ``AffineGeometry`` of (align_size, size), built by the first call that asks for it."""
+    key = (check_align_size(align_size), int(size))
+    if key not in _AFFINE_GEOMETRY:
+        _AFFINE_GEOMETRY[key] = AffineGeometry(*key)
+    return _AFFINE_GEOMETRY[key]
+
+
+def check_affines(affines, rows):
+    """Everything the aligned calls refuse about ``affines``, on the host: -> float64 numpy [rows, 6], Pillow's
+    ``Image.transform(..., AFFINE, data)`` coefficients per frame, all finite.  Affines are host numbers like ``counts``:
+    checking a GPU tensor would cost a synchronisation, so one is refused."""
+    if torch.is_tensor(affines):
+        if affines.is_cuda:
+            raise ValueError("affines: expected host numbers (a list, a numpy array or a CPU tensor), got a GPU tensor")
+        if affines.is_complex() or affines.dtype == torch.bool:
+            raise ValueError(f"affines: expected real numbers, got dtype {affines.dtype}")
+        arr = affines.numpy()
+    else:
+        try:
+            arr = np.asarray(affines)
+        except ValueError:
+            raise ValueError("affines: expected six coefficients per frame, got a ragged sequence") from None
+    if arr.size == 0 and rows == 0:
+        return np.zeros((0, 6), np.float64)
+    if arr.dtype.kind not in "iuf":
+        raise ValueError(f"affines: expected real numbers, got dtype {arr.dtype}")
+    if arr.ndim == 3:
+        arr = arr.reshape(-1, arr.shape[2])
+    if arr.shape != (rows, 6):
+        raise ValueError(f"affines: expected six coefficients (a0 .. a5) per frame [{rows}, 6], got {arr.shape}")
+    arr = np.ascontiguousarray(arr, dtype=np.float64)
+    if not np.isfinite(arr).all():
+        i = int(np.nonzero(~np.isfinite(arr).all(axis=1))[0][0])
+        raise ValueError(f"affines: affine {i} = {arr[i].tolist()} is not finite")
+    return arr
+
+
+def similarity_from_landmarks(landmarks, align_size=ALIGN_SIZE):
+    """Five landmarks per face -> the Pillow coefficients that align it: float64 numpy [M, 6] for ``aligned`` /
+    ``push_aligned``.  ``landmarks`` [M, 5, 2] (or [5, 2]) host numbers, (x, y) pixel coordinates of left eye, right eye,
+    nose, left mouth corner, right mouth corner, as a face detector returns them.
+
+    The non-reflective similarity u = a x - b y + tx, v = b x + a y + ty that takes the landmarks to
+    ``ARCFACE_TEMPLATE * align_size / 112`` in the least-squares sense is fitted in closed form in float64 (the direction the
+    reference's aligners fit), inverted, and converted from a map between integer pixel centres to Pillow's half-pixel
+    convention: Pillow samples output pixel (x, y) at A (x + 0.5, y + 0.5) + (a2, a5) and reads pixel centres at +0.5, so
+    a2 = t_x - 0.5 (a0 + a1) + 0.5 and a5 likewise.  Landmarks that all coincide have no fit and raise ValueError."""
+    align_size = check_align_size(align_size)
+    p = np.asarray(landmarks, dtype=np.float64)
+    if p.ndim == 2:
+        p = p[None]
+    if p.ndim != 3 or p.shape[1:] != (5, 2):
+        raise ValueError(f"landmarks: expected five (x, y) points per face [M, 5, 2], got {p.shape}")
+    if not np.isfinite(p).all():
+        raise ValueError("landmarks: a coordinate is not finite")
+    q = np.asarray(ARCFACE_TEMPLATE, dtype=np.float64) * align_size / 112.0
+    pm, qm = p.mean(axis=1, keepdims=True), q.mean(axis=0, keepdims=True)
+    pc, qc = p - pm, (q - qm)[None]
+    den = (pc * pc).sum(axis=(1, 2))
+    if (den == 0).any():
+        raise ValueError(f"landmarks: the five points of face {int(np.nonzero(den == 0)[0][0])} coincide; no similarity fits them")
+    a = (pc * qc).sum(axis=(1, 2)) / den
+    b = (pc[:, :, 0] * qc[:, :, 1] - pc[:, :, 1] * qc[:, :, 0]).sum(axis=1) / den
+    if ((a * a + b * b) == 0).any():
+        raise ValueError("landmarks: the fitted similarity has scale 0 and cannot be inverted")
+    tx = qm[0, 0] - (a * pm[:, 0, 0] - b * pm[:, 0, 1])
+    ty = qm[0, 1] - (b * pm[:, 0, 0] + a * pm[:, 0, 1])
+    # the inverse x = (a u + b v - (a tx + b ty)) / s, y = (-b u + a v - (-b tx + a ty)) / s, s = a^2 + b^2
+    s = a * a + b * b
+    ia, ib = a / s, b / s
+    out = np.empty((p.shape[0], 6), np.float64)
+    out[:, 0], out[:, 1], out[:, 3], out[:, 4] = ia, ib, -ib, ia
+    itx, ity = -(ia * tx + ib * ty), -(-ib * tx + ia * ty)
+    out[:, 2] = itx - 0.5 * (out[:, 0] + out[:, 1]) + 0.5
+    out[:, 5] = ity - 0.5 * (out[:, 3] + out[:, 4]) + 0.5
+    return out
+
+
 PIXEL_FORMATS = ("rgb24", "nv12", "i420")
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}                    # (kr, kb)
 YUV_RANGES = {"limited": (255.0 / 219.0, 255.0 / 224.0, 16), "full": (1.0, 1.0, 0)}      # (luma scale, chroma scale, yoff)
@@ -324,6 +452,39 @@ class FrameTransform:
                                        flat_out[s:e], flat_u8[s:e] if return_u8 else None, yuv=self.yuv)
         return (out, u8) if return_u8 else out
 
+    def aligned(self, frames, affines, crop_xyf=None, return_u8=False, align_size=ALIGN_SIZE):
+        """``__call__`` of full camera frames with one affine map per frame: ``affines`` [B, L, 6] or [B * L, 6] host
+        float64, Pillow's coefficients (``similarity_from_landmarks`` makes them from five landmarks).  Frame f is first
+        warped to an ``align_size`` x ``align_size`` face as ``PIL.Image.transform((A, A), AFFINE, affines[f], BILINEAR)``
+        does -- zero outside the frame -- so the result is what the plain call gives those faces.  One launch for any mix of
+        maps (csrc/frames_affine.hip); the pixel format is the transform's."""
+        from . import ops
+        geom = affine_geometry(align_size, self.size)
+        geom.check_crop(self.crop)
+        rank = 5 if self.yuv is None else 4
+        if torch.is_tensor(frames) and frames.dim() in (rank - 1, rank):      # the table is looked at first, like boxes
+            check_affines(affines, int(np.prod(frames.shape[:frames.dim() - rank + 2])))
+        frames, b, l, h, w = self._clip(frames)
+        if crop_xyf is None:
+            crop_xyf = self.draw(b)
+        crop_xyf = np.ascontiguousarray(crop_xyf, dtype=np.int32).reshape(b, 3)
+        if (crop_xyf[:, :2] < 0).any() or (crop_xyf[:, :2] + self.crop > self.size).any():
+            raise RuntimeError("FrameTransform: crop offset outside the resized image")
+        affines = check_affines(affines, b * l)
+        if l > 65535:
+            raise RuntimeError("FrameTransform: clip longer than 65535 frames")
+        cx, af = torch.from_numpy(crop_xyf).to(frames.device), torch.from_numpy(affines).to(frames.device)
+        out = torch.empty((b, l, 3, self.crop, self.crop), dtype=torch.float32, device=frames.device)
+        u8 = torch.empty((b, l, self.crop, self.crop, 3), dtype=torch.uint8, device=frames.device) if return_u8 else None
+        n, step = b * l, 65535 // l * l
+        flat_in, flat_out = frames.view(n, *frames.shape[2:]), out.view(n, 3, self.crop, self.crop)
+        flat_u8 = u8.view(n, self.crop, self.crop, 3) if return_u8 else None
+        for s in range(0, n, step):
+            e = min(n, s + step)
+            ops.frames_transform_affine(flat_in[s:e], af[s:e], geom, self.size, cx[s // l:e // l], l, self.mean, self.std,
+                                        flat_out[s:e], flat_u8[s:e] if return_u8 else None, yuv=self.yuv)
+        return (out, u8) if return_u8 else out
+
 
 def hold_ring(hold, max_new):
     """Slots of a ring in which up to ``hold`` rows wait while a push adds up to ``max_new``: the power of two >= their sum."""
@@ -346,6 +507,11 @@ class FrameStream:
                                             is cropped to its box first, as ``FrameTransform(..., boxes=)`` does (sides up
                                             to ``max_side``; still one upload and one launch).  Boxed and unboxed pushes
                                             may alternate: the ring holds crops.
+      push_aligned(frames_u8, counts, affines, align_size=256)
+                                            the same for full camera frames with one affine map per packed frame,
+                                            ``affines`` [M, 6] host float64 (``similarity_from_landmarks``): each frame is
+                                            warped to an ``align_size`` face as ``FrameTransform.aligned`` does; one upload
+                                            and one launch, and it may alternate with the other two.
       take(pairs)                           pairs = (stream, frame number) per row -> float32 [M, 3, crop, crop], the bits
                                             ``FrameTransform`` gives those frames.  A stream's frames up to the largest one
                                             taken are released; the others go on waiting.
@@ -415,6 +581,17 @@ class FrameStream:
 
     def check_push(self, frames_u8, counts, boxes=None):
         """Everything ``push`` refuses, without a launch or a change of state.  Returns the counts as ints."""
+        return self._check_push(frames_u8, counts, None if boxes is None else lambda rows: check_boxes(boxes, rows, self.max_side))
+
+    def check_push_aligned(self, frames_u8, counts, affines, align_size=ALIGN_SIZE):
+        """Everything ``push_aligned`` refuses, without a launch or a change of state.  Returns the counts as ints."""
+        def table(rows):
+            check_affines(affines, rows)
+            affine_geometry(align_size, self.size).check_crop(self.crop)
+        return self._check_push(frames_u8, counts, table)
+
+    def _check_push(self, frames_u8, counts, table):
+        """The checks of every kind of push; ``table(rows)`` looks at the per-frame table that comes with the frames."""
         try:
             counts = [int(c) for c in counts]
         except TypeError:
@@ -426,8 +603,8 @@ class FrameStream:
                 raise ValueError(f"counts: stream {s} brings {c} frames, outside 0 .. max_new = {self.max_new}")
             if self.held[s] + c > self.hold:
                 raise ValueError(f"stream {s}: {self.held[s]} frames wait and {c} more exceed hold = {self.hold}; take some first")
-        if boxes is not None:
-            check_boxes(boxes, sum(counts), self.max_side)
+        if table is not None:
+            table(sum(counts))
         f = frames_u8
         if self._xf.yuv is not None:      # the shape is looked at first, then the device
             if not (torch.is_tensor(f) and f.dtype == torch.uint8 and f.dim() == 3):
@@ -448,6 +625,12 @@ class FrameStream:
             raise ValueError(f"frames: empty images {tuple(f.shape)}")
         return counts
 
+    def _alloc(self):
+        if self.ring is None:
+            self.ring = torch.zeros((self.streams, self.ring_frames, self.crop, self.crop, 3), device=self.device,
+                                    dtype=torch.uint8)
+            self._cx = torch.from_numpy(self.crop_xyf).to(self.device)
+
     @torch.no_grad()
     def push(self, frames_u8, counts, boxes=None):
         from . import ops
@@ -460,10 +643,7 @@ class FrameStream:
             tables, _, _, span = self._xf._get_tables(h, w, frames.device)
         else:
             boxes, store = check_boxes(boxes, sum(counts), self.max_side), box_tables(self.size, self.max_side)
-        if self.ring is None:
-            self.ring = torch.zeros((self.streams, self.ring_frames, self.crop, self.crop, 3), device=self.device,
-                                    dtype=torch.uint8)
-            self._cx = torch.from_numpy(self.crop_xyf).to(self.device)
+        self._alloc()
         first = [b + n for b, n in zip(self._base, self.frames_seen)]
         if boxes is None:
             row_stream, row_pos = ops.stream_row_table(first, counts, self.device)
@@ -473,6 +653,25 @@ class FrameStream:
             row_stream, row_pos, bx = ops.stream_row_box_table(first, counts, boxes, self.device)
             ops.frames_stream_append_boxes(frames, bx, store, self.size, self._cx, row_stream, row_pos, max(counts), self.ring,
                                            yuv=yuv)
+        self.frames_seen = [n + c for n, c in zip(self.frames_seen, counts)]
+
+    @torch.no_grad()
+    def push_aligned(self, frames_u8, counts, affines, align_size=ALIGN_SIZE):
+        """``push`` of full camera frames with one affine map per packed frame: ``affines`` [M, 6] host float64, Pillow's
+        coefficients (``similarity_from_landmarks`` makes them from five landmarks).  Frame m is warped to an
+        ``align_size`` x ``align_size`` face as ``PIL.Image.transform((A, A), AFFINE, affines[m], BILINEAR)`` does and that
+        face goes through GroupScale -> crop -> flip: the ring gets the bytes ``push`` gives the warped faces.  Still one
+        upload and one launch (csrc/frames_affine.hip); aligned, boxed and plain pushes may alternate."""
+        from . import ops
+        counts = self.check_push_aligned(frames_u8, counts, affines, align_size)
+        if not sum(counts):
+            return
+        frames, yuv = frames_u8.contiguous(), self._xf.yuv
+        affines, geom = check_affines(affines, sum(counts)), affine_geometry(align_size, self.size)
+        self._alloc()
+        first = [b + n for b, n in zip(self._base, self.frames_seen)]
+        row_stream, row_pos, aff = ops.stream_row_affine_table(first, counts, affines, self.device)
+        ops.frames_stream_append_affine(frames, aff, geom, self.size, self._cx, row_stream, row_pos, max(counts), self.ring, yuv=yuv)
         self.frames_seen = [n + c for n, c in zip(self.frames_seen, counts)]
 
     def check_take(self, pairs):

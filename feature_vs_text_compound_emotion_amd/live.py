@@ -78,6 +78,10 @@ class AVStream:
             -> (logits [P, n_cls], counts): every frame that became paired in this call, stream-major, each stream's frames in
             time order (the row order of ``push_ragged``); counts[s] of them belong to stream s.  Nothing paired: an empty
             [0, n_cls] and no model launch.
+      push_aligned(video, video_counts, video_affines, audio=None, audio_counts=None, extra=None, align_size=256)
+            ``push`` of full camera frames with one affine map per frame, ``video_affines`` [M, 6] host float64
+            (``frames.similarity_from_landmarks`` of the detector's five landmarks): frame m is warped to an ``align_size``
+            face first, as ``FrameStream.push_aligned`` does.  The two share one body and may alternate.
       finish(streams=None)   the streams have ended: the same pair for their remaining frames (the audio stage's one second of
             edge padding, the last example repeated, examples past the last frame dropped); those streams are reset.  A stream
             that received frames but never a sample emits nothing for them.
@@ -223,13 +227,31 @@ class AVStream:
     # ------------------------------------------------------------------------------------------------ the session
     @torch.no_grad()
     def push(self, video=None, video_counts=None, audio=None, audio_counts=None, extra=None, video_boxes=None):
+        if video is None and video_counts is None and video_boxes is not None:
+            raise ValueError("push: video_boxes without video")
+        fs = self.frame_stream
+        return self._push(video, video_counts, audio, audio_counts, extra, fs.check_push, fs.push, (video_boxes,))
+
+    @torch.no_grad()
+    def push_aligned(self, video, video_counts, video_affines, audio=None, audio_counts=None, extra=None, align_size=256):
+        """``push`` of full camera frames with one affine map per frame: ``video_affines`` [M, 6] host float64, Pillow's
+        coefficients (``frames.similarity_from_landmarks`` makes them from the detector's five landmarks); frame m is warped
+        to an ``align_size`` face first, as ``FrameStream.push_aligned`` does.  Everything else is ``push``."""
+        if video is None:
+            raise ValueError("push_aligned: video_affines without video" if video_affines is not None else
+                             "push_aligned: no video; a push without frames is push()")
+        fs = self.frame_stream
+        return self._push(video, video_counts, audio, audio_counts, extra, fs.check_push_aligned, fs.push_aligned,
+                          (video_affines, align_size))
+
+    def _push(self, video, video_counts, audio, audio_counts, extra, check_frames, push_frames, how):
+        """The one body of ``push`` and ``push_aligned``: ``check_frames(video, counts, *how)`` and
+        ``push_frames(video, counts, *how)`` are the ``FrameStream``'s pair for this kind of frames."""
         zeros = [0] * self.streams
         if (video is None) != (video_counts is None) or (audio is None) != (audio_counts is None):
             raise ValueError("push: video and video_counts come together, and so do audio and audio_counts")
-        if video is None and video_boxes is not None:
-            raise ValueError("push: video_boxes without video")
         self.model_stream._check_keys(dict.fromkeys(self.model_stream.modalities))   # the model may have left eval mode
-        vcounts = self.frame_stream.check_push(video, video_counts, video_boxes) if video is not None else zeros
+        vcounts = check_frames(video, video_counts, *how) if video is not None else zeros
         extra = self._check_extra(extra, sum(vcounts))
         pcm, acounts = self.audio_stream.check_push(audio, audio_counts) if audio is not None else (None, zeros)
         for s in range(self.streams):
@@ -246,7 +268,7 @@ class AVStream:
                 self._hold_rows(examples.view(-1, self.win * 64), self._exring, self.examples_seen, got)
                 self.examples_seen = [e + g for e, g in zip(self.examples_seen, got)]
         if sum(vcounts):
-            self.frame_stream.push(video, vcounts, video_boxes)
+            push_frames(video, vcounts, *how)
             for m in self.extra_keys:
                 self._hold_rows(extra[m], self._extra[m], self.frames_seen, vcounts)
             self.frames_seen = [f + c for f, c in zip(self.frames_seen, vcounts)]

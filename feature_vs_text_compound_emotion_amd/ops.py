@@ -2156,6 +2156,86 @@ def frames_stream_append_boxes(frames, boxes, store, size, crop_xyf, row_stream,
         STREAM_TRACE.append(("frames_append_boxes", 0))
 
 
+# ------------------------------------------------------------------ per-frame affine maps (csrc/frames_affine.hip)
+def stream_row_affine_table(positions, counts, affines, device):
+    """``stream_row_table`` and the affines of the same rows in ONE upload: ``affines`` float64 [M, 6] on the host, row m the
+    Pillow coefficients of packed frame m -> (row_stream [M], row_pos [M], affines [M, 6] float64), views of one fresh int32
+    tensor on ``device``.  The doubles travel as int32 pairs at the head of the tensor, so they sit at its 8-byte aligned
+    start whatever M."""
+    streams, pos = _stream_rows(positions, counts)
+    m = len(streams)
+    affines = np.ascontiguousarray(affines, dtype=np.float64)
+    if affines.shape != (m, 6):
+        raise ValueError(f"stream_row_affine_table: expected one affine per row [{m}, 6], got {affines.shape}")
+    host = np.empty(14 * m, np.int32)
+    host[:12 * m], host[12 * m:13 * m], host[13 * m:] = affines.ravel().view(np.int32), streams, pos
+    table = torch.from_numpy(host).to(device)
+    return table[12 * m:13 * m], table[13 * m:], table[:12 * m].view(torch.float64).view(m, 6)
+
+
+def _affine_args(frames, affines, geom, size, crop, like, yuv=None):
+    """The checks the two affine entries share.  Returns (n, H, W, bounds, coef)."""
+    if yuv is not None:
+        n, h, w = _yuv_frames(frames, yuv, like)
+    elif not (torch.is_tensor(frames) and frames.is_cuda and frames.device == like.device and frames.dtype == torch.uint8
+              and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
+        raise ValueError(f"frames: expected a contiguous uint8 [n >= 1, H, W, 3] tensor on the GPU ({like.device}), got "
+                         f"{(frames.dtype, frames.device, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
+    else:
+        n, h, w, _ = frames.shape
+    if geom.size != int(size):
+        raise ValueError(f"geom: built for size {geom.size}, not {size}")
+    if not (torch.is_tensor(affines) and affines.is_cuda and affines.device == like.device and affines.dtype == torch.float64
+            and affines.is_contiguous() and affines.dim() == 2 and affines.shape[1] == 6 and affines.data_ptr() % 8 == 0):
+        raise ValueError(f"affines: expected a contiguous, 8-byte aligned float64 [rows, 6] tensor on the GPU ({like.device}), got "
+                         f"{(affines.dtype, affines.device, tuple(affines.shape)) if torch.is_tensor(affines) else type(affines)}")
+    geom.check_crop(crop)
+    bounds, coef = geom.on(like.device)
+    return n, h, w, bounds, coef
+
+
+def frames_transform_affine(frames, affines, geom, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None, yuv=None):
+    """``Image.transform((A, A), AFFINE, affines[f], BILINEAR)`` -> GroupScale(size) -> crop -> flip -> ToTensor -> Normalize
+    of full frames ``frames`` [n, H, W, 3] uint8 into ``out`` [n, 3, crop, crop] float32 (and ``out_u8`` [n, crop, crop, 3]).
+    ``affines`` float64 [n, 6] on the GPU, Pillow's coefficients (output pixel centre -> frame coordinate); the kernel only
+    compares and multiplies them and fetches every pixel at a clamped index, so a table nobody vetted -- NaN, infinities,
+    1e300 -- gives the all-zero picture and no access outside ``frames``.  ``geom``: ``frames.affine_geometry(A, size)``;
+    ``crop_xyf`` int32 [groups, 3] on the GPU, one entry per ``frames_per_group`` frames.  ``yuv``: ``frames`` are 4:2:0
+    frames [n, H * 3 / 2, W] (``_yuv_frames``); the four pixels of a sample are converted, then interpolated."""
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4
+            and out.shape[1] == 3 and out.shape[2] == out.shape[3]):
+        raise ValueError("out: expected a contiguous float32 [n, 3, crop, crop] GPU tensor")
+    crop, g = out.shape[2], int(frames_per_group)
+    n, h, w, bounds, coef = _affine_args(frames, affines, geom, size, crop, out, yuv)
+    if out.shape[0] != n or affines.shape[0] != n or g < 1:
+        raise ValueError(f"out / affines: expected {n} rows, got {out.shape[0]} and {affines.shape[0]}")
+    _i32_table(crop_xyf, "crop_xyf", ((n + g - 1) // g, 3), out)
+    if out_u8 is not None and not (torch.is_tensor(out_u8) and out_u8.is_cuda and out_u8.device == out.device and out_u8.dtype == torch.uint8
+                                   and out_u8.is_contiguous() and tuple(out_u8.shape) == (n, crop, crop, 3)):
+        raise ValueError(f"out_u8: expected a contiguous uint8 [{n}, {crop}, {crop}, 3] tensor on the GPU of out")
+    entry, how = _yuv_entry("cer_frames_transform_affine", yuv)
+    check(entry(ptr(frames), *how, n, h, w, ptr(affines), ptr(bounds), ptr(coef), geom.ks, geom.align_size, geom.span, int(size),
+                crop, ptr(crop_xyf), g, float(mean), float(std), ptr(out), ptr(out_u8), current_stream()), entry.__name__)
+
+
+def frames_stream_append_affine(frames, affines, geom, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None):
+    """``frames_stream_append`` of full frames with one affine per row: row m of the row table is packed frame m, warped by
+    ``affines[m]`` as ``frames_transform_affine`` does, and lands in slot (row_stream[m], row_pos[m] % Rf).  The bytes are
+    ``return_u8`` of ``FrameTransform.aligned`` for the same frame, affine and crop entry.  ``yuv``: as there."""
+    s, rf, crop = _u8_ring(u8ring)
+    n, h, w, bounds, coef = _affine_args(frames, affines, geom, size, crop, u8ring, yuv)
+    m = _row_table(row_stream, row_pos, u8ring)
+    if affines.shape[0] != m:
+        raise ValueError(f"affines: expected one affine per row [{m}, 6], got {tuple(affines.shape)}")
+    _i32_table(crop_xyf, "crop_xyf", (s, 3), u8ring)
+    entry, how = _yuv_entry("cer_frames_stream_append_affine", yuv)
+    check(entry(ptr(frames), *how, n, h, w, ptr(affines), ptr(bounds), ptr(coef), geom.ks, geom.align_size, geom.span, int(size),
+                crop, ptr(crop_xyf), ptr(row_stream), ptr(row_pos), m, int(max_count), ptr(u8ring), s, rf, current_stream()),
+          entry.__name__)
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("frames_append_affine", 0))
+
+
 def frames_stream_gather(u8ring, row_stream, row_pos, mean=0.5, std=0.5):
     """out[m] = ((u8ring[row_stream[m], row_pos[m] % Rf] / 255) - mean) / std as float32 [M, 3, crop, crop]: the tensor
     ``FrameTransform`` gives the same frames."""

@@ -894,6 +894,61 @@ int cer_frames_stream_append_boxes_yuv(const uint8_t *frames, const cer_yuv420 *
                                        uint8_t *u8ring, int S, int Rf, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Per-frame affine maps on full camera frames (csrc/frames_affine.hip): PIL's Image.transform((A, A), AFFINE, a, BILINEAR)
+ * -> cer_frames_transform, per frame; A = align_size.  This is how a face is aligned from five landmarks: the similarity
+ * that puts them on a template, inverted, is the affine of its frame.
+ *
+ * affines [rows][6] float64, 8-byte aligned = (a0 .. a5) per launch row, Pillow's coefficients: with xin = x + 0.5 and
+ * yin = y + 0.5, pixel (x, y) of the A x A face is sampled at X = (a0 xin + a1 yin) + a2, Y = (a3 xin + a4 yin) + a5 of the
+ * H x W frame.  Every step below is float64 and none is fused:
+ *   the pixel is (0, 0, 0) unless X >= 0 && X < W && Y >= 0 && Y < H (so a NaN is outside);
+ *   X -= 0.5, Y -= 0.5; ix = floor(X), iy = floor(Y); dx = X - ix, dy = Y - iy;
+ *   x0 = clamp(ix, 0, W - 1), x1 = clamp(ix + 1, 0, W - 1), row0 = clamp(iy, 0, H - 1);
+ *   v1 = p[row0][x0] + (p[row0][x1] - p[row0][x0]) dx;
+ *   v2 = 0 <= iy + 1 < H ? p[iy + 1][x0] + (p[iy + 1][x1] - p[iy + 1][x0]) dx : v1;
+ *   byte = (uint8) trunc(v1 + (v2 - v1) dy).
+ * Row f gives the bytes (and floats) cer_frames_transform gives that A x A picture.  Under the _yuv entries the four
+ * pixels are converted (cer_yuv420) and then interpolated: the bits of the RGB entries on the converted frames.
+ *
+ * bounds [size][2] and coef [size][ksize] are the rows of cer_frames_transform for A -> size and serve both passes (the
+ * face is square); max_band_rows = the most rows of the face one band of cer_frames_band_rows() output rows needs, over
+ * every crop offset.  A block keeps the warped rows of its band in LDS: cer_frames_affine_lds_bytes() bytes, bounded by
+ * (size, crop, align_size) whatever H x W.
+ *
+ * cer_frames_transform_affine: the clip form; rows = n_frames, the other arguments as in cer_frames_transform.
+ * cer_frames_stream_append_affine: the ring form; row m reads packed frame m (clamped below n_frames) and affine m, the
+ *   other arguments as in cer_frames_stream_append.
+ *
+ * The affine table is never trusted with an address: its values are only compared and multiplied, a coordinate becomes an
+ * integer after the range test above has passed, and every pixel is fetched at an index clamped into the frame; the streamed
+ * tables are treated as in cer_frames_stream_append.  NaN, infinities and huge values give the all-zero picture.
+ * Refused before any launch, with a cer_last_error() text that begins with the entry's name: a null pointer; a count or a
+ * dimension below 1; crop > size; align_size outside 1 .. 2^14; max_band_rows > align_size; ksize > 2 align_size + 3; a
+ * frame above 2^29 pixels; a misaligned affine table; Rf not a power of two up to 2^30; max_count > Rf; more than 65535 rows
+ * or frames per call; what the _yuv descriptor check refuses (CER_ERR_INVALID_ARG); an align_size whose LDS need exceeds
+ * 160 KiB (CER_ERR_UNSUPPORTED).
+ * ---------------------------------------------------------------------- */
+size_t cer_frames_affine_lds_bytes(int align_size, int max_band_rows, int ksize, int crop);
+int cer_frames_transform_affine(const uint8_t *frames, int n_frames, int H, int W, const double *affines, const int32_t *bounds,
+                                const int32_t *coef, int ksize, int align_size, int max_band_rows, int size, int crop,
+                                const int32_t *crop_xyf, int frames_per_group, float mean, float stdv, float *out,
+                                uint8_t *out_u8, void *stream);
+int cer_frames_stream_append_affine(const uint8_t *frames, int n_frames, int H, int W, const double *affines,
+                                    const int32_t *bounds, const int32_t *coef, int ksize, int align_size, int max_band_rows,
+                                    int size, int crop, const int32_t *crop_xyf, const int32_t *row_stream,
+                                    const int32_t *row_pos, int num_rows, int max_count, uint8_t *u8ring, int S, int Rf,
+                                    void *stream);
+int cer_frames_transform_affine_yuv(const uint8_t *frames, const cer_yuv420 *yuv, int n_frames, int H, int W,
+                                    const double *affines, const int32_t *bounds, const int32_t *coef, int ksize, int align_size,
+                                    int max_band_rows, int size, int crop, const int32_t *crop_xyf, int frames_per_group,
+                                    float mean, float stdv, float *out, uint8_t *out_u8, void *stream);
+int cer_frames_stream_append_affine_yuv(const uint8_t *frames, const cer_yuv420 *yuv, int n_frames, int H, int W,
+                                        const double *affines, const int32_t *bounds, const int32_t *coef, int ksize,
+                                        int align_size, int max_band_rows, int size, int crop, const int32_t *crop_xyf,
+                                        const int32_t *row_stream, const int32_t *row_pos, int num_rows, int max_count,
+                                        uint8_t *u8ring, int S, int Rf, void *stream);
+
+/* ------------------------------------------------------------------------
  * Running video-level decisions of S live streams (csrc/decision_stream.hip): logit rows in, the three decisions of
  * metrics.py:118-139 out -- majority vote over the frame predictions, argmax of the mean logits, argmax of the mean softmax
  * probabilities -- over the first nc = C - (drop_last ? 1 : 0) columns.
