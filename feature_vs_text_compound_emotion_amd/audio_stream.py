@@ -53,16 +53,9 @@ def num_rows(samples):
     return 0 if samples < ROW_SAMPLES else 1 + (samples - ROW_SAMPLES) // ROW_HOP
 
 
-def _pow2(need):
-    r = 1
-    while r < need:
-        r *= 2
-    return r
-
-
 def ring_sizes(win, max_samples):
     """(Rs, Rm) for examples of ``win`` rows and pushes of up to ``max_samples`` samples per stream (derivation above)."""
-    return _pow2(ROW_SAMPLES - 1 + max_samples), _pow2(win + max_samples // ROW_HOP + 1)
+    return ops.pow2_at_least(ROW_SAMPLES - 1 + max_samples), ops.pow2_at_least(win + max_samples // ROW_HOP + 1)
 
 
 def num_examples(rows, win, hop_frames):
@@ -112,7 +105,7 @@ def resample_ring_sizes(win, max_samples, L, M, T):
     (derivation above); ``max_out``: the most 16 kHz samples one push or the tail of ``finish`` adds to a stream."""
     max_out = max(max_samples * L // M + 1, (T // 2) * L // M + 2)
     rs, rm = ring_sizes(win, max_out)
-    return _pow2(T - 1 + max_samples), rs, rm, max_out
+    return ops.pow2_at_least(T - 1 + max_samples), rs, rm, max_out
 
 
 def schedule(samples, rows, examples, count, win, hop_frames, limit=None):

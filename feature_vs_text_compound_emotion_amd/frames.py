@@ -8,15 +8,13 @@ frames that are already resident in HBM.  The resize is bit-identical to ``PIL.I
 (``precompute_coeffs`` + ``normalize_coeffs_8bpc`` of Pillow's Resample.c, third-party, restated) once per
 geometry and the kernel does the two fixed-point passes.
 """
-import ctypes
 import math
 import random
 
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import check, current_stream, ptr
+from . import _lib, ops
 
 PRECISION_BITS = 32 - 8 - 2
 
@@ -110,6 +108,18 @@ class BoxTables:
             self._dev[key] = (torch.from_numpy(self.meta).to(device), torch.from_numpy(self.data).to(device))
         return self._dev[key]
 
+    stem = "boxes"      # of the C entries cer_frames_transform_boxes / cer_frames_stream_append_boxes
+
+    def check_rows(self, boxes, rows, size, crop, like):
+        """What the entries ask of the device table, int32 [rows, 4] on the GPU of ``like``, and of the store."""
+        if self.size != int(size):
+            raise ValueError(f"store: built for size {self.size}, not {size}")
+        ops._i32_table(boxes, "boxes", (rows, 4), like)
+
+    def entry_args(self, device):
+        """The two device tables and three integers the entries take after the boxes."""
+        return (*self.on(device), self.max_side, self.max_rows, self.max_ks)
+
 
 _BOX_TABLES = {}
 
@@ -191,6 +201,23 @@ class AffineGeometry:
         if key not in self._dev:
             self._dev[key] = (torch.from_numpy(self.bounds).to(device), torch.from_numpy(self.coef).to(device))
         return self._dev[key]
+
+    stem = "affine"     # of the C entries cer_frames_transform_affine / cer_frames_stream_append_affine
+
+    def check_rows(self, affines, rows, size, crop, like):
+        """What the entries ask of the device table, 8-byte aligned float64 [rows, 6] on the GPU of ``like``, and of the
+        geometry."""
+        if self.size != int(size):
+            raise ValueError(f"geom: built for size {self.size}, not {size}")
+        if not (torch.is_tensor(affines) and affines.is_cuda and affines.device == like.device and affines.dtype == torch.float64
+                and affines.is_contiguous() and tuple(affines.shape) == (rows, 6) and affines.data_ptr() % 8 == 0):
+            raise ValueError(f"affines: expected a contiguous, 8-byte aligned float64 [{rows}, 6] tensor on the GPU ({like.device}), got "
+                             f"{(affines.dtype, affines.device, tuple(affines.shape)) if torch.is_tensor(affines) else type(affines)}")
+        self.check_crop(crop)
+
+    def entry_args(self, device):
+        """The two device tables and three integers the entries take after the affines."""
+        return (*self.on(device), self.ks, self.align_size, self.span)
 
 
 AFFINE_LDS_BYTES = 160 * 1024     # what one block of csrc/frames_affine.hip may hold
@@ -406,41 +433,34 @@ class FrameTransform:
         return frames.contiguous(), b, l, h, w
 
     def __call__(self, frames, crop_xyf=None, return_u8=False, boxes=None):
-        frames, b, l, h, w = self._clip(frames)
+        clip = self._clip(frames)
+        if boxes is None:
+            return self._run(clip, crop_xyf, return_u8, None, self._plain, ops.frames_transform)
+        return self._run(clip, crop_xyf, return_u8, lambda rows: check_boxes(boxes, rows, self.max_side),
+                         lambda *_: (box_tables(self.size, self.max_side),), ops.frames_transform_boxes)
+
+    def _plain(self, h, w, device):
+        """What the plain wrappers take after the frames: (the four resample tables of an H x W picture, the band span)."""
+        tables, _, _, span = self._get_tables(h, w, device)
+        return tables, span
+
+    def _run(self, clip, crop_xyf, return_u8, table, how, call):
+        """Everything after ``_clip()``: the crop entries, the outputs, and the launches over chunks of whole clips of at most
+        65535 frames.  ``table(rows)``: the checked host table that comes with the frames (boxes, affines), or None;
+        ``how(H, W, device)``: what ``call`` takes between the frames (and their table) and ``size`` -- ``_plain``, the box
+        store, the affine geometry; ``call``: the ``ops.frames_transform*`` that runs one chunk."""
+        frames, b, l, h, w = clip
         if crop_xyf is None:
             crop_xyf = self.draw(b)
         crop_xyf = np.ascontiguousarray(crop_xyf, dtype=np.int32).reshape(b, 3)
         if (crop_xyf[:, :2] < 0).any() or (crop_xyf[:, :2] + self.crop > self.size).any():
             raise RuntimeError("FrameTransform: crop offset outside the resized image")
-        if boxes is not None:
-            return self._boxed(frames, crop_xyf, return_u8, check_boxes(boxes, b * l, self.max_side))
-        (hb, hk, vb, vk), hks, vks, span = self._get_tables(h, w, frames.device)
-        cx = torch.from_numpy(crop_xyf).to(frames.device)
-        out = torch.empty((b, l, 3, self.crop, self.crop), dtype=torch.float32, device=frames.device)
-        u8 = torch.empty((b, l, self.crop, self.crop, 3), dtype=torch.uint8, device=frames.device) if return_u8 else None
-        lib = _lib.load()
-        n = b * l
-        step = 65535 // l * l if l <= 65535 else 0
-        if step == 0:
-            raise RuntimeError("FrameTransform: clip longer than 65535 frames")
-        flat_in, flat_out = frames.view(n, *frames.shape[2:]), out.view(n, 3, self.crop, self.crop)
-        flat_u8 = u8.view(n, self.crop, self.crop, 3) if return_u8 else None
-        entry, how = (lib.cer_frames_transform, ()) if self.yuv is None else (lib.cer_frames_transform_yuv, (ctypes.byref(self.yuv),))
-        for s in range(0, n, step):
-            e = min(n, s + step)
-            check(entry(ptr(flat_in[s:e]), *how, e - s, h, w, ptr(hb), ptr(hk), hks, ptr(vb), ptr(vk), vks,
-                        self.size, self.crop, ptr(cx[s // l:]), l, span, self.mean, self.std,
-                        ptr(flat_out[s:e]), ptr(flat_u8[s:e]) if return_u8 else None,
-                        current_stream()), "cer_frames_transform" + ("_yuv" if how else ""))
-        return (out, u8) if return_u8 else out
-
-    def _boxed(self, frames, crop_xyf, return_u8, boxes):
-        from . import ops
-        b, l = frames.shape[:2]
+        rows = None if table is None else table(b * l)
         if l > 65535:
             raise RuntimeError("FrameTransform: clip longer than 65535 frames")
-        store = box_tables(self.size, self.max_side)
-        cx, bx = torch.from_numpy(crop_xyf).to(frames.device), torch.from_numpy(boxes).to(frames.device)
+        how = how(h, w, frames.device)
+        cx = torch.from_numpy(crop_xyf).to(frames.device)
+        rows = None if rows is None else torch.from_numpy(rows).to(frames.device)
         out = torch.empty((b, l, 3, self.crop, self.crop), dtype=torch.float32, device=frames.device)
         u8 = torch.empty((b, l, self.crop, self.crop, 3), dtype=torch.uint8, device=frames.device) if return_u8 else None
         n, step = b * l, 65535 // l * l
@@ -448,8 +468,8 @@ class FrameTransform:
         flat_u8 = u8.view(n, self.crop, self.crop, 3) if return_u8 else None
         for s in range(0, n, step):
             e = min(n, s + step)
-            ops.frames_transform_boxes(flat_in[s:e], bx[s:e], store, self.size, cx[s // l:e // l], l, self.mean, self.std,
-                                       flat_out[s:e], flat_u8[s:e] if return_u8 else None, yuv=self.yuv)
+            call(flat_in[s:e], *([] if rows is None else [rows[s:e]]), *how, self.size, cx[s // l:e // l], l, self.mean, self.std,
+                 flat_out[s:e], flat_u8[s:e] if return_u8 else None, yuv=self.yuv)
         return (out, u8) if return_u8 else out
 
     def aligned(self, frames, affines, crop_xyf=None, return_u8=False, align_size=ALIGN_SIZE):
@@ -458,40 +478,18 @@ class FrameTransform:
         warped to an ``align_size`` x ``align_size`` face as ``PIL.Image.transform((A, A), AFFINE, affines[f], BILINEAR)``
         does -- zero outside the frame -- so the result is what the plain call gives those faces.  One launch for any mix of
         maps (csrc/frames_affine.hip); the pixel format is the transform's."""
-        from . import ops
         geom = affine_geometry(align_size, self.size)
         geom.check_crop(self.crop)
         rank = 5 if self.yuv is None else 4
         if torch.is_tensor(frames) and frames.dim() in (rank - 1, rank):      # the table is looked at first, like boxes
             check_affines(affines, int(np.prod(frames.shape[:frames.dim() - rank + 2])))
-        frames, b, l, h, w = self._clip(frames)
-        if crop_xyf is None:
-            crop_xyf = self.draw(b)
-        crop_xyf = np.ascontiguousarray(crop_xyf, dtype=np.int32).reshape(b, 3)
-        if (crop_xyf[:, :2] < 0).any() or (crop_xyf[:, :2] + self.crop > self.size).any():
-            raise RuntimeError("FrameTransform: crop offset outside the resized image")
-        affines = check_affines(affines, b * l)
-        if l > 65535:
-            raise RuntimeError("FrameTransform: clip longer than 65535 frames")
-        cx, af = torch.from_numpy(crop_xyf).to(frames.device), torch.from_numpy(affines).to(frames.device)
-        out = torch.empty((b, l, 3, self.crop, self.crop), dtype=torch.float32, device=frames.device)
-        u8 = torch.empty((b, l, self.crop, self.crop, 3), dtype=torch.uint8, device=frames.device) if return_u8 else None
-        n, step = b * l, 65535 // l * l
-        flat_in, flat_out = frames.view(n, *frames.shape[2:]), out.view(n, 3, self.crop, self.crop)
-        flat_u8 = u8.view(n, self.crop, self.crop, 3) if return_u8 else None
-        for s in range(0, n, step):
-            e = min(n, s + step)
-            ops.frames_transform_affine(flat_in[s:e], af[s:e], geom, self.size, cx[s // l:e // l], l, self.mean, self.std,
-                                        flat_out[s:e], flat_u8[s:e] if return_u8 else None, yuv=self.yuv)
-        return (out, u8) if return_u8 else out
+        return self._run(self._clip(frames), crop_xyf, return_u8, lambda rows: check_affines(affines, rows), lambda *_: (geom,),
+                         ops.frames_transform_affine)
 
 
 def hold_ring(hold, max_new):
     """Slots of a ring in which up to ``hold`` rows wait while a push adds up to ``max_new``: the power of two >= their sum."""
-    r = 1
-    while r < hold + max_new:
-        r *= 2
-    return r
+    return ops.pow2_at_least(hold + max_new)
 
 
 class FrameStream:
@@ -581,17 +579,25 @@ class FrameStream:
 
     def check_push(self, frames_u8, counts, boxes=None):
         """Everything ``push`` refuses, without a launch or a change of state.  Returns the counts as ints."""
-        return self._check_push(frames_u8, counts, None if boxes is None else lambda rows: check_boxes(boxes, rows, self.max_side))
+        return self._check_push(frames_u8, counts, self._box_rows(boxes))[0]
 
     def check_push_aligned(self, frames_u8, counts, affines, align_size=ALIGN_SIZE):
         """Everything ``push_aligned`` refuses, without a launch or a change of state.  Returns the counts as ints."""
+        return self._check_push(frames_u8, counts, self._affine_rows(affines, align_size))[0]
+
+    def _box_rows(self, boxes):
+        return None if boxes is None else lambda rows: check_boxes(boxes, rows, self.max_side)
+
+    def _affine_rows(self, affines, align_size):
         def table(rows):
-            check_affines(affines, rows)
+            arr = check_affines(affines, rows)
             affine_geometry(align_size, self.size).check_crop(self.crop)
-        return self._check_push(frames_u8, counts, table)
+            return arr
+        return table
 
     def _check_push(self, frames_u8, counts, table):
-        """The checks of every kind of push; ``table(rows)`` looks at the per-frame table that comes with the frames."""
+        """The checks of every kind of push; ``table(rows)`` checks the per-frame table that comes with the frames (None: there
+        is none).  Returns (the counts as ints, that table as ``table`` returns it)."""
         try:
             counts = [int(c) for c in counts]
         except TypeError:
@@ -603,8 +609,7 @@ class FrameStream:
                 raise ValueError(f"counts: stream {s} brings {c} frames, outside 0 .. max_new = {self.max_new}")
             if self.held[s] + c > self.hold:
                 raise ValueError(f"stream {s}: {self.held[s]} frames wait and {c} more exceed hold = {self.hold}; take some first")
-        if table is not None:
-            table(sum(counts))
+        rows = None if table is None else table(sum(counts))
         f = frames_u8
         if self._xf.yuv is not None:      # the shape is looked at first, then the device
             if not (torch.is_tensor(f) and f.dtype == torch.uint8 and f.dim() == 3):
@@ -623,7 +628,7 @@ class FrameStream:
             raise ValueError(f"frames: {f.shape[0]} frames in one push exceed 65535")
         if f.shape[0] and (f.shape[1] < 1 or f.shape[2] < 1):
             raise ValueError(f"frames: empty images {tuple(f.shape)}")
-        return counts
+        return counts, rows
 
     def _alloc(self):
         if self.ring is None:
@@ -632,47 +637,36 @@ class FrameStream:
             self._cx = torch.from_numpy(self.crop_xyf).to(self.device)
 
     @torch.no_grad()
-    def push(self, frames_u8, counts, boxes=None):
-        from . import ops
-        counts = self.check_push(frames_u8, counts, boxes)
+    def _push(self, frames_u8, counts, table, how, upload, append):
+        """The body of every kind of push.  ``table``: as for ``_check_push``; ``how``: as for ``FrameTransform._run``;
+        ``upload``: the ``ops.stream_row_*table`` that takes what ``table`` returns; ``append``: the
+        ``ops.frames_stream_append*`` of the one launch."""
+        counts, rows = self._check_push(frames_u8, counts, table)
         if not sum(counts):
             return
         frames, yuv = frames_u8.contiguous(), self._xf.yuv
         h, w = frames.shape[1:3] if yuv is None else yuv_picture(frames.shape[1], frames.shape[2])
-        if boxes is None:
-            tables, _, _, span = self._xf._get_tables(h, w, frames.device)
-        else:
-            boxes, store = check_boxes(boxes, sum(counts), self.max_side), box_tables(self.size, self.max_side)
+        how = how(h, w, frames.device)
         self._alloc()
         first = [b + n for b, n in zip(self._base, self.frames_seen)]
-        if boxes is None:
-            row_stream, row_pos = ops.stream_row_table(first, counts, self.device)
-            ops.frames_stream_append(frames, tables, span, self.size, self._cx, row_stream, row_pos, max(counts), self.ring,
-                                     yuv=yuv)
-        else:
-            row_stream, row_pos, bx = ops.stream_row_box_table(first, counts, boxes, self.device)
-            ops.frames_stream_append_boxes(frames, bx, store, self.size, self._cx, row_stream, row_pos, max(counts), self.ring,
-                                           yuv=yuv)
+        row_stream, row_pos, *rows = upload(first, counts, *([] if rows is None else [rows]), self.device)
+        append(frames, *rows, *how, self.size, self._cx, row_stream, row_pos, max(counts), self.ring, yuv=yuv)
         self.frames_seen = [n + c for n, c in zip(self.frames_seen, counts)]
 
-    @torch.no_grad()
+    def push(self, frames_u8, counts, boxes=None):
+        if boxes is None:
+            return self._push(frames_u8, counts, None, self._xf._plain, ops.stream_row_table, ops.frames_stream_append)
+        return self._push(frames_u8, counts, self._box_rows(boxes), lambda *_: (box_tables(self.size, self.max_side),),
+                          ops.stream_row_box_table, ops.frames_stream_append_boxes)
+
     def push_aligned(self, frames_u8, counts, affines, align_size=ALIGN_SIZE):
         """``push`` of full camera frames with one affine map per packed frame: ``affines`` [M, 6] host float64, Pillow's
         coefficients (``similarity_from_landmarks`` makes them from five landmarks).  Frame m is warped to an
         ``align_size`` x ``align_size`` face as ``PIL.Image.transform((A, A), AFFINE, affines[m], BILINEAR)`` does and that
         face goes through GroupScale -> crop -> flip: the ring gets the bytes ``push`` gives the warped faces.  Still one
         upload and one launch (csrc/frames_affine.hip); aligned, boxed and plain pushes may alternate."""
-        from . import ops
-        counts = self.check_push_aligned(frames_u8, counts, affines, align_size)
-        if not sum(counts):
-            return
-        frames, yuv = frames_u8.contiguous(), self._xf.yuv
-        affines, geom = check_affines(affines, sum(counts)), affine_geometry(align_size, self.size)
-        self._alloc()
-        first = [b + n for b, n in zip(self._base, self.frames_seen)]
-        row_stream, row_pos, aff = ops.stream_row_affine_table(first, counts, affines, self.device)
-        ops.frames_stream_append_affine(frames, aff, geom, self.size, self._cx, row_stream, row_pos, max(counts), self.ring, yuv=yuv)
-        self.frames_seen = [n + c for n, c in zip(self.frames_seen, counts)]
+        return self._push(frames_u8, counts, self._affine_rows(affines, align_size),
+                          lambda *_: (affine_geometry(align_size, self.size),), ops.stream_row_affine_table, ops.frames_stream_append_affine)
 
     def check_take(self, pairs):
         """What ``take`` refuses.  Returns the pairs as ints."""
@@ -689,7 +683,6 @@ class FrameStream:
 
     @torch.no_grad()
     def take(self, pairs):
-        from . import ops
         pairs = self.check_take(pairs)
         if not pairs:
             return torch.empty((0, 3, self.crop, self.crop), device=self.device, dtype=torch.float32)

@@ -1707,6 +1707,14 @@ def tcn_stream_conv(ring, head, c, w_packed, bias, k, dil, *, res_ring=None, res
     _stream_conv("conv", d, (), s, cin, s * int(c), ring, w_packed, bias, res_ring, res_w, res_bias, out_ring, out_dense)
 
 
+def pow2_at_least(n):
+    """The power of two >= n (1 for n <= 1): the length of every ring, so that a position is masked, not divided."""
+    r = 1
+    while r < n:
+        r *= 2
+    return r
+
+
 ROW_POS_MOD = 1 << 30   # row positions travel modulo 2^30: every ring length divides it, so each launch's mask sees the same slot
 
 
@@ -1722,14 +1730,32 @@ def _stream_rows(positions, counts):
     return streams, [(p + i) % ROW_POS_MOD for p, c in zip(positions, counts) for i in range(c)]
 
 
+def _upload_rows(positions, counts, device, payload=None, dtype=np.int32, cols=0, name="stream_row_table"):
+    """The row table of ``_stream_rows`` and an optional per-row ``payload`` [M, cols] of ``dtype`` as ONE fresh int32 host
+    array [payload | streams | positions] and one upload (no staging buffer an unfinished copy could still read).  The payload
+    leads, so 8-byte values sit at the allocation's aligned start whatever M.
+    Returns (row_stream [M], row_pos [M], the payload's int32 words or None), views of that tensor on ``device``."""
+    streams, pos = _stream_rows(positions, counts)
+    m, w = len(streams), 0
+    if payload is not None:
+        payload = np.ascontiguousarray(payload, dtype=dtype)
+        if payload.shape != (m, cols):
+            raise ValueError(f"{name}: expected one entry per row [{m}, {cols}], got {payload.shape}")
+        w = payload.nbytes // 4
+    host = np.empty(w + 2 * m, np.int32)
+    host[w:] = streams + pos
+    if w:
+        host[:w] = payload.ravel().view(np.int32)
+    table = torch.from_numpy(host).to(device)
+    return table[w:w + m], table[w + m:], None if payload is None else table[:w]
+
+
 def stream_row_table(positions, counts, device):
     """The row table of one ragged push: stream s brings ``counts[s]`` frames, the first at position ``positions[s]`` (frames
     that stream has been pushed so far).  Returns (row_stream, row_pos), int32 [M] each on ``device``: rows stream-major in
     ascending stream order, a stream's frames in time order, positions modulo 2^30; a stream with count 0 has no row.
-    Built from Python ints and uploaded in one fresh tensor per call (no staging buffer an unfinished copy could still read)."""
-    streams, pos = _stream_rows(positions, counts)
-    table = torch.tensor([streams, pos], dtype=torch.int32, device=device).view(2, len(streams))
-    return table[0], table[1]
+    Built from Python ints and uploaded in one fresh tensor per call (``_upload_rows``)."""
+    return _upload_rows(positions, counts, device)[:2]
 
 
 DECISION_FIELDS = 6   # stream, count, offset, position, frames (low word), frames (high word)
@@ -2041,6 +2067,56 @@ def _yuv_frames(frames, yuv, like):
     return (frames.shape[0], *yuv_picture(frames.shape[1], frames.shape[2]))
 
 
+def _yuv_entry(name, yuv):
+    """The C entry ``name`` or its ``_yuv`` sibling, and the arguments the sibling takes after ``frames``."""
+    return (getattr(_lib.load(), name), ()) if yuv is None else (getattr(_lib.load(), name + "_yuv"), (ctypes.byref(yuv),))
+
+
+def _frames_in(frames, like, yuv, rows=None):
+    """The check of packed input frames that every frame wrapper shares: ``frames`` contiguous uint8 [n >= 1, H, W, 3] on
+    the GPU of ``like`` (the ring or ``out``), or 4:2:0 frames under ``yuv`` (``_yuv_frames``); ``rows``: the n that ``out``
+    has room for.  Returns (n, H, W)."""
+    if yuv is not None:
+        n, h, w = _yuv_frames(frames, yuv, like)
+    elif not (torch.is_tensor(frames) and frames.is_cuda and frames.device == like.device and frames.dtype == torch.uint8
+              and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
+        raise ValueError(f"frames: expected a contiguous uint8 [n >= 1, H, W, 3] tensor on the GPU of the ring or out ({like.device}), "
+                         f"got {(frames.dtype, frames.device, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
+    else:
+        n, h, w, _ = frames.shape
+    if rows is not None and rows != n:
+        raise ValueError(f"frames: {n} frames for the {rows} rows of out")
+    return n, h, w
+
+
+def _clip_out(out, out_u8, crop_xyf, frames_per_group):
+    """What only a clip call has: ``out`` contiguous float32 [n, 3, crop, crop] on the GPU; where asked for, ``out_u8`` uint8
+    [n, crop, crop, 3] beside it; ``crop_xyf`` int32 [groups, 3], one entry per ``frames_per_group`` of the n frames.
+    Returns (n, crop, frames_per_group)."""
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4
+            and out.shape[1] == 3 and out.shape[2] == out.shape[3]):
+        raise ValueError("out: expected a contiguous float32 [n, 3, crop, crop] GPU tensor")
+    n, crop = out.shape[0], out.shape[2]
+    if out_u8 is not None and not (torch.is_tensor(out_u8) and out_u8.is_cuda and out_u8.device == out.device and out_u8.dtype == torch.uint8
+                                   and out_u8.is_contiguous() and tuple(out_u8.shape) == (n, crop, crop, 3)):
+        raise ValueError(f"out_u8: expected a contiguous uint8 [{n}, {crop}, {crop}, 3] tensor on the GPU of out")
+    g = int(frames_per_group)
+    if g < 1:
+        raise ValueError(f"frames_per_group = {g}: must be >= 1")
+    _i32_table(crop_xyf, "crop_xyf", ((n + g - 1) // g, 3), out)
+    return n, crop, g
+
+
+def _resample_tables(tables, size, like):
+    """``tables`` = (hbounds, hcoef, vbounds, vcoef) of ``frames.resample_tables`` as int32 [size, 2] / [size, k] GPU tensors."""
+    hb, hk, vb, vk = tables
+    for t, name, cols in ((hb, "hbounds", 2), (vb, "vbounds", 2), (hk, "hcoef", None), (vk, "vcoef", None)):
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise ValueError(f"{name}: expected an int32 [size, k] GPU tensor")
+        _i32_table(t, name, (int(size), cols if cols is not None else t.shape[1]), like)
+    return hb, hk, vb, vk
+
+
 def frames_stream_append(frames, tables, span, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None):
     """GroupScale(size) -> crop -> flip of the raw frames ``frames`` [n, H, W, 3] uint8 into the ring ``u8ring``
     [S, Rf, crop, crop, 3]: row m of the row table (``stream_row_table``) is frame m and lands in slot
@@ -2050,67 +2126,74 @@ def frames_stream_append(frames, tables, span, size, crop_xyf, row_stream, row_p
     The bytes are ``return_u8`` of ``FrameTransform`` for the same frame and crop entry.  ``yuv``: ``frames`` are 4:2:0
     frames [n, H * 3 / 2, W] (``_yuv_frames``), converted where the kernel reads them; the tables stay those of H and W."""
     s, rf, crop = _u8_ring(u8ring)
-    if yuv is not None:
-        n, h, w = _yuv_frames(frames, yuv, u8ring)
-    elif not (torch.is_tensor(frames) and frames.is_cuda and frames.device == u8ring.device and frames.dtype == torch.uint8
-              and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
-        raise ValueError("frames: expected a contiguous uint8 [n >= 1, H, W, 3] tensor on the GPU of the ring, got "
-                         f"{(frames.dtype, frames.device, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
-    else:
-        n, h, w, _ = frames.shape
+    n, h, w = _frames_in(frames, u8ring, yuv)
     m = _row_table(row_stream, row_pos, u8ring)
-    hb, hk, vb, vk = tables
-    size = int(size)
-    for t, name, rows in ((hb, "hbounds", 2), (vb, "vbounds", 2), (hk, "hcoef", None), (vk, "vcoef", None)):
-        if not torch.is_tensor(t) or t.dim() != 2:
-            raise ValueError(f"{name}: expected an int32 [size, k] GPU tensor")
-        _i32_table(t, name, (size, rows if rows is not None else t.shape[1]), u8ring)
+    hb, hk, vb, vk = _resample_tables(tables, size, u8ring)
     _i32_table(crop_xyf, "crop_xyf", (s, 3), u8ring)
     entry, how = _yuv_entry("cer_frames_stream_append", yuv)
-    check(entry(ptr(frames), *how, n, h, w, ptr(hb), ptr(hk), hk.shape[1], ptr(vb), ptr(vk), vk.shape[1], size, crop,
+    check(entry(ptr(frames), *how, n, h, w, ptr(hb), ptr(hk), hk.shape[1], ptr(vb), ptr(vk), vk.shape[1], int(size), crop,
                 ptr(crop_xyf), int(span), ptr(row_stream), ptr(row_pos), m, int(max_count), ptr(u8ring), s, rf, current_stream()),
           entry.__name__)
     if STREAM_TRACE is not None:
         STREAM_TRACE.append(("frames_append", 0))
 
 
-# ------------------------------------------------------------------ per-frame face boxes (csrc/frames_box.hip)
+def frames_transform(frames, tables, span, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None, yuv=None):
+    """GroupScale(size) -> crop -> flip -> ToTensor -> Normalize of the raw frames ``frames`` [n, H, W, 3] uint8 into ``out``
+    [n, 3, crop, crop] float32 (and ``out_u8`` [n, crop, crop, 3]), the clip form of ``frames_stream_append``: ``tables`` and
+    ``span`` as there; ``crop_xyf`` int32 [groups, 3] on the GPU, one (x1, y1, flip) per ``frames_per_group`` frames.
+    ``yuv``: as there."""
+    n, crop, g = _clip_out(out, out_u8, crop_xyf, frames_per_group)
+    h, w = _frames_in(frames, out, yuv, n)[1:]
+    hb, hk, vb, vk = _resample_tables(tables, size, out)
+    entry, how = _yuv_entry("cer_frames_transform", yuv)
+    check(entry(ptr(frames), *how, n, h, w, ptr(hb), ptr(hk), hk.shape[1], ptr(vb), ptr(vk), vk.shape[1], int(size), crop,
+                ptr(crop_xyf), g, int(span), float(mean), float(std), ptr(out), ptr(out_u8), current_stream()), entry.__name__)
+
+
+# ------------------------------------------------------------------ per-frame tables: face boxes (csrc/frames_box.hip) and
+# affine maps (csrc/frames_affine.hip).  ``geom`` is the ``frames.BoxTables`` / ``frames.AffineGeometry`` of the call: its
+# ``stem`` names the C entries, ``check_rows`` vets the device table, ``entry_args`` gives its two device tables and three ints.
 def stream_row_box_table(positions, counts, boxes, device):
     """``stream_row_table`` and the boxes of the same rows in ONE upload: ``boxes`` int [M, 4] on the host, row m the box of
     packed frame m -> (row_stream [M], row_pos [M], boxes [M, 4]), int32 views of one fresh tensor on ``device``."""
-    streams, pos = _stream_rows(positions, counts)
-    m = len(streams)
-    boxes = np.ascontiguousarray(boxes, dtype=np.int32)
-    if boxes.shape != (m, 4):
-        raise ValueError(f"stream_row_box_table: expected one box per row [{m}, 4], got {boxes.shape}")
-    host = np.empty(6 * m, np.int32)
-    host[:m], host[m:2 * m], host[2 * m:] = streams, pos, boxes.ravel()
-    table = torch.from_numpy(host).to(device)
-    return table[:m], table[m:2 * m], table[2 * m:].view(m, 4)
+    row_stream, row_pos, words = _upload_rows(positions, counts, device, boxes, np.int32, 4, "stream_row_box_table")
+    return row_stream, row_pos, words.view(-1, 4)
 
 
-def _yuv_entry(name, yuv):
-    """The C entry ``name`` or its ``_yuv`` sibling, and the arguments the sibling takes after ``frames``."""
-    return (getattr(_lib.load(), name), ()) if yuv is None else (getattr(_lib.load(), name + "_yuv"), (ctypes.byref(yuv),))
+def stream_row_affine_table(positions, counts, affines, device):
+    """``stream_row_table`` and the affines of the same rows in ONE upload: ``affines`` float64 [M, 6] on the host, row m the
+    Pillow coefficients of packed frame m -> (row_stream [M], row_pos [M], affines [M, 6] float64), views of one fresh int32
+    tensor on ``device``.  The doubles travel as int32 pairs at the head of the tensor, so they sit at its 8-byte aligned
+    start whatever M."""
+    row_stream, row_pos, words = _upload_rows(positions, counts, device, affines, np.float64, 6, "stream_row_affine_table")
+    return row_stream, row_pos, words.view(torch.float64).view(-1, 6)
 
 
-def _box_args(frames, boxes, store, size, like, yuv=None):
-    """The checks the two boxed entries share.  Returns (n, H, W, meta, data)."""
-    if yuv is not None:
-        n, h, w = _yuv_frames(frames, yuv, like)
-    elif not (torch.is_tensor(frames) and frames.is_cuda and frames.device == like.device and frames.dtype == torch.uint8
-              and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
-        raise ValueError(f"frames: expected a contiguous uint8 [n >= 1, H, W, 3] tensor on the GPU ({like.device}), got "
-                         f"{(frames.dtype, frames.device, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
-    else:
-        n, h, w, _ = frames.shape
-    if store.size != int(size):
-        raise ValueError(f"store: built for size {store.size}, not {size}")
-    if not torch.is_tensor(boxes) or boxes.dim() != 2:
-        raise ValueError("boxes: expected an int32 [rows, 4] GPU tensor")
-    _i32_table(boxes, "boxes", (boxes.shape[0], 4), like)
-    meta, data = store.on(like.device)
-    return n, h, w, meta, data
+def _transform_rows(frames, rows, geom, size, crop_xyf, frames_per_group, mean, std, out, out_u8, yuv):
+    """The clip call of a per-frame table: ``frames_transform_boxes`` / ``frames_transform_affine``."""
+    n, crop, g = _clip_out(out, out_u8, crop_xyf, frames_per_group)
+    h, w = _frames_in(frames, out, yuv, n)[1:]
+    geom.check_rows(rows, n, size, crop, out)
+    a, b, *ints = geom.entry_args(out.device)
+    entry, how = _yuv_entry("cer_frames_transform_" + geom.stem, yuv)
+    check(entry(ptr(frames), *how, n, h, w, ptr(rows), ptr(a), ptr(b), *ints, int(size), crop, ptr(crop_xyf), g, float(mean),
+                float(std), ptr(out), ptr(out_u8), current_stream()), entry.__name__)
+
+
+def _append_rows(frames, rows, geom, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv):
+    """The ring call of a per-frame table: ``frames_stream_append_boxes`` / ``frames_stream_append_affine``."""
+    s, rf, crop = _u8_ring(u8ring)
+    n, h, w = _frames_in(frames, u8ring, yuv)
+    m = _row_table(row_stream, row_pos, u8ring)
+    geom.check_rows(rows, m, size, crop, u8ring)
+    _i32_table(crop_xyf, "crop_xyf", (s, 3), u8ring)
+    a, b, *ints = geom.entry_args(u8ring.device)
+    entry, how = _yuv_entry("cer_frames_stream_append_" + geom.stem, yuv)
+    check(entry(ptr(frames), *how, n, h, w, ptr(rows), ptr(a), ptr(b), *ints, int(size), crop, ptr(crop_xyf), ptr(row_stream),
+                ptr(row_pos), m, int(max_count), ptr(u8ring), s, rf, current_stream()), entry.__name__)
+    if STREAM_TRACE is not None:
+        STREAM_TRACE.append(("frames_append_" + geom.stem, 0))
 
 
 def frames_transform_boxes(frames, boxes, store, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None, yuv=None):
@@ -2121,77 +2204,14 @@ def frames_transform_boxes(frames, boxes, store, size, crop_xyf, frames_per_grou
     access outside ``frames``.  ``store``: ``frames.box_tables(size, max_side)``; ``crop_xyf`` int32 [groups, 3] on the GPU,
     one entry per ``frames_per_group`` frames.  ``yuv``: ``frames`` are 4:2:0 frames [n, H * 3 / 2, W] (``_yuv_frames``); the
     boxes stay in luma pixels and what lies outside the picture is RGB 0."""
-    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4
-            and out.shape[1] == 3 and out.shape[2] == out.shape[3]):
-        raise ValueError("out: expected a contiguous float32 [n, 3, crop, crop] GPU tensor")
-    n, h, w, meta, data = _box_args(frames, boxes, store, size, out, yuv)
-    crop, g = out.shape[2], int(frames_per_group)
-    if out.shape[0] != n or boxes.shape[0] != n or g < 1:
-        raise ValueError(f"out / boxes: expected {n} rows, got {out.shape[0]} and {boxes.shape[0]}")
-    _i32_table(crop_xyf, "crop_xyf", ((n + g - 1) // g, 3), out)
-    if out_u8 is not None and not (torch.is_tensor(out_u8) and out_u8.is_cuda and out_u8.device == out.device and out_u8.dtype == torch.uint8
-                                   and out_u8.is_contiguous() and tuple(out_u8.shape) == (n, crop, crop, 3)):
-        raise ValueError(f"out_u8: expected a contiguous uint8 [{n}, {crop}, {crop}, 3] tensor on the GPU of out")
-    entry, how = _yuv_entry("cer_frames_transform_boxes", yuv)
-    check(entry(ptr(frames), *how, n, h, w, ptr(boxes), ptr(meta), ptr(data), store.max_side, store.max_rows, store.max_ks,
-                int(size), crop, ptr(crop_xyf), g, float(mean), float(std), ptr(out), ptr(out_u8), current_stream()),
-          entry.__name__)
+    _transform_rows(frames, boxes, store, size, crop_xyf, frames_per_group, mean, std, out, out_u8, yuv)
 
 
 def frames_stream_append_boxes(frames, boxes, store, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None):
     """``frames_stream_append`` of full frames with one box per row: row m of the row table is packed frame m, cropped to
     ``boxes[m]`` as ``frames_transform_boxes`` does, and lands in slot (row_stream[m], row_pos[m] % Rf).  The bytes are
     ``return_u8`` of ``FrameTransform(..., boxes=)`` for the same frame, box and crop entry.  ``yuv``: as there."""
-    s, rf, crop = _u8_ring(u8ring)
-    n, h, w, meta, data = _box_args(frames, boxes, store, size, u8ring, yuv)
-    m = _row_table(row_stream, row_pos, u8ring)
-    if boxes.shape[0] != m:
-        raise ValueError(f"boxes: expected one box per row [{m}, 4], got {tuple(boxes.shape)}")
-    _i32_table(crop_xyf, "crop_xyf", (s, 3), u8ring)
-    entry, how = _yuv_entry("cer_frames_stream_append_boxes", yuv)
-    check(entry(ptr(frames), *how, n, h, w, ptr(boxes), ptr(meta), ptr(data), store.max_side, store.max_rows, store.max_ks,
-                int(size), crop, ptr(crop_xyf), ptr(row_stream), ptr(row_pos), m, int(max_count), ptr(u8ring), s, rf,
-                current_stream()), entry.__name__)
-    if STREAM_TRACE is not None:
-        STREAM_TRACE.append(("frames_append_boxes", 0))
-
-
-# ------------------------------------------------------------------ per-frame affine maps (csrc/frames_affine.hip)
-def stream_row_affine_table(positions, counts, affines, device):
-    """``stream_row_table`` and the affines of the same rows in ONE upload: ``affines`` float64 [M, 6] on the host, row m the
-    Pillow coefficients of packed frame m -> (row_stream [M], row_pos [M], affines [M, 6] float64), views of one fresh int32
-    tensor on ``device``.  The doubles travel as int32 pairs at the head of the tensor, so they sit at its 8-byte aligned
-    start whatever M."""
-    streams, pos = _stream_rows(positions, counts)
-    m = len(streams)
-    affines = np.ascontiguousarray(affines, dtype=np.float64)
-    if affines.shape != (m, 6):
-        raise ValueError(f"stream_row_affine_table: expected one affine per row [{m}, 6], got {affines.shape}")
-    host = np.empty(14 * m, np.int32)
-    host[:12 * m], host[12 * m:13 * m], host[13 * m:] = affines.ravel().view(np.int32), streams, pos
-    table = torch.from_numpy(host).to(device)
-    return table[12 * m:13 * m], table[13 * m:], table[:12 * m].view(torch.float64).view(m, 6)
-
-
-def _affine_args(frames, affines, geom, size, crop, like, yuv=None):
-    """The checks the two affine entries share.  Returns (n, H, W, bounds, coef)."""
-    if yuv is not None:
-        n, h, w = _yuv_frames(frames, yuv, like)
-    elif not (torch.is_tensor(frames) and frames.is_cuda and frames.device == like.device and frames.dtype == torch.uint8
-              and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
-        raise ValueError(f"frames: expected a contiguous uint8 [n >= 1, H, W, 3] tensor on the GPU ({like.device}), got "
-                         f"{(frames.dtype, frames.device, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
-    else:
-        n, h, w, _ = frames.shape
-    if geom.size != int(size):
-        raise ValueError(f"geom: built for size {geom.size}, not {size}")
-    if not (torch.is_tensor(affines) and affines.is_cuda and affines.device == like.device and affines.dtype == torch.float64
-            and affines.is_contiguous() and affines.dim() == 2 and affines.shape[1] == 6 and affines.data_ptr() % 8 == 0):
-        raise ValueError(f"affines: expected a contiguous, 8-byte aligned float64 [rows, 6] tensor on the GPU ({like.device}), got "
-                         f"{(affines.dtype, affines.device, tuple(affines.shape)) if torch.is_tensor(affines) else type(affines)}")
-    geom.check_crop(crop)
-    bounds, coef = geom.on(like.device)
-    return n, h, w, bounds, coef
+    _append_rows(frames, boxes, store, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv)
 
 
 def frames_transform_affine(frames, affines, geom, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None, yuv=None):
@@ -2202,38 +2222,14 @@ def frames_transform_affine(frames, affines, geom, size, crop_xyf, frames_per_gr
     1e300 -- gives the all-zero picture and no access outside ``frames``.  ``geom``: ``frames.affine_geometry(A, size)``;
     ``crop_xyf`` int32 [groups, 3] on the GPU, one entry per ``frames_per_group`` frames.  ``yuv``: ``frames`` are 4:2:0
     frames [n, H * 3 / 2, W] (``_yuv_frames``); the four pixels of a sample are converted, then interpolated."""
-    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4
-            and out.shape[1] == 3 and out.shape[2] == out.shape[3]):
-        raise ValueError("out: expected a contiguous float32 [n, 3, crop, crop] GPU tensor")
-    crop, g = out.shape[2], int(frames_per_group)
-    n, h, w, bounds, coef = _affine_args(frames, affines, geom, size, crop, out, yuv)
-    if out.shape[0] != n or affines.shape[0] != n or g < 1:
-        raise ValueError(f"out / affines: expected {n} rows, got {out.shape[0]} and {affines.shape[0]}")
-    _i32_table(crop_xyf, "crop_xyf", ((n + g - 1) // g, 3), out)
-    if out_u8 is not None and not (torch.is_tensor(out_u8) and out_u8.is_cuda and out_u8.device == out.device and out_u8.dtype == torch.uint8
-                                   and out_u8.is_contiguous() and tuple(out_u8.shape) == (n, crop, crop, 3)):
-        raise ValueError(f"out_u8: expected a contiguous uint8 [{n}, {crop}, {crop}, 3] tensor on the GPU of out")
-    entry, how = _yuv_entry("cer_frames_transform_affine", yuv)
-    check(entry(ptr(frames), *how, n, h, w, ptr(affines), ptr(bounds), ptr(coef), geom.ks, geom.align_size, geom.span, int(size),
-                crop, ptr(crop_xyf), g, float(mean), float(std), ptr(out), ptr(out_u8), current_stream()), entry.__name__)
+    _transform_rows(frames, affines, geom, size, crop_xyf, frames_per_group, mean, std, out, out_u8, yuv)
 
 
 def frames_stream_append_affine(frames, affines, geom, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None):
     """``frames_stream_append`` of full frames with one affine per row: row m of the row table is packed frame m, warped by
     ``affines[m]`` as ``frames_transform_affine`` does, and lands in slot (row_stream[m], row_pos[m] % Rf).  The bytes are
     ``return_u8`` of ``FrameTransform.aligned`` for the same frame, affine and crop entry.  ``yuv``: as there."""
-    s, rf, crop = _u8_ring(u8ring)
-    n, h, w, bounds, coef = _affine_args(frames, affines, geom, size, crop, u8ring, yuv)
-    m = _row_table(row_stream, row_pos, u8ring)
-    if affines.shape[0] != m:
-        raise ValueError(f"affines: expected one affine per row [{m}, 6], got {tuple(affines.shape)}")
-    _i32_table(crop_xyf, "crop_xyf", (s, 3), u8ring)
-    entry, how = _yuv_entry("cer_frames_stream_append_affine", yuv)
-    check(entry(ptr(frames), *how, n, h, w, ptr(affines), ptr(bounds), ptr(coef), geom.ks, geom.align_size, geom.span, int(size),
-                crop, ptr(crop_xyf), ptr(row_stream), ptr(row_pos), m, int(max_count), ptr(u8ring), s, rf, current_stream()),
-          entry.__name__)
-    if STREAM_TRACE is not None:
-        STREAM_TRACE.append(("frames_append_affine", 0))
+    _append_rows(frames, affines, geom, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv)
 
 
 def frames_stream_gather(u8ring, row_stream, row_pos, mean=0.5, std=0.5):
@@ -2264,9 +2260,7 @@ def decision_stream_state(streams, n_out, *, window=None, max_new=32, classify=T
             state["first"] = torch.full((streams, n_out), DECISION_NEVER, dtype=torch.int64, device=device)
             state["sprob"] = torch.zeros((streams, n_out), dtype=torch.float64, device=device)
         return state
-    r = 1
-    while r < int(window) + int(max_new):
-        r *= 2
+    r = pow2_at_least(int(window) + int(max_new))
     return {"zring": torch.zeros((streams, r, n_out), dtype=torch.float32, device=device)}
 
 

@@ -29,10 +29,7 @@ from .temporal_convnet import TemporalConvNet
 
 def ring_frames(k, dil, max_new):
     """Smallest power of two that holds the (k - 1) d frames of history a conv reaches back plus ``max_new`` new ones."""
-    need, r = (k - 1) * dil + max_new, 1
-    while r < need:
-        r *= 2
-    return r
+    return ops.pow2_at_least((k - 1) * dil + max_new)
 
 
 class _Lockstep(tuple):

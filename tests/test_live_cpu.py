@@ -170,6 +170,43 @@ def test_wrappers_refuse_cpu_and_wrong_dtype_tensors():
                                  i32, i32, 1, ring)
 
 
+class _OnGpu(torch.Tensor):
+    """A CPU tensor that says it is on the GPU: the wrappers ask ``is_cuda`` and compare devices, and every check runs before
+    the library is loaded, so the refusals after the first can be reached without a GPU."""
+    is_cuda = True
+
+
+def test_clip_wrapper_refuses_by_argument_name_before_the_library_is_loaded():
+    from feature_vs_text_compound_emotion_amd import ops
+    gpu = lambda t: t.as_subclass(_OnGpu)      # noqa: E731
+    frames = gpu(torch.zeros((2, 8, 8, 3), dtype=torch.uint8))      # two 8 x 8 frames, size 6, crop 4
+    tables = tuple(gpu(torch.zeros((6, k), dtype=torch.int32)) for k in (2, 3, 2, 3))
+    cx, out, u8 = gpu(torch.zeros((2, 3), dtype=torch.int32)), gpu(torch.zeros((2, 3, 4, 4))), gpu(torch.zeros((2, 4, 4, 3), dtype=torch.uint8))
+
+    def call(frames=frames, tables=tables, cx=cx, group=1, out=out, u8=u8, **kw):
+        ops.frames_transform(frames, tables, 8, 6, cx, group, 0.5, 0.5, out, u8, **kw)
+    bad_table = lambda i, t: tables[:i] + (t,) + tables[i + 1:]      # noqa: E731
+    for match, kw in (("frames: ", {"frames": torch.zeros((2, 8, 8, 3), dtype=torch.uint8)}),      # a CPU tensor
+                      ("frames: ", {"frames": gpu(torch.zeros((2, 8, 8, 4), dtype=torch.uint8))}),
+                      ("frames: ", {"frames": frames[:1]}),                                      # one frame for two rows of out
+                      ("out: ", {"out": torch.zeros((2, 3, 4, 4))}),                             # a CPU float tensor
+                      ("out: ", {"out": gpu(torch.zeros((2, 3, 4, 4), dtype=torch.float64))}),
+                      ("out: ", {"out": gpu(torch.zeros((2, 4, 4, 3)))}),
+                      ("out_u8: ", {"u8": gpu(torch.zeros((2, 4, 4, 3)))}),
+                      ("out_u8: ", {"u8": u8[:1]}),
+                      ("crop_xyf: ", {"cx": cx[:1]}),                                            # one entry for two groups
+                      ("crop_xyf: ", {"group": 2}),                                              # two entries for one group
+                      ("crop_xyf: ", {"cx": gpu(torch.zeros((2, 3), dtype=torch.int64))}),
+                      ("frames_per_group", {"group": 0}),
+                      ("hcoef: ", {"tables": bad_table(1, gpu(torch.zeros((6, 3), dtype=torch.int64)))}),
+                      ("vbounds: ", {"tables": bad_table(2, gpu(torch.zeros((6, 2))))}),
+                      ("hbounds: ", {"tables": bad_table(0, gpu(torch.zeros((5, 2), dtype=torch.int32)))}),
+                      ("vcoef: ", {"tables": bad_table(3, torch.zeros((6, 3), dtype=torch.int32))}),
+                      ("yuv: ", {"yuv": object()})):
+        with pytest.raises(ValueError, match="^" + match):
+            call(**kw)
+
+
 def test_c_entries_refuse_before_any_launch():
     from feature_vs_text_compound_emotion_amd import _lib
     lib = _lib.load()
