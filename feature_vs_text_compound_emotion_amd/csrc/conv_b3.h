@@ -11,8 +11,6 @@ typedef __attribute__((address_space(3))) void *lds_ptr_t;
 
 __device__ __forceinline__ bf16x8 as_bf16x8(const u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ int swz16(int q) { return (0x78 >> (2 * q)) & 3; }  // F = {0, 2, 3, 1}
 
 int conv_b3_patch_launch(int tile, const ConvArgs &a, hipStream_t st);  // conv_b3_patch.hip

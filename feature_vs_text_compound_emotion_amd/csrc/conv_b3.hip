@@ -181,13 +181,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_b3_dma16_kernel
             }
     }
 
-    // ---- epilogue ----
-    // Accumulator layout: D[i = cout][j = pixel] of a 16x16 tile, lane = couts 4*(lane>>4) + 0..3 of pixel lane&15.  Storing
-    // straight from it means 16 scattered 16-byte pieces per instruction and one fully inlined copy of the (large) fused
-    // epilogue per 16x16 tile -- 20-40k instructions, several times the instruction cache, and as long as the whole K loop
-    // of a K = 576 layer.  So the tile goes through LDS once (the staging buffers are free now): rows of BN floats, 16-byte
-    // granules XOR-swizzled by (row & 15) so that the 16 pixels of a ds_write_b128 group hit 16 different granules; then
-    // ONE compact loop in which consecutive lanes own consecutive couts of a pixel (1 KiB contiguous per wave store).
+    // ---- staged epilogue (why and how: conv_common.h, "staged epilogue") ----
+    // Written out here, not called as epi_stage / epi_staged_rows: through the helpers hipcc allocates the bf16x3 kernels
+    // differently (this kernel's 256 x 64 tile 127 instead of 121 VGPRs, conv_b3_patch_kernel<64> 72 instead of 63 SGPR spills) and
+    // four per-kernel timings got slower, tile 59's generic epilogue by 5 %.  The narrow twin calls the helpers.
     constexpr bool LDSEPI = BM * BN * 4 <= STAGES * BUF;
     if constexpr (LDSEPI) {
         constexpr int G = BN / 4;               // 16-byte granules per row (>= 16)
@@ -261,16 +258,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_b3_dma16_kernel
                 red[(r0 * 2 + 1) * BN + g * 4 + e] = s2[e];
             }
             __syncthreads();
-            if (tid < BN && c0 + tid < p.Cout) {
-                float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-                for (int w = 0; w < RPI; ++w) {
-                    t1 += red[(w * 2 + 0) * BN + tid];
-                    t2 += red[(w * 2 + 1) * BN + tid];
-                }
-                p.stats[((size_t)tile_m * 2 + 0) * p.Cout + c0 + tid] = t1;
-                p.stats[((size_t)tile_m * 2 + 1) * p.Cout + c0 + tid] = t2;
-            }
+            epi_stats_flush<RPI, BN>(p, red, tid, c0, (size_t)tile_m);
         }
         return;
     }
@@ -329,16 +317,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void conv_b3_dma16_kernel
             });
         });
         __syncthreads();
-        if (tid < BN && c0 + tid < p.Cout) {
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < WP; ++w) {
-                s1 += red[(w * 2 + 0) * BN + tid];
-                s2 += red[(w * 2 + 1) * BN + tid];
-            }
-            p.stats[((size_t)tile_m * 2 + 0) * p.Cout + c0 + tid] = s1;
-            p.stats[((size_t)tile_m * 2 + 1) * p.Cout + c0 + tid] = s2;
-        }
+        epi_stats_flush<WP, BN>(p, red, tid, c0, (size_t)tile_m);
     }
 }
 

@@ -286,7 +286,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_patch_kernel(ConvArgs
     }
 
     // ---- staged epilogue (every other launch): accumulators -> LDS (fp32, swizzled granules) -> compact coalesced loop, one patch
-    // row per iteration ----
+    // row per iteration; conv_common.h's epi_stage / epi_staged_patch_rows written out (conv_b3.hip's epilogue says why) ----
     constexpr int G = BN / 4, RPI = NT / G;
     static_assert(NT % G == 0 && RPI % 16 == 0 && 256 * BN * 4 <= SINK, "whole patch rows of 16 pixels per loop iteration; one pass");
     float *Ct = reinterpret_cast<float *>(smem_b3p);
@@ -336,16 +336,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_patch_kernel(ConvArgs
             red[(r0 * 2 + 1) * BN + g * 4 + t] = s2[t];
         }
         __syncthreads();
-        if (tid < BN && c0 + tid < p.Cout) {
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < RPI; ++w) {
-                t1 += red[(w * 2 + 0) * BN + tid];
-                t2 += red[(w * 2 + 1) * BN + tid];
-            }
-            p.stats[((size_t)patch * 2 + 0) * p.Cout + c0 + tid] = t1;
-            p.stats[((size_t)patch * 2 + 1) * p.Cout + c0 + tid] = t2;
-        }
+        epi_stats_flush<RPI, BN>(p, red, tid, c0, (size_t)patch);
     }
 }
 
@@ -617,7 +608,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_win_kernel(ConvArgs p
     }
 
     // ---- staged epilogue (every other launch): accumulators -> LDS (fp32, swizzled granules) -> compact coalesced loop over
-    // consecutive output rows ----
+    // consecutive output rows; conv_common.h's epi_stage / epi_staged_rows written out (conv_b3.hip's epilogue says why) ----
     constexpr int G = BN / 4, RPI = NT / G;
     static_assert(NT % G == 0, "one thread per granule");
     float *Ct = reinterpret_cast<float *>(smem_b3p);   // the launcher sizes the LDS for 256 * BN floats at least
@@ -678,16 +669,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_win_kernel(ConvArgs p
             red[(r0 * 2 + 1) * BN + g * 4 + t] = s2[t];
         }
         __syncthreads();
-        if (tid < BN && c0 + tid < p.Cout) {
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < RPI; ++w) {
-                t1 += red[(w * 2 + 0) * BN + tid];
-                t2 += red[(w * 2 + 1) * BN + tid];
-            }
-            p.stats[((size_t)tile_m * 2 + 0) * p.Cout + c0 + tid] = t1;
-            p.stats[((size_t)tile_m * 2 + 1) * p.Cout + c0 + tid] = t2;
-        }
+        epi_stats_flush<RPI, BN>(p, red, tid, c0, (size_t)tile_m);
     }
 }
 

@@ -16,8 +16,9 @@
 // A block owns 256 consecutive flattened output pixels x BN couts (as conv_b3_win_kernel).  Per 32-channel chunk of a phase
 // the window [m0 - Wo - 1, m0 + 255] of the phase image is fetched once by LDS-DMA (P01 only needs [m0 - 1, ..], P00 only
 // [m0, ..]) and serves the phase's 4 / 2 / 2 / 1 steps; the weights stream through the 3-slot ring in STEP ORDER (the host
-// permutes the K columns once: ops.pack_s2d_weight).  Ping-pong phases, counted vmcnt, masks and the epilogue are the
-// window kernel's.  What is new is the window schedule, because a chunk now lasts 1-4 steps instead of 9:
+// permutes the K columns once: ops.pack_s2d_weight).  Ping-pong phases, counted vmcnt and masks are the window kernel's,
+// the epilogue is the staged one of conv_common.h.  What is new is the window schedule, because a chunk now lasts 1-4
+// steps instead of 9:
 //   * a DMA issued by group g in its READ phase of step j may be read by group h in step j + D only if the wave waited
 //     d <= 2 D + h - g - 1 phases later (the end-of-step wait is d = 3, a wait at the end of the NEXT step's READ phase d = 2);
 //   * P11 chunks (4 steps) issue the next window in steps 0 and 1 (D >= 3); P10 / P01 chunks (2 steps) issue it in step 0 and
@@ -276,62 +277,15 @@ __global__ __launch_bounds__(512, 2) void conv_b3_s2d_kernel(ConvArgs p, int NPF
     if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-    // ---- epilogue (conv_b3_win_kernel's): accumulators -> LDS (fp32, swizzled granules) -> coalesced loop over output rows ----
-    constexpr int G = BN / 4, RPI = NT / G;
-    static_assert(NT % G == 0, "one thread per granule");
+    // ---- staged epilogue (conv_common.h) over consecutive output rows; no bias9 on a strided conv: every pixel is case 0 ----
     float *Ct = reinterpret_cast<float *>(smem_b3s);   // the launcher sizes the LDS for 256 * BN floats at least
-    const int g = tid % G, r0 = tid / G;
-    const int c = c0 + g * 4;
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    EpiCtx ec;
-    epi_init(p, c, ec);
+    EpiStaged<BN, NT> es;
+    epi_staged_init(p, tid, c0, es);
     __syncthreads();
-    static_for<TP>([&](auto B) {
-        constexpr int b = decltype(B)::v;
-        const int ml = (b * WP + wp) * 16 + l15;
-        static_for<TC>([&](auto A) {
-            constexpr int a = decltype(A)::v;
-            const int gg = (wc * TC + a) * 4 + kg;
-            *reinterpret_cast<f32x4 *>(Ct + ml * BN + ((gg ^ (ml & 15)) << 2)) = acc[a][b];
-        });
-    });
+    epi_stage<BN, 0, TP>(Ct, acc, [&](int b) { return (b * WP + wp) * 16 + l15; }, [&](int a) { return (wc * TC + a) * 4 + kg; });
     __syncthreads();
-    epi_dispatch(ec.mode, [&](auto MODE_) {
-        for (int ml = r0; ml < BM; ml += RPI) {
-            const int m = m0 + ml;
-            if (m >= p.M) break;
-            const f32x4 q = *reinterpret_cast<const f32x4 *>(Ct + ml * BN + ((g ^ (ml & 15)) << 2));
-            float v[4] = {q[0], q[1], q[2], q[3]};
-            if (c < p.Cout) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    s1[t] += v[t];
-                    s2[t] += v[t] * v[t];
-                }
-                epi_row<decltype(MODE_)::v>(p, ec, m, c, v, 0);   // no bias9 on a strided conv
-            }
-        }
-    });
-    if (p.stats) {
-        __syncthreads();
-        float *red = reinterpret_cast<float *>(smem_b3s);  // [RPI][2][BN]
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            red[(r0 * 2 + 0) * BN + g * 4 + t] = s1[t];
-            red[(r0 * 2 + 1) * BN + g * 4 + t] = s2[t];
-        }
-        __syncthreads();
-        if (tid < BN && c0 + tid < p.Cout) {
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < RPI; ++w) {
-                t1 += red[(w * 2 + 0) * BN + tid];
-                t2 += red[(w * 2 + 1) * BN + tid];
-            }
-            p.stats[((size_t)tile_m * 2 + 0) * p.Cout + c0 + tid] = t1;
-            p.stats[((size_t)tile_m * 2 + 1) * p.Cout + c0 + tid] = t2;
-        }
-    }
+    epi_staged_rows<BN, NT, BM, false, false, false>(p, es, Ct, m0, 0);
+    epi_staged_stats(p, es, Ct, tid, c0, (size_t)tile_m);
 }
 
 // full-window pieces per plane, or 0 when two full buffers do not fit the 98 KiB window region

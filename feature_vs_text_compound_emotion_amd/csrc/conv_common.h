@@ -9,6 +9,7 @@
 namespace cer {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));   // the accumulators of a 16x16 MFMA tile; one granule of the staged epilogue
 
 constexpr int BK = 32;  // K padding granule of packed weights ([Cout][Kpad], Kpad % 32 == 0)
 
@@ -467,6 +468,175 @@ __device__ __forceinline__ void epi_row(const ConvArgs &p, const EpiCtx &e, int 
     }
 }
 
+// Split-K: 4 consecutive couts of output row m into slab `split` of p.y ([split][M][Cout] raw partial sums)
+__device__ __forceinline__ void epi_splitk_store4(const ConvArgs &p, int split, int m, int c, const float v[4]) {
+    float *dst = p.y + ((size_t)split * p.M + m) * p.Cout + c;
+    if (((p.Cout & 3) == 0) && c + 3 < p.Cout) {
+        *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (c + e < p.Cout) dst[e] = v[e];
+    }
+}
+
+// The block's batch statistics from red ([ROWS][2][BN] floats in LDS: ROWS partial sums / sums of squares per cout, complete
+// behind the caller's barrier): thread tid adds the partial rows of cout c0 + tid in ascending order (tests pin the order)
+// into row stats_row of p.stats.
+template <int ROWS, int BN>
+__device__ __forceinline__ void epi_stats_flush(const ConvArgs &p, const float *red, int tid, int c0, size_t stats_row) {
+    if (tid < BN && c0 + tid < p.Cout) {
+        float t1 = 0.f, t2 = 0.f;
+#pragma unroll
+        for (int w = 0; w < ROWS; ++w) {
+            t1 += red[(w * 2 + 0) * BN + tid];
+            t2 += red[(w * 2 + 1) * BN + tid];
+        }
+        p.stats[(stats_row * 2 + 0) * p.Cout + c0 + tid] = t1;
+        p.stats[(stats_row * 2 + 1) * p.Cout + c0 + tid] = t2;
+    }
+}
+
+// ---- staged epilogue: accumulators -> LDS -> compact row loop -> global memory ----
+// Accumulator layout: D[i = cout][j = pixel] of a 16x16 tile, lane = couts 4*(lane>>4) + 0..3 of pixel lane&15.  Storing
+// straight from it means 16 scattered 16-byte pieces per instruction and one fully inlined copy of the (large) fused
+// epilogue per 16x16 tile -- 20-40k instructions, several times the instruction cache, and as long as the whole K loop
+// of a K = 576 layer.  So the tile goes through LDS once (the staging buffers are free now): rows of BN floats, 16-byte
+// granules XOR-swizzled by (row & 15) so that the 16 pixels of a ds_write_b128 group hit 16 different granules; then
+// ONE compact loop in which consecutive lanes own consecutive couts of a pixel (1 KiB contiguous per wave store).
+// The kernel keeps what is its own: where Ct is and how many rows it holds, the barriers around the staging, the pass
+// structure, and the row of p.stats its tile owns.  (conv_b3.hip and conv_b3_patch.hip hold the same text in line.)
+
+// Granule gran (4 couts) of row ml of the staging tile Ct: the swizzle, for epi_stage's stores and the row loops' loads alike
+template <int BN> __device__ __forceinline__ f32x4 *epi_granule(float *Ct, int ml, int gran) {
+    return reinterpret_cast<f32x4 *>(Ct + ml * BN + ((gran ^ (ml & 15)) << 2));
+}
+
+// Pixel tiles B0 .. B0 + NB - 1 of a wave's accumulators -> Ct.  row_of(b): the Ct row of the lane's pixel of the b-th of them;
+// gran_of(a): the granule of the lane's 4 couts of cout tile a (plain, or permuted by epi_cout_of_row).
+template <int BN, int B0, int NB, int TC, int TP, class ROW, class GRAN>
+__device__ __forceinline__ void epi_stage(float *Ct, const f32x4 (&acc)[TC][TP], ROW &&row_of, GRAN &&gran_of) {
+    static_for<NB>([&](auto B) {
+        constexpr int b = decltype(B)::v;
+        const int ml = row_of(b);
+        static_for<TC>([&](auto A) {
+            constexpr int a = decltype(A)::v;
+            *epi_granule<BN>(Ct, ml, gran_of(a)) = acc[a][B0 + b];
+        });
+    });
+}
+
+// A thread's share of the row loops: granule g = couts c .. c + 3 of the rows r0, r0 + RPI, ... of Ct, the sums of the raw
+// results it has stored, and its epilogue constants (their loads are issued here, ahead of the staging barrier).
+template <int BN, int NT> struct EpiStaged {
+    static constexpr int G = BN / 4, RPI = NT / G;   // 16-byte granules per row; rows per loop iteration
+    static_assert(NT % G == 0 && G >= 16, "one thread per granule");
+    int g, r0, c;
+    float s1[4], s2[4];
+    EpiCtx ec;
+};
+
+template <int BN, int NT> __device__ __forceinline__ void epi_staged_init(const ConvArgs &p, int tid, int c0, EpiStaged<BN, NT> &t) {
+    t.g = tid % t.G;
+    t.r0 = tid / t.G;
+    t.c = c0 + t.g * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) t.s1[e] = t.s2[e] = 0.f;
+    epi_init(p, t.c, t.ec);
+}
+
+// One granule of row ml out of Ct; the sums see it only where the couts exist
+template <int BN, int NT> __device__ __forceinline__ void epi_staged_load(const ConvArgs &p, EpiStaged<BN, NT> &t, float *Ct, int ml, float v[4]) {
+    const f32x4 q = *epi_granule<BN>(Ct, ml, t.g);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = q[e];
+    if (t.c < p.Cout) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            t.s1[e] += v[e];
+            t.s2[e] += v[e] * v[e];
+        }
+    }
+}
+
+// Rows r0, r0 + RPI, ... < ROWS of Ct are the consecutive output pixels m_first, m_first + 1, ...: epilogue and store of the
+// thread's granule of each, in ascending order.  COORDS: the pixel's image row / column are tracked (one division before the
+// loop, steps of RPI pixels after it) for the border case 3 ry + rx of bias9 and, with YS2D, for the space-to-depth row of a
+// p.y_s2d launch; without COORDS every pixel is case 0.  SPLITK: a p.split_k > 1 launch stores raw slabs instead.
+template <int BN, int NT, int ROWS, bool SPLITK, bool YS2D, bool COORDS>
+__device__ __forceinline__ void epi_staged_rows(const ConvArgs &p, EpiStaged<BN, NT> &t, float *Ct, int m_first, int split) {
+    static_assert(COORDS || !YS2D, "the space-to-depth row needs the coordinates");
+    constexpr int RPI = EpiStaged<BN, NT>::RPI;
+    int ho = 0, wo = 0;
+    const bool track = COORDS && (p.bias9 || (YS2D && p.y_s2d));
+    if (track) {
+        const int mm = m_first + t.r0 < p.M ? m_first + t.r0 : 0;
+        const int r = mm % (p.Ho * p.Wo);
+        ho = r / p.Wo;
+        wo = r - ho * p.Wo;
+    }
+    epi_dispatch(t.ec.mode, [&](auto MODE_) {
+        for (int ml = t.r0; ml < ROWS; ml += RPI) {
+            const int m = m_first + ml;
+            if (m >= p.M) break;
+            float v[4];
+            epi_staged_load(p, t, Ct, ml, v);
+            if (t.c < p.Cout) {
+                if (SPLITK && p.split_k > 1) {
+                    epi_splitk_store4(p, split, m, t.c, v);
+                } else {
+                    const int ry = ho == 0 ? 0 : (ho == p.Ho - 1 ? 2 : 1), rx = wo == 0 ? 0 : (wo == p.Wo - 1 ? 2 : 1);
+                    epi_row<decltype(MODE_)::v>(p, t.ec, YS2D && p.y_s2d ? s2d_row(m, ho, wo, p.Wo) : m, t.c, v, COORDS ? 3 * ry + rx : 0);
+                }
+            }
+            if (track) {  // advance RPI pixels
+                wo += RPI;
+                while (wo >= p.Wo) {
+                    wo -= p.Wo;
+                    if (++ho == p.Ho) ho = 0;
+                }
+            }
+        }
+    });
+}
+
+// The same for a 16-pixel-wide patch of PH image rows at (y0, x0) of image n, whose pixel (oy, ox) is row 16 oy + ox of Ct:
+// RPI / 16 whole patch rows per iteration, no ragged end.
+template <int BN, int NT, int PH>
+__device__ __forceinline__ void epi_staged_patch_rows(const ConvArgs &p, EpiStaged<BN, NT> &t, float *Ct, int n, int y0, int x0) {
+    constexpr int RPI = EpiStaged<BN, NT>::RPI;
+    static_assert(RPI % 16 == 0, "whole patch rows of 16 pixels per loop iteration");
+    const int ox = t.r0 & 15, gx = x0 + ox;
+    const int rx = gx == 0 ? 0 : (gx == p.W - 1 ? 2 : 1);
+    const size_t pix0 = ((size_t)n * p.H + (size_t)y0) * p.W + gx;
+    epi_dispatch(t.ec.mode, [&](auto MODE_) {
+        for (int oy = t.r0 >> 4; oy < PH; oy += RPI / 16) {
+            const int m = (int)(pix0 + (size_t)oy * p.W);
+            float v[4];
+            epi_staged_load(p, t, Ct, oy * 16 + ox, v);
+            if (t.c < p.Cout) {
+                const int gy = y0 + oy;
+                const int ry = gy == 0 ? 0 : (gy == p.H - 1 ? 2 : 1);
+                epi_row<decltype(MODE_)::v>(p, t.ec, p.y_s2d ? s2d_row(m, gy, gx, p.W) : m, t.c, v, 3 * ry + rx);
+            }
+        }
+    });
+}
+
+// The statistics of a launch that wants them: the threads' sums -> red ([RPI][2][BN] floats over the consumed Ct) -> p.stats
+template <int BN, int NT>
+__device__ __forceinline__ void epi_staged_stats(const ConvArgs &p, const EpiStaged<BN, NT> &t, float *red, int tid, int c0, size_t stats_row) {
+    if (!p.stats) return;
+    __syncthreads();  // Ct has been consumed
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        red[(t.r0 * 2 + 0) * BN + t.g * 4 + e] = t.s1[e];
+        red[(t.r0 * 2 + 1) * BN + t.g * 4 + e] = t.s2[e];
+    }
+    __syncthreads();
+    epi_stats_flush<EpiStaged<BN, NT>::RPI, BN>(p, red, tid, c0, stats_row);
+}
+
 // ---- direct epilogue: accumulators -> global memory without the LDS round trip ----
 // In-kernel stamps of the 64 -> 64 @224x224 launch (tools/exp_stamp.py, profiles/round3_stamps_*.txt): of a block's 15.3 us,
 // 1.5 us went into writing the accumulators to LDS (ds_write_b128 runs at a third of the read rate), 3.2 us into the row
@@ -657,16 +827,7 @@ __device__ __forceinline__ void epi_direct_stats(const ConvArgs &p, float (&s1)[
         }
     }
     __syncthreads();
-    if (tid < BN && c0 + tid < p.Cout) {
-        float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-        for (int w = 0; w < WP; ++w) {
-            t1 += red[(w * 2 + 0) * BN + tid];
-            t2 += red[(w * 2 + 1) * BN + tid];
-        }
-        p.stats[(stats_row * 2 + 0) * p.Cout + c0 + tid] = t1;
-        p.stats[(stats_row * 2 + 1) * p.Cout + c0 + tid] = t2;
-    }
+    epi_stats_flush<WP, BN>(p, red, tid, c0, stats_row);
 }
 
 }  // namespace cer

@@ -273,6 +273,8 @@ __global__ __launch_bounds__(WP * WC * 64, 3) void conv_igemm_kernel(ConvArgs p)
                 float v[4] = {acc[a][b][4 * q + 0], acc[a][b][4 * q + 1], acc[a][b][4 * q + 2], acc[a][b][4 * q + 3]};
                 if (m < p.M && c < p.Cout) {
                     if (p.split_k > 1) {
+                        // epi_splitk_store4's text, in line: called as the helper, hipcc gives the 64 x 64 vector-gather
+                        // instantiation 81 instead of 73 VGPRs, one wave per SIMD fewer
                         float *dst = p.y + ((size_t)split * p.M + m) * p.Cout + c;
                         if (((p.Cout & 3) == 0) && c + 3 < p.Cout) {
                             *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
@@ -318,16 +320,7 @@ __global__ __launch_bounds__(WP * WC * 64, 3) void conv_igemm_kernel(ConvArgs p)
             });
         });
         __syncthreads();
-        if (tid < BN && c0 + tid < p.Cout) {
-            float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < WP; ++w) {
-                s1 += red[(w * 2 + 0) * BN + tid];
-                s2 += red[(w * 2 + 1) * BN + tid];
-            }
-            p.stats[((size_t)tile_m * 2 + 0) * p.Cout + c0 + tid] = s1;
-            p.stats[((size_t)tile_m * 2 + 1) * p.Cout + c0 + tid] = s2;
-        }
+        epi_stats_flush<WP, BN>(p, red, tid, c0, (size_t)tile_m);
     }
 }
 

@@ -7,7 +7,7 @@ namespace cer {
 typedef __bf16 n_bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 n_f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int n_u32x4 __attribute__((ext_vector_type(4)));
-typedef float n_f32x4 __attribute__((ext_vector_type(4)));
+typedef f32x4 n_f32x4;
 typedef __attribute__((address_space(3))) void *n_lds_ptr_t;
 
 template <bool F16>

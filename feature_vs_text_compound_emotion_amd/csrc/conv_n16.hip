@@ -230,91 +230,17 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_kernel(ConvArgs p) {
     constexpr int EPR = n16_epilogue_rows(BM, BN, WP);   // output rows per pass
     constexpr int NPASS = BM / EPR, TPP = TP / NPASS;    // pixel tiles per wave and pass
     static_assert(EPR % (16 * WP) == 0 && TPP * NPASS == TP && EPR * BN * 4 <= 2 * BUF, "epilogue pass geometry");
-    constexpr int G = BN / 4;       // 16-byte granules per row
-    constexpr int RPI = NT / G;     // rows per loop iteration
-    static_assert(NT % G == 0 && G >= 16, "one thread per granule");
     float *Ct = reinterpret_cast<float *>(smem_n16);
-    const int g = tid % G, r0 = tid / G;
-    const int c = c0 + g * 4;
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    EpiCtx ec;
-    epi_init(p, c, ec);
+    EpiStaged<BN, NT> es;
+    epi_staged_init(p, tid, c0, es);
     static_for<NPASS>([&](auto E) {
         constexpr int e = decltype(E)::v;
         __syncthreads();  // the fragment reads of the last step / the previous pass's loop are done
-        static_for<TPP>([&](auto BB) {
-            constexpr int bb = decltype(BB)::v;
-            const int ml = (bb * WP + wp) * 16 + l15;
-            static_for<TC>([&](auto A) {
-                constexpr int a = decltype(A)::v;
-                const int gg = (wc * TC + a) * 4 + kg;
-                *reinterpret_cast<n_f32x4 *>(Ct + ml * BN + ((gg ^ (ml & 15)) << 2)) = acc[a][e * TPP + bb];
-            });
-        });
+        epi_stage<BN, e * TPP, TPP>(Ct, acc, [&](int b) { return (b * WP + wp) * 16 + l15; }, [&](int a) { return (wc * TC + a) * 4 + kg; });
         __syncthreads();
-        int ho = 0, wo = 0;
-        if (p.bias9) {
-            const int mm = m0 + e * EPR + r0 < p.M ? m0 + e * EPR + r0 : 0;
-            const int r = mm % (p.Ho * p.Wo);
-            ho = r / p.Wo;
-            wo = r - ho * p.Wo;
-        }
-        epi_dispatch(ec.mode, [&](auto MODE_) {
-            for (int ml = r0; ml < EPR; ml += RPI) {
-                const int m = m0 + e * EPR + ml;
-                if (m >= p.M) break;
-                const n_f32x4 q = *reinterpret_cast<const n_f32x4 *>(Ct + ml * BN + ((g ^ (ml & 15)) << 2));
-                float v[4] = {q[0], q[1], q[2], q[3]};
-                if (c < p.Cout) {
-    #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        s1[t] += v[t];
-                        s2[t] += v[t] * v[t];
-                    }
-                    if (p.split_k > 1) {
-                        float *dst = p.y + ((size_t)split * p.M + m) * p.Cout + c;
-                        if (((p.Cout & 3) == 0) && c + 3 < p.Cout) {
-                            *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-                        } else {
-    #pragma unroll
-                            for (int t = 0; t < 4; ++t)
-                                if (c + t < p.Cout) dst[t] = v[t];
-                        }
-                    } else {
-                        const int ry = ho == 0 ? 0 : (ho == p.Ho - 1 ? 2 : 1), rx = wo == 0 ? 0 : (wo == p.Wo - 1 ? 2 : 1);
-                        epi_row<decltype(MODE_)::v>(p, ec, m, c, v, 3 * ry + rx);
-                    }
-                }
-                if (p.bias9) {  // advance RPI pixels
-                    wo += RPI;
-                    while (wo >= p.Wo) {
-                        wo -= p.Wo;
-                        if (++ho == p.Ho) ho = 0;
-                    }
-                }
-            }
-        });
+        epi_staged_rows<BN, NT, EPR, true, false, true>(p, es, Ct, m0 + e * EPR, split);
     });
-    if (p.stats) {
-        __syncthreads();  // Ct has been consumed
-        float *red = reinterpret_cast<float *>(smem_n16);  // [RPI][2][BN]
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            red[(r0 * 2 + 0) * BN + g * 4 + t] = s1[t];
-            red[(r0 * 2 + 1) * BN + g * 4 + t] = s2[t];
-        }
-        __syncthreads();
-        if (tid < BN && c0 + tid < p.Cout) {
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < RPI; ++w) {
-                t1 += red[(w * 2 + 0) * BN + tid];
-                t2 += red[(w * 2 + 1) * BN + tid];
-            }
-            p.stats[((size_t)tile_m * 2 + 0) * p.Cout + c0 + tid] = t1;
-            p.stats[((size_t)tile_m * 2 + 1) * p.Cout + c0 + tid] = t2;
-        }
-    }
+    epi_staged_stats(p, es, Ct, tid, c0, (size_t)tile_m);
 }
 
 // fp32 -> one 16-bit plane (optional per-channel affine first), 4 elements per thread; and back

@@ -262,68 +262,17 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_patch_kernel(ConvArg
         if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
     }
 
-    // ---- staged epilogue (every other launch): accumulators -> LDS (fp32, 16-byte granules XOR-swizzled by the row) -> compact
-    // coalesced loop ----
-    constexpr int G = BN / 4, RPI = NT / G;
-    static_assert(NT % G == 0 && RPI % 16 == 0 && 256 * BN * 4 <= SINK, "whole patch rows of 16 pixels per loop iteration; one pass");
+    // ---- staged epilogue (every other launch; conv_common.h), one patch row per iteration ----
+    static_assert(PWD == 16 && 256 * BN * 4 <= SINK, "patch rows of 16 pixels; one pass");
     float *Ct = reinterpret_cast<float *>(smem_n16p);
-    const int g = tid % G, r0 = tid / G, ox = r0 & 15;   // this thread's cout granule, first pixel and patch column
-    const int c = c0 + g * 4;
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    EpiCtx ec;
-    epi_init(p, c, ec);
+    EpiStaged<BN, NT> es;
+    epi_staged_init(p, tid, c0, es);
     __syncthreads();  // the fragment reads of the last step are done
-    static_for<TP>([&](auto B) {
-        constexpr int b = decltype(B)::v;
-        const int ml = (b * WP + wp) * 16 + l15;
-        static_for<TC>([&](auto A) {
-            constexpr int a = decltype(A)::v;
-            const int gg = (wc * TC * 16 + epi_cout_of_row(a * 16 + kg * 4)) >> 2;   // the granule of the lane's 4 couts
-            *reinterpret_cast<n_f32x4 *>(Ct + ml * BN + ((gg ^ (ml & 15)) << 2)) = acc[a][b];
-        });
-    });
+    epi_stage<BN, 0, TP>(Ct, acc, [&](int b) { return (b * WP + wp) * 16 + l15; },
+                         [&](int a) { return (wc * TC * 16 + epi_cout_of_row(a * 16 + kg * 4)) >> 2; });
     __syncthreads();
-    const int gx = px * PWD + ox;
-    const int rx = gx == 0 ? 0 : (gx == p.W - 1 ? 2 : 1);
-    const size_t pix0 = ((size_t)n * p.H + (size_t)py * PH) * p.W + gx;
-    epi_dispatch(ec.mode, [&](auto MODE_) {
-        for (int oy = r0 >> 4; oy < PH; oy += RPI / 16) {
-            const int ml = oy * 16 + ox;
-            const int m = (int)(pix0 + (size_t)oy * p.W);
-            const n_f32x4 q = *reinterpret_cast<const n_f32x4 *>(Ct + ml * BN + ((g ^ (ml & 15)) << 2));
-            float v[4] = {q[0], q[1], q[2], q[3]};
-            if (c < p.Cout) {
-    #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    s1[t] += v[t];
-                    s2[t] += v[t] * v[t];
-                }
-                const int gy = py * PH + oy;
-                const int ry = gy == 0 ? 0 : (gy == p.H - 1 ? 2 : 1);
-                epi_row<decltype(MODE_)::v>(p, ec, p.y_s2d ? s2d_row(m, gy, gx, p.W) : m, c, v, 3 * ry + rx);
-            }
-        }
-    });
-    if (p.stats) {
-        __syncthreads();  // Ct has been consumed
-        float *red = reinterpret_cast<float *>(smem_n16p);  // [RPI][2][BN]
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            red[(r0 * 2 + 0) * BN + g * 4 + t] = s1[t];
-            red[(r0 * 2 + 1) * BN + g * 4 + t] = s2[t];
-        }
-        __syncthreads();
-        if (tid < BN && c0 + tid < p.Cout) {
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < RPI; ++w) {
-                t1 += red[(w * 2 + 0) * BN + tid];
-                t2 += red[(w * 2 + 1) * BN + tid];
-            }
-            p.stats[((size_t)patch * 2 + 0) * p.Cout + c0 + tid] = t1;
-            p.stats[((size_t)patch * 2 + 1) * p.Cout + c0 + tid] = t2;
-        }
-    }
+    epi_staged_patch_rows<BN, NT, PH>(p, es, Ct, n, py * PH, px * PWD);
+    epi_staged_stats(p, es, Ct, tid, c0, (size_t)patch);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -580,79 +529,16 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_win_kernel(ConvArgs 
         if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
     }
 
-    // ---- staged epilogue (every other launch): accumulators -> LDS (fp32, swizzled granules) -> compact coalesced loop over
-    // consecutive output pixels ----
-    constexpr int G = BN / 4, RPI = NT / G;
-    static_assert(NT % G == 0, "one thread per granule");
+    // ---- staged epilogue (every other launch; conv_common.h) over consecutive output pixels ----
     float *Ct = reinterpret_cast<float *>(smem_n16p);   // the launcher sizes the LDS for 256 * BN floats at least
-    const int g = tid % G, r0 = tid / G;
-    const int c = c0 + g * 4;
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    EpiCtx ec;
-    epi_init(p, c, ec);
+    EpiStaged<BN, NT> es;
+    epi_staged_init(p, tid, c0, es);
     __syncthreads();
-    static_for<TP>([&](auto B) {
-        constexpr int b = decltype(B)::v;
-        const int ml = (b * WP + wp) * 16 + l15;
-        static_for<TC>([&](auto A) {
-            constexpr int a = decltype(A)::v;
-            const int gg = (wc * TC * 16 + epi_cout_of_row(a * 16 + kg * 4)) >> 2;   // the granule of the lane's 4 couts
-            *reinterpret_cast<n_f32x4 *>(Ct + ml * BN + ((gg ^ (ml & 15)) << 2)) = acc[a][b];
-        });
-    });
+    epi_stage<BN, 0, TP>(Ct, acc, [&](int b) { return (b * WP + wp) * 16 + l15; },
+                         [&](int a) { return (wc * TC * 16 + epi_cout_of_row(a * 16 + kg * 4)) >> 2; });
     __syncthreads();
-    int ho = 0, wo = 0;
-    const bool track = p.bias9 || p.y_s2d;   // the row loop needs the pixel's image coordinates
-    if (track) {
-        const int mm = m0 + r0 < p.M ? m0 + r0 : 0;
-        const int r = mm % (p.Ho * p.Wo);
-        ho = r / p.Wo;
-        wo = r - ho * p.Wo;
-    }
-    epi_dispatch(ec.mode, [&](auto MODE_) {
-        for (int ml = r0; ml < BM; ml += RPI) {
-            const int m = m0 + ml;
-            if (m >= p.M) break;
-            const n_f32x4 q = *reinterpret_cast<const n_f32x4 *>(Ct + ml * BN + ((g ^ (ml & 15)) << 2));
-            float v[4] = {q[0], q[1], q[2], q[3]};
-            if (c < p.Cout) {
-    #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    s1[t] += v[t];
-                    s2[t] += v[t] * v[t];
-                }
-                const int ry = ho == 0 ? 0 : (ho == p.Ho - 1 ? 2 : 1), rx = wo == 0 ? 0 : (wo == p.Wo - 1 ? 2 : 1);
-                epi_row<decltype(MODE_)::v>(p, ec, p.y_s2d ? s2d_row(m, ho, wo, p.Wo) : m, c, v, 3 * ry + rx);
-            }
-            if (track) {
-                wo += RPI;
-                while (wo >= p.Wo) {
-                    wo -= p.Wo;
-                    if (++ho == p.Ho) ho = 0;
-                }
-            }
-        }
-    });
-    if (p.stats) {
-        __syncthreads();
-        float *red = reinterpret_cast<float *>(smem_n16p);  // [RPI][2][BN]
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            red[(r0 * 2 + 0) * BN + g * 4 + t] = s1[t];
-            red[(r0 * 2 + 1) * BN + g * 4 + t] = s2[t];
-        }
-        __syncthreads();
-        if (tid < BN && c0 + tid < p.Cout) {
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < RPI; ++w) {
-                t1 += red[(w * 2 + 0) * BN + tid];
-                t2 += red[(w * 2 + 1) * BN + tid];
-            }
-            p.stats[((size_t)tile_m * 2 + 0) * p.Cout + c0 + tid] = t1;
-            p.stats[((size_t)tile_m * 2 + 1) * p.Cout + c0 + tid] = t2;
-        }
-    }
+    epi_staged_rows<BN, NT, BM, false, true, true>(p, es, Ct, m0, 0);
+    epi_staged_stats(p, es, Ct, tid, c0, (size_t)tile_m);
 }
 
 // 8-row window pieces per buffer for this conv, or 0 when two buffers do not fit beside the 128-cout weight ring

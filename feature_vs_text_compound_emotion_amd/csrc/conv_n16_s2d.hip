@@ -238,62 +238,15 @@ __global__ __launch_bounds__(512, 2) void conv_n16_s2d_kernel(ConvArgs p, int NP
     if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-    // ---- epilogue (conv_n16_win_kernel's): accumulators -> LDS (fp32, swizzled granules) -> coalesced loop over output rows ----
-    constexpr int G = BN / 4, RPI = NT / G;
-    static_assert(NT % G == 0, "one thread per granule");
+    // ---- staged epilogue (conv_common.h) over consecutive output rows; no bias9 on a strided conv: every pixel is case 0 ----
     float *Ct = reinterpret_cast<float *>(smem_n16s);   // the launcher sizes the LDS for 256 * BN floats at least
-    const int g = tid % G, r0 = tid / G;
-    const int c = c0 + g * 4;
-    float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    EpiCtx ec;
-    epi_init(p, c, ec);
+    EpiStaged<BN, NT> es;
+    epi_staged_init(p, tid, c0, es);
     __syncthreads();
-    static_for<TP>([&](auto B) {
-        constexpr int b = decltype(B)::v;
-        const int ml = (b * WP + wp) * 16 + l15;
-        static_for<TC>([&](auto A) {
-            constexpr int a = decltype(A)::v;
-            const int gg = (wc * TC + a) * 4 + kg;
-            *reinterpret_cast<n_f32x4 *>(Ct + ml * BN + ((gg ^ (ml & 15)) << 2)) = acc[a][b];
-        });
-    });
+    epi_stage<BN, 0, TP>(Ct, acc, [&](int b) { return (b * WP + wp) * 16 + l15; }, [&](int a) { return (wc * TC + a) * 4 + kg; });
     __syncthreads();
-    epi_dispatch(ec.mode, [&](auto MODE_) {
-        for (int ml = r0; ml < BM; ml += RPI) {
-            const int m = m0 + ml;
-            if (m >= p.M) break;
-            const n_f32x4 q = *reinterpret_cast<const n_f32x4 *>(Ct + ml * BN + ((g ^ (ml & 15)) << 2));
-            float v[4] = {q[0], q[1], q[2], q[3]};
-            if (c < p.Cout) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    s1[t] += v[t];
-                    s2[t] += v[t] * v[t];
-                }
-                epi_row<decltype(MODE_)::v>(p, ec, m, c, v, 0);   // no bias9 on a strided conv
-            }
-        }
-    });
-    if (p.stats) {
-        __syncthreads();
-        float *red = reinterpret_cast<float *>(smem_n16s);  // [RPI][2][BN]
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            red[(r0 * 2 + 0) * BN + g * 4 + t] = s1[t];
-            red[(r0 * 2 + 1) * BN + g * 4 + t] = s2[t];
-        }
-        __syncthreads();
-        if (tid < BN && c0 + tid < p.Cout) {
-            float t1 = 0.f, t2 = 0.f;
-#pragma unroll
-            for (int w = 0; w < RPI; ++w) {
-                t1 += red[(w * 2 + 0) * BN + tid];
-                t2 += red[(w * 2 + 1) * BN + tid];
-            }
-            p.stats[((size_t)tile_m * 2 + 0) * p.Cout + c0 + tid] = t1;
-            p.stats[((size_t)tile_m * 2 + 1) * p.Cout + c0 + tid] = t2;
-        }
-    }
+    epi_staged_rows<BN, NT, BM, false, false, false>(p, es, Ct, m0, 0);
+    epi_staged_stats(p, es, Ct, tid, c0, (size_t)tile_m);
 }
 
 // full-window pieces (8 rows), or 0 when two full buffers do not fit the 98 KiB window region

@@ -342,7 +342,10 @@ def test_persistent_patch_kernel_equals_the_one_patch_per_block_kernel(kind, n, 
 # ---- space-to-depth hand-over of the stride-2 units (narrow twins of the bf16x3 tests) ----
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("n,cin,cout,h,w,tile", [(2, 64, 64, 32, 48, 71), (1, 128, 128, 16, 32, 72), (1, 128, 128, 16, 32, 78),
-                                                 (3, 64, 128, 20, 12, 76), (5, 128, 40, 10, 6, 73), (2, 64, 64, 14, 6, 77)])
+                                                 (3, 64, 128, 20, 12, 76), (5, 128, 40, 10, 6, 73), (2, 64, 64, 14, 6, 77),
+                                                 # Cout % 8 == 4: the staged epilogue (Cout % 8 == 0 stores directly)
+                                                 (1, 64, 36, 16, 16, 71), (1, 128, 100, 16, 32, 72), (1, 128, 100, 16, 32, 78),
+                                                 (2, 64, 100, 20, 12, 76), (3, 64, 36, 10, 6, 73), (2, 64, 36, 14, 6, 77)])
 def test_narrow_producer_writes_the_space_to_depth_layout(n, cin, cout, h, w, tile, dtype):
     from feature_vs_text_compound_emotion_amd import ops
     g = torch.Generator().manual_seed(n + cin + h)
