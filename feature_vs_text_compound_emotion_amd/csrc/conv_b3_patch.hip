@@ -20,6 +20,10 @@
 // Against the flat 128-pixel tile this cuts the L2 -> LDS activation traffic of a 3x3 layer from nine fetches of every
 // input line to 1.27 (the halo), the round-1 limiter of the bf16x3 kernel ("both operands' L2 -> LDS
 // traffic"; roofline.traffic 2.2x the algorithmic bytes).
+//
+// Two kernels, ONE step: conv_b3_patch_kernel and conv_b3_win_kernel (below) differ in how a block's 256 pixels map to the
+// image, how the window is fetched (issue_x) and where a pixel fragment sits in LDS (ldb); the unrolled step with its phases,
+// barriers and counted vmcnt is conv_b3.h's b3_step, called by both, so their outputs are bit-equal (tests/test_conv_b3_gpu.py).
 #include "conv_b3.h"
 
 namespace cer {
@@ -58,12 +62,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_patch_kernel(ConvArgs
     const int wp = wave % WP, wc = wave / WP;
     const int kg = lane >> 4, l15 = lane & 15;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    int bid = blockIdx.x;
-    {   // XCD-aware remap (bijective)
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
     const int patch = (int)fdiv((unsigned)bid, geo.tiles_n), tile_n = bid - patch * p.tiles_n;
     const int prw = (int)fdiv((unsigned)patch, geo.pxn), px = patch - prw * (int)geo.pxn.d;
     const int n = (int)fdiv((unsigned)prw, geo.pyn), py = prw - n * (int)geo.pyn.d;
@@ -119,6 +118,9 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_patch_kernel(ConvArgs
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rh, (lds_ptr_t)dst, 16, vo, 0, 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rl, (lds_ptr_t)(real ? dst + XPL : dst), 16, vo, 0, 0, 0);
     };
+    // (The weight ring -- the assignment above and issue_w -- is the same text in conv_b3_win_kernel.  Moved into helpers beside
+    // b3_step, as conv_n16.h has them, it made the compiler spill 10 - 12 more SGPRs in three of the four kernels, and tiles 56
+    // and 59 ran 1 - 5 % and 1 - 3 % slower (profiles/window_step.json): it stays in line.)
     auto issue_w = [&](int cc, int tap, int ring) {
         const bool real = cc < cin_steps;
         const size_t koff = ((size_t)tap * p.Cin + (size_t)cc * 32) * 2;
@@ -151,15 +153,8 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_patch_kernel(ConvArgs
     for (int i = 0; i < XPW; ++i) issue_x(i, 0);
     issue_w(0, 0, 0);
     issue_w(0, 1, 1);
-    if constexpr (!SINGLE) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WQ) : "memory");   // the window and slice 0 (slice 1 may still be in flight)
-        __builtin_amdgcn_s_barrier();
-        if (wc == 1) __builtin_amdgcn_s_barrier();                  // group 1 runs one phase behind group 0
-    }
+    pp_enter<!SINGLE, WQ>(wc);   // the window and slice 0 (slice 1 may still be in flight)
 
-    // One step = one filter tap of one 32-channel chunk; per wave and step WQ weight pieces (slice of step s + 2) and, during
-    // taps 0 .. XPW-1, the two planes of one window piece of the next chunk.  At the top of step s everything issued before
-    // step s-1 must have landed: vmcnt(pieces of the previous step).
     for (int cc = 0; cc < cin_steps; ++cc) {
         const int xcur = SINGLE ? 0 : (cc & 1) * XBYTES;
         if constexpr (SINGLE) {
@@ -174,83 +169,11 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_patch_kernel(ConvArgs
         }
         static_for<9>([&](auto T) {
             constexpr int tap = decltype(T)::v, kh = tap / 3, kw = tap % 3;
-            constexpr int ntap = (tap + 2) % 9, nring = (tap + 2) % 3;
-            const int ncc = cc + (tap + 2 >= 9 ? 1 : 0);
             const unsigned char *Wr = smem + (tap % 3) * WSLICE;
             const unsigned char *Xb = smem + xcur + kh * (WW * 64);
-            // (fragments travel as u32x4 and are re-typed at the MFMA: a lambda returning a __bf16 vector made hipcc's host pass
-            // drop the kernel stub)
             auto lda = [&](int a, int pl) { return *reinterpret_cast<const u32x4 *>(Wr + pl * WPL + arow + a * 16 * 64); };
             auto ldb = [&](int b, int pl) { return *reinterpret_cast<const u32x4 *>(Xb + pl * XPL + bcol[kw] + b * WP * WW * 64); };
-            if constexpr (!SINGLE) {
-                // ---- READ phase: every fragment of the step, then the step's DMA (slice of step + 2, a window piece) ----
-                u32x4 ah[TC], al[TC], bh[TP], bl[TP];
-#pragma unroll
-                for (int a = 0; a < TC; ++a) { ah[a] = lda(a, 0); al[a] = lda(a, 1); }
-#pragma unroll
-                for (int b = 0; b < TP; ++b) { bh[b] = ldb(b, 0); bl[b] = ldb(b, 1); }
-                issue_w(ncc, ntap, nring);
-                if constexpr (tap < XPW) issue_x(tap, cc + 1);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                // ---- MFMA phase: consecutive MFMAs go to different accumulators (lo*hi, hi*lo, hi*hi per accumulator) ----
-#pragma unroll
-                for (int a = 0; a < TC; ++a)
-#pragma unroll
-                    for (int g = 0; g < TP; ++g)
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(al[a]), as_bf16x8(bh[g]), acc[a][g], 0, 0, 0);
-#pragma unroll
-                for (int a = 0; a < TC; ++a)
-#pragma unroll
-                    for (int g = 0; g < TP; ++g)
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(ah[a]), as_bf16x8(bl[g]), acc[a][g], 0, 0, 0);
-#pragma unroll
-                for (int a = 0; a < TC; ++a)
-#pragma unroll
-                    for (int g = 0; g < TP; ++g)
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(ah[a]), as_bf16x8(bh[g]), acc[a][g], 0, 0, 0);
-                // everything this wave issued before this step's READ phase has landed (slice of step + 1, older window pieces)
-                constexpr int cnt = WQ + (tap < XPW ? 2 : 0);
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(cnt) : "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-            } else {
-                // single-phase step: at its top the slice of this step has landed (issued two steps ago); the step issues the
-                // slice of step + 2 after its first MFMA group
-                if (cc == 0 && tap == 0) {
-                    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WQ) : "memory");  // prologue: all but slice 1
-                } else {
-                    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WQ) : "memory");
-                }
-                __builtin_amdgcn_s_barrier();
-                u32x4 ah[TC], al[TC], bh[TP], bl[TP];
-#pragma unroll
-                for (int a = 0; a < TC; ++a) { ah[a] = lda(a, 0); al[a] = lda(a, 1); }
-                bh[0] = ldb(0, 0); bl[0] = ldb(0, 1);
-                bh[1] = ldb(1, 0); bl[1] = ldb(1, 1);
-                static_for<TP>([&](auto G) {
-                    constexpr int g = decltype(G)::v;
-                    if constexpr (g + 2 < TP) { bh[g + 2] = ldb(g + 2, 0); bl[g + 2] = ldb(g + 2, 1); }
-                    if constexpr (g == 0) issue_w(ncc, ntap, nring);
-#pragma unroll
-                    for (int a = 0; a < TC; ++a) {
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(al[a]), as_bf16x8(bh[g]), acc[a][g], 0, 0, 0);
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(ah[a]), as_bf16x8(bl[g]), acc[a][g], 0, 0, 0);
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(ah[a]), as_bf16x8(bh[g]), acc[a][g], 0, 0, 0);
-                    }
-                });
-                __builtin_amdgcn_sched_group_barrier(0x100, 2 * TC + 4, 0);
-                static_for<TP>([&](auto G) {
-                    constexpr int g = decltype(G)::v;
-                    __builtin_amdgcn_sched_group_barrier(0x008, 3 * TC, 0);
-                    if constexpr (g + 2 < TP) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    if constexpr (g == 0) __builtin_amdgcn_sched_group_barrier(0x010, WQ, 0);
-                });
-            }
+            b3_step<tap, TC, TP, WQ, XPW, SINGLE>(acc, cc, lda, ldb, issue_w, issue_x);
         });
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the sink pieces of the last steps (zero fills: they return at once)
@@ -275,15 +198,11 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_patch_kernel(ConvArgs
             constexpr int MODE = decltype(MODE_)::v;
             if constexpr (MODE != EPI_GENERIC) epi_direct_stores<MODE, CER_STORE_BF16, TC, TP>(p, acc, c0 + wc * TC * 16, kg, epx, s1, s2);
         });
-        if constexpr (!SINGLE) {
-            if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
-        }
+        pp_leave<!SINGLE>(wc);
         if (p.stats) epi_direct_stats<TC, WP, BN>(p, s1, s2, reinterpret_cast<float *>(smem_b3p), wp, wc, kg, l15, tid, c0, (size_t)patch);
         return;
     }
-    if constexpr (!SINGLE) {
-        if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
-    }
+    pp_leave<!SINGLE>(wc);
 
     // ---- staged epilogue (every other launch): accumulators -> LDS (fp32, swizzled granules) -> compact coalesced loop, one patch
     // row per iteration; conv_common.h's epi_stage / epi_staged_patch_rows written out (conv_b3.hip's epilogue says why) ----
@@ -350,8 +269,9 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_patch_kernel(ConvArgs
 // plane, fetched once per 32-channel chunk and double buffered; a tap is a row shift kh*W + kw of the fragment address.
 // Taps that fall off the image (zero padding; the previous / next image row or frame in the flat array) are masked per lane:
 // such a lane reads the window's last row, which the DMA zero-fills.  Fragment rows start at any alignment; the swizzle
-// slot = chunk ^ ((row & 4) >> 1) is conflict free for every alignment (tools/check_swizzle.py).  Everything else -- weight
-// ring, counted vmcnt, unrolled taps, ping-pong phases -- is the patch kernel's.
+// slot = chunk ^ ((row & 4) >> 1) is conflict free for every alignment (tools/check_swizzle.py).  The step -- counted vmcnt,
+// unrolled taps, ping-pong phases -- is the function the patch kernel calls (conv_b3.h: b3_step); the weight ring is the patch
+// kernel's text once more (it says why).
 // SINGLE: as in conv_b3_patch_kernel -- 4 waves, one window buffer re-filled per chunk, single-phase steps, two blocks per CU.
 template <int BN, int WP, int WC, bool SINGLE>
 __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_win_kernel(ConvArgs p, int NP, WinGeo geo) {
@@ -375,12 +295,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_win_kernel(ConvArgs p
     const int wp = wave % WP, wc = wave / WP;
     const int kg = lane >> 4, l15 = lane & 15;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
     const int tile_m = (int)fdiv((unsigned)bid, geo.tiles_n), tile_n = bid - tile_m * p.tiles_n;
     const int m0 = tile_m * BM, c0 = tile_n * BN;
     const int cin_steps = p.cin_steps;
@@ -434,6 +349,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_win_kernel(ConvArgs p
         const size_t koff = ((size_t)tap * p.Cin + (size_t)cc * 32) * 2;
 #pragma unroll
         for (int i = 0; i < WQ; ++i) {
+            // (the plane is chosen on the POINTER: a ?: between two buffer resources made hipcc's host pass drop the kernel stub)
             const char *base = (w_plane[i] ? wl : wh) + koff;
             const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(base), 0, (int)OOB, 0x00020000);
             unsigned char *dst = real ? smem + WOFF + ring * WSLICE + w_dst[i] : smem + SINK;
@@ -474,11 +390,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_win_kernel(ConvArgs p
     for (int i = 0; i < XPW; ++i) issue_x(i, 0);
     issue_w(0, 0, 0);
     issue_w(0, 1, 1);
-    if constexpr (!SINGLE) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WQ) : "memory");   // the window and slice 0 (slice 1 may still be in flight)
-        __builtin_amdgcn_s_barrier();
-        if (wc == 1) __builtin_amdgcn_s_barrier();                  // group 1 runs one phase behind group 0
-    }
+    pp_enter<!SINGLE, WQ>(wc);   // the window and slice 0 (slice 1 may still be in flight)
 
     for (int cc = 0; cc < cin_steps; ++cc) {
         const int xcur = SINGLE ? 0 : (cc & 1) * XBYTES;
@@ -494,8 +406,6 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_win_kernel(ConvArgs p
         }
         static_for<9>([&](auto T) {
             constexpr int tap = decltype(T)::v, kh = tap / 3, kw = tap % 3;
-            constexpr int ntap = (tap + 2) % 9, nring = (tap + 2) % 3;
-            const int ncc = cc + (tap + 2 >= 9 ? 1 : 0);
             const unsigned char *Wr = smem + WOFF + (tap % 3) * WSLICE;
             const unsigned char *Xb = smem + xcur;
             const int toff = kh * p.W + kw;
@@ -507,69 +417,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_win_kernel(ConvArgs p
                 baddr[b] = row * 64 + ((kg ^ ((row & 4) >> 1)) << 4);
             }
             auto ldb = [&](int b, int pl) { return *reinterpret_cast<const u32x4 *>(Xb + pl * XPL + baddr[b]); };
-            if constexpr (!SINGLE) {
-                // ---- READ phase: every fragment of the step, then the step's DMA (slice of step + 2, a window piece) ----
-                u32x4 ah[TC], al[TC], bh[TP], bl[TP];
-#pragma unroll
-                for (int a = 0; a < TC; ++a) { ah[a] = lda(a, 0); al[a] = lda(a, 1); }
-#pragma unroll
-                for (int b = 0; b < TP; ++b) { bh[b] = ldb(b, 0); bl[b] = ldb(b, 1); }
-                issue_w(ncc, ntap, nring);
-                if constexpr (tap < XPW) issue_x(tap, cc + 1);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                // ---- MFMA phase: consecutive MFMAs go to different accumulators (lo*hi, hi*lo, hi*hi per accumulator) ----
-#pragma unroll
-                for (int a = 0; a < TC; ++a)
-#pragma unroll
-                    for (int g = 0; g < TP; ++g)
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(al[a]), as_bf16x8(bh[g]), acc[a][g], 0, 0, 0);
-#pragma unroll
-                for (int a = 0; a < TC; ++a)
-#pragma unroll
-                    for (int g = 0; g < TP; ++g)
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(ah[a]), as_bf16x8(bl[g]), acc[a][g], 0, 0, 0);
-#pragma unroll
-                for (int a = 0; a < TC; ++a)
-#pragma unroll
-                    for (int g = 0; g < TP; ++g)
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(ah[a]), as_bf16x8(bh[g]), acc[a][g], 0, 0, 0);
-                // everything this wave issued before this step's READ phase has landed (slice of step + 1, older window pieces)
-                constexpr int cnt = WQ + (tap < XPW ? 2 : 0);
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(cnt) : "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-            } else {
-                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WQ) : "memory");   // this step's slice has landed
-                __builtin_amdgcn_s_barrier();
-                u32x4 ah[TC], al[TC], bh[TP], bl[TP];
-#pragma unroll
-                for (int a = 0; a < TC; ++a) { ah[a] = lda(a, 0); al[a] = lda(a, 1); }
-                bh[0] = ldb(0, 0); bl[0] = ldb(0, 1);
-                bh[1] = ldb(1, 0); bl[1] = ldb(1, 1);
-                static_for<TP>([&](auto G) {
-                    constexpr int g = decltype(G)::v;
-                    if constexpr (g + 2 < TP) { bh[g + 2] = ldb(g + 2, 0); bl[g + 2] = ldb(g + 2, 1); }
-                    if constexpr (g == 0) issue_w(ncc, ntap, nring);
-#pragma unroll
-                    for (int a = 0; a < TC; ++a) {
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(al[a]), as_bf16x8(bh[g]), acc[a][g], 0, 0, 0);
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(ah[a]), as_bf16x8(bl[g]), acc[a][g], 0, 0, 0);
-                        acc[a][g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(ah[a]), as_bf16x8(bh[g]), acc[a][g], 0, 0, 0);
-                    }
-                });
-                __builtin_amdgcn_sched_group_barrier(0x100, 2 * TC + 4, 0);
-                static_for<TP>([&](auto G) {
-                    constexpr int g = decltype(G)::v;
-                    __builtin_amdgcn_sched_group_barrier(0x008, 3 * TC, 0);
-                    if constexpr (g + 2 < TP) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    if constexpr (g == 0) __builtin_amdgcn_sched_group_barrier(0x010, WQ, 0);
-                });
-            }
+            b3_step<tap, TC, TP, WQ, XPW, SINGLE>(acc, cc, lda, ldb, issue_w, issue_x);
         });
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -597,15 +445,11 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_b3_win_kernel(ConvArgs p
             constexpr int MODE = decltype(MODE_)::v;
             if constexpr (MODE != EPI_GENERIC) epi_direct_stores<MODE, CER_STORE_BF16, TC, TP>(p, acc, c0 + wc * TC * 16, kg, epx, s1, s2);
         });
-        if constexpr (!SINGLE) {
-            if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
-        }
+        pp_leave<!SINGLE>(wc);
         if (p.stats) epi_direct_stats<TC, WP, BN>(p, s1, s2, reinterpret_cast<float *>(smem_b3p), wp, wc, kg, l15, tid, c0, (size_t)tile_m);
         return;
     }
-    if constexpr (!SINGLE) {
-        if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
-    }
+    pp_leave<!SINGLE>(wc);
 
     // ---- staged epilogue (every other launch): accumulators -> LDS (fp32, swizzled granules) -> compact coalesced loop over
     // consecutive output rows; conv_common.h's epi_stage / epi_staged_rows written out (conv_b3.hip's epilogue says why) ----
@@ -684,23 +528,15 @@ static int launch_b3_win(const ConvArgs &a, hipStream_t st) {
     const int np = b3_win_pieces(a);
     size_t lds = (size_t)(SINGLE ? 2 : 4) * np * 1024 + 3 * (size_t)2 * BN * 64 + 1024;
     if (lds < (size_t)256 * BN * 4) lds = (size_t)256 * BN * 4;   // the epilogue's accumulator tile
-    auto k = conv_b3_win_kernel<BN, WP, WC, SINGLE>;
-    if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const WinGeo geo{make_fastdiv((unsigned)a.tiles_n), make_fastdiv((unsigned)(a.H * a.W)), make_fastdiv((unsigned)a.W)};
-    CER_LAUNCH(k, dim3(a.tiles_m * a.tiles_n, 1, 1), dim3(WP * WC * 64), lds, st, a, np, geo);
-    CER_HIP_CHECK(hipGetLastError());
-    return CER_OK;
+    return launch_lds(conv_b3_win_kernel<BN, WP, WC, SINGLE>, dim3(a.tiles_m * a.tiles_n, 1, 1), dim3(WP * WC * 64), lds, st, a, np, geo);
 }
 
 template <int BN, int WP, int WC, bool SINGLE = false>
 static int launch_b3_patch(const ConvArgs &a, hipStream_t st) {
     const size_t lds = (size_t)(SINGLE ? 1 : 2) * 2 * 21 * 1024 + 3 * (size_t)2 * BN * 64 + 1024;
-    auto k = conv_b3_patch_kernel<BN, WP, WC, SINGLE>;
-    if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const B3PatchGeo geo{make_fastdiv((unsigned)a.tiles_n), make_fastdiv((unsigned)(a.W / 16)), make_fastdiv((unsigned)(a.H / 16))};
-    CER_LAUNCH(k, dim3(a.tiles_m * a.tiles_n, 1, 1), dim3(WP * WC * 64), lds, st, a, geo);
-    CER_HIP_CHECK(hipGetLastError());
-    return CER_OK;
+    return launch_lds(conv_b3_patch_kernel<BN, WP, WC, SINGLE>, dim3(a.tiles_m * a.tiles_n, 1, 1), dim3(WP * WC * 64), lds, st, a, geo);
 }
 
 bool conv_b3_patch_ok(const ConvArgs &a) {

@@ -69,6 +69,37 @@ template <int N, class F> __device__ __forceinline__ void static_for(F &&f) {
     }
 }
 
+// Launch kernel k with `lds` bytes of dynamic LDS (past 64 KiB the kernel's limit has to be raised first)
+template <class K, class... A> int launch_lds(K k, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+    if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    CER_LAUNCH(k, grid, block, lds, st, args...);
+    CER_HIP_CHECK(hipGetLastError());
+    return CER_OK;
+}
+
+// XCD-aware block remap (bijective on [0, nwg)): the hardware deals consecutive workgroup ids round-robin to the 8 XCDs, so
+// the blocks that share an XCD's L2 take neighbouring tiles
+__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
+    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
+// Ping-pong phases of the window-resident kernels (conv_n16.h / conv_b3.h: the step): the wave group wc = 1 runs one phase
+// behind group 0.  pp_enter opens the K loop once everything but the wave's newest VM0 DMA pieces has landed; pp_leave
+// closes it: group 0 pairs with group 1's last phase boundary.
+template <bool PP, int VM0> __device__ __forceinline__ void pp_enter(int wc) {
+    if constexpr (PP) {
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM0) : "memory");
+        __builtin_amdgcn_s_barrier();
+        if (wc == 1) __builtin_amdgcn_s_barrier();
+    }
+}
+template <bool PP> __device__ __forceinline__ void pp_leave(int wc) {
+    if constexpr (PP) {
+        if (wc == 0) __builtin_amdgcn_s_barrier();
+    }
+}
+
 // bf16 <-> f32 bit helpers; the split is round-to-nearest-even (the hardware cvt) on both parts
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
 __device__ __forceinline__ uint16_t f32_to_bf16(float f) {

@@ -57,12 +57,7 @@ __global__ __launch_bounds__(WP * WC * 64, 3) void conv_igemm_kernel(ConvArgs p)
 
     // XCD-aware tile order: blocks b and b+8 share an L2, so give each XCD a
     // contiguous run of tiles (cout tile fastest: neighbours share activations).
-    const int nwg = p.tiles_m * p.tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
     const int tile_n = bid % p.tiles_n, tile_m = bid / p.tiles_n;
     const int m0 = tile_m * BM, c0 = tile_n * BN;
     const int split = blockIdx.z;

@@ -52,12 +52,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_kernel(ConvArgs p) {
     const int wp = wave % WP, wc = wave / WP;
     const int kg = lane >> 4, l15 = lane & 15;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    int bid = blockIdx.x;
-    {   // XCD-aware remap (bijective): blocks that share an XCD's L2 take neighbouring tiles
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
     const int tile_n = bid % p.tiles_n, tile_m = bid / p.tiles_n;
     const int m0 = tile_m * BM, c0 = tile_n * BN;
     const int split = blockIdx.z;
@@ -272,17 +267,8 @@ static int launch_n16(const ConvArgs &a, hipStream_t st) {
         return cer_set_error(CER_ERR_UNSUPPORTED, "conv2d (narrow): weight panel exceeds 31-bit offsets");
     const size_t lds = (size_t)2 * (BM + BN) * 128;
     const dim3 grid(a.tiles_m * a.tiles_n, 1, a.split_k), block(WP * WC * 64);
-    if (a.narrow == CER_STORE_F16) {
-        auto k = conv_n16_kernel<BM, BN, WP, WC, true, ILV>;
-        if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CER_LAUNCH(k, grid, block, lds, st, a);
-    } else {
-        auto k = conv_n16_kernel<BM, BN, WP, WC, false, ILV>;
-        if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CER_LAUNCH(k, grid, block, lds, st, a);
-    }
-    CER_HIP_CHECK(hipGetLastError());
-    return CER_OK;
+    return a.narrow == CER_STORE_F16 ? launch_lds(conv_n16_kernel<BM, BN, WP, WC, true, ILV>, grid, block, lds, st, a)
+                                     : launch_lds(conv_n16_kernel<BM, BN, WP, WC, false, ILV>, grid, block, lds, st, a);
 }
 
 // tile ids (desc.tile): 0 = auto; flat kernels (K step 64): 63 = 256x64, 64 = 128x128, 65 = 128x64, 66 = 64x64, 67 = 64x128

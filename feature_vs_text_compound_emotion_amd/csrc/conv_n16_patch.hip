@@ -20,6 +20,12 @@
 //
 // L2 -> LDS bytes per 256 pixels x 64 channels x 9 taps: 41 KiB of window + 9 weight slices, against 9 x 32 KiB of
 // activations + the same 9 slices for the flat 256-row tile.
+//
+// Two kernels, ONE step: conv_n16_patch_kernel (16 x 16 patches) and conv_n16_win_kernel (256 consecutive pixels, any image
+// size) differ in how a block's 256 pixels map to the image, how the window is fetched (issue_x) and where a pixel fragment
+// sits in LDS (ldb).  The weight ring (n16_ring_assign / n16_ring_issue) and the unrolled step with its barriers, counted
+// vmcnt and DMA placement (n16_step_top / n16_step) are conv_n16.h's, called by both: what the two compute per accumulator is
+// the same instruction sequence, and their outputs are bit-equal (tests/test_conv_n16_gpu.py).
 #include "conv_n16.h"
 
 namespace cer {
@@ -32,15 +38,12 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_patch_kernel(ConvArg
     constexpr int XPIECES = (WROWS + 7) / 8;                       // 41 one-KiB pieces (328 rows, the last 4 unused)
     constexpr int XPW = (XPIECES + NW - 1) / NW;                   // window pieces per wave and chunk
     constexpr int XBYTES = XPIECES * 1024;
-    constexpr int WSLICE = BN * 128, RING = 3;
-    static_assert(BN % (8 * NW) == 0, "weight-slice pieces are dealt round-robin to the waves");
-    constexpr int WQ = BN / (8 * NW);                               // weight pieces per wave and step
     constexpr int TP = PH / WP, TC = BN / (16 * WC);                // 16x16 MFMA tiles per wave: output rows x cout tiles
+    constexpr int WSLICE = BN * 128, RING = 3, WQ = BN / (8 * NW);     // weight slice bytes, ring slots, pieces per wave and step
     static_assert(PH % WP == 0 && XBUFS >= 1 && XBUFS <= 2 && (XBUFS == 1 || XPW <= 9) && TC % 2 == 0, "geometry");
     static_assert(!PP || (WP == 4 && WC == 2 && XBUFS == 2 && (BN / 16) % 4 == 0), "ping-pong: waves w and w + 4 share a SIMD and split the couts");
     constexpr int WOFF = XBUFS * XBYTES, SINK = WOFF + RING * WSLICE;  // LDS map: windows | weight ring | 1 KiB sink
     constexpr unsigned OOB = 0x80000000u;
-    constexpr int NGRP = 2 * TP;                                    // MFMA groups (kk, b) per step, TC MFMAs each
     extern __shared__ __attribute__((aligned(16))) uint16_t smem_n16p[];
     unsigned char *smem = reinterpret_cast<unsigned char *>(smem_n16p);
 
@@ -49,12 +52,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_patch_kernel(ConvArg
     const int wp = wave % WP, wc = wave / WP;
     const int kg = lane >> 4, l15 = lane & 15;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    int bid = blockIdx.x;
-    {   // XCD-aware remap (bijective): blocks that share an XCD's L2 take neighbouring patches
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
     const int patch = (int)fdiv((unsigned)bid, geo.tiles_n), tile_n = bid - patch * p.tiles_n;
     const int prw = (int)fdiv((unsigned)patch, geo.pxn), px = patch - prw * (int)geo.pxn.d;
     const int n = (int)fdiv((unsigned)prw, geo.pyn), py = prw - n * (int)geo.pyn.d;
@@ -68,26 +66,9 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_patch_kernel(ConvArg
     const int prow = lane >> 3, slot = lane & 7;
     unsigned w_off[WQ];
     int w_piece[WQ];
-#pragma unroll
-    for (int i = 0; i < WQ; ++i) {
-        // PP: the group's own cout half (BN / 16 pieces of 8 rows) dealt to its four waves; else all pieces over all waves
-        w_piece[i] = PP ? (wave >> 2) * (BN / 16) + (wave & 3) + 4 * i : wave + NW * i;
-        const int row = w_piece[i] * 8 + prow;                                          // LDS row of the slice
-        const int grow = row / (TC * 16) * (TC * 16) + epi_cout_of_row(row % (TC * 16));  // the cout it holds (conv_common.h)
-        w_off[i] = c0 + grow < p.Cout ? (unsigned)(grow * p.Kpad * 2) + (unsigned)((slot ^ ((row >> 1) & 7)) << 4) : OOB;
-    }
+    n16_ring_assign<BN, NW, TC, PP>(p, wave, lane, c0, w_piece, w_off);
     const char *wpanel = reinterpret_cast<const char *>(p.w_hi) + (size_t)c0 * p.Kpad * 2;
-    // weight slice (cc, tap) into ring slot `ring` (zeros into the sink past the end of the K loop)
-    auto issue_w = [&](int cc, int tap, int ring) {
-        const bool real = cc < cin_steps;
-        const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<char *>(wpanel) + ((size_t)tap * p.Cin + (size_t)cc * 64) * 2, 0, (int)OOB, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < WQ; ++i) {
-            unsigned char *dst = real ? smem + WOFF + ring * WSLICE + w_piece[i] * 1024 : smem + SINK;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (n_lds_ptr_t)dst, 16, (int)(real ? w_off[i] : OOB), 0, 0, 0);
-        }
-    };
+    auto issue_w = [&](int cc, int tap, int ring) { n16_ring_issue<WSLICE>(p, wpanel, smem + WOFF, smem + SINK, w_piece, w_off, cc, tap, ring); };
     issue_w(0, 0, 0);
     issue_w(0, 1, 1);
 
@@ -138,95 +119,18 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_patch_kernel(ConvArg
     for (int kw = 0; kw < 3; ++kw) bcol[kw] = (wp * WW + kw + l15) * 128 + ((kg ^ patch_f(kw + l15)) << 4);
 
     // ---- prologue: the weight slices of steps 0 and 1 and the whole window of chunk 0 are in flight (issued above) ----
-    if constexpr (PP) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // slices 0 / 1 and the window
-        __builtin_amdgcn_s_barrier();
-        if (wc == 1) __builtin_amdgcn_s_barrier();                  // group 1 runs one phase behind group 0
-    }
+    pp_enter<PP, 0>(wc);
 
-    // One step = one filter tap of one 64-channel chunk.  DMA issued per wave and step: WQ weight pieces (slice of step
-    // s + 2) and, with two window buffers, one window piece of the next chunk during taps 0 .. XPW-1: CNT(tap) pieces.
-    // At the top of step s every piece issued before step s-1 must have landed (slice s was issued in step s-2, the
-    // window of this chunk during the previous chunk / the prologue): vmcnt(CNT(previous tap)).
     for (int cc = 0; cc < cin_steps; ++cc) {
         const int xcur = XBUFS == 2 ? (cc & 1) * XBYTES : 0;
         static_for<9>([&](auto T) {
             constexpr int tap = decltype(T)::v, kh = tap / 3, kw = tap % 3;
-            constexpr bool XWIN2 = XBUFS == 2;
-            if constexpr (!PP) {
-                constexpr int ptap = (tap + 8) % 9;                                  // the previous step's tap
-                constexpr int pcnt = WQ + ((XBUFS == 2 && ptap < XPW) ? 1 : 0);      // pieces the previous step issued
-                // (lgkmcnt(0): this wave's fragment reads of the previous step have returned before anyone's DMA may
-                // overwrite the slot / window they came from)
-                if (cc == 0 && tap == 0) {
-                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");            // prologue: the slices and the window
-                } else {
-                    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(pcnt) : "memory");
-                }
-                __builtin_amdgcn_s_barrier();
-            }
-            constexpr int ntap = (tap + 2) % 9, nring = (tap + 2) % 3;
-            const int ncc = cc + (tap + 2 >= 9 ? 1 : 0);
+            n16_step_top<tap, WQ, XPW, XBUFS == 2, PP, 0>(cc);
             const unsigned char *Wr = smem + (tap % 3) * WSLICE;
             const unsigned char *Xb = smem + xcur + kh * (WW * 128);
             auto lda = [&](int a, int kk) { return *reinterpret_cast<const n_u32x4 *>(Wr + ((arow + a * 16 * 128) ^ (kk << 6))); };
             auto ldb = [&](int b, int kk) { return *reinterpret_cast<const n_u32x4 *>(Xb + ((bcol[kw] + b * WP * WW * 128) ^ (kk << 6))); };
-            if constexpr (PP) {
-                // ---- READ phase: every fragment of the step, then the step's DMA (slice of step + 2, a window piece) ----
-                n_u32x4 af[2][TC], bf[NGRP];
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                    for (int a = 0; a < TC; ++a) af[kk][a] = lda(a, kk);
-#pragma unroll
-                for (int g = 0; g < NGRP; ++g) bf[g] = ldb(g % TP, g / TP);
-                issue_w(ncc, ntap, nring);
-                if constexpr (XWIN2 && tap < XPW) issue_x(tap, cc + 1);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                // ---- MFMA phase ----
-#pragma unroll
-                for (int g = 0; g < NGRP; ++g)
-#pragma unroll
-                    for (int a = 0; a < TC; ++a) acc[a][g % TP] = mfma_n16<F16>(af[g / TP][a], bf[g], acc[a][g % TP]);
-                // everything this wave issued before this step's READ phase has landed (slice of step + 1, older window pieces)
-                constexpr int cnt = WQ + ((XWIN2 && tap < XPW) ? 1 : 0);
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(cnt) : "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-            } else {
-            n_u32x4 af[2][TC], bf[NGRP];
-#pragma unroll
-            for (int a = 0; a < TC; ++a) af[0][a] = lda(a, 0);
-            bf[0] = ldb(0, 0);
-            bf[1] = ldb(1 % TP, 1 / TP);
-            static_for<NGRP>([&](auto G) {
-                constexpr int g = decltype(G)::v, kk = g / TP, b = g % TP;
-                if constexpr (g + 2 < NGRP) bf[g + 2] = ldb((g + 2) % TP, (g + 2) / TP);
-                if constexpr (g == 0) {
-#pragma unroll
-                    for (int a = 0; a < TC; ++a) af[1][a] = lda(a, 1);
-                }
-                if constexpr (g == 0) issue_w(ncc, ntap, nring);
-                if constexpr (g == 2 % NGRP && XBUFS == 2 && tap < XPW) issue_x(tap, cc + 1);
-#pragma unroll
-                for (int a = 0; a < TC; ++a) acc[a][b] = mfma_n16<F16>(af[kk][a], bf[g], acc[a][b]);
-            });
-            // issue order: TC MFMAs of group g, then the reads for group g+2 and the group's DMA pieces (see conv_n16.hip)
-            __builtin_amdgcn_sched_group_barrier(0x100, TC + 2, 0);
-            static_for<NGRP>([&](auto G) {
-                constexpr int g = decltype(G)::v;
-                __builtin_amdgcn_sched_group_barrier(0x008, TC, 0);
-                constexpr int nread = (g + 2 < NGRP ? 1 : 0) + (g == 0 ? TC : 0);
-                if constexpr (nread > 0) __builtin_amdgcn_sched_group_barrier(0x100, nread, 0);
-                constexpr int npiece = (g == 0 ? WQ : 0) + ((g == 2 % NGRP && XBUFS == 2 && tap < XPW) ? 1 : 0);
-                if constexpr (npiece > 0) __builtin_amdgcn_sched_group_barrier(0x010, npiece, 0);
-            });
-            }
+            n16_step<tap, TC, TP, WQ, XPW, XBUFS == 2, PP, F16>(acc, cc, lda, ldb, issue_w, issue_x);
         });
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the sink pieces of the last steps (zero fills: they return at once)
@@ -252,15 +156,11 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_patch_kernel(ConvArg
             constexpr int MODE = decltype(MODE_)::v;
             if constexpr (MODE != EPI_GENERIC) epi_direct_stores<MODE, NARROW, TC, TP>(p, acc, c0 + wc * TC * 16, kg, epx, s1, s2);
         });
-        if constexpr (PP) {
-            if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
-        }
+        pp_leave<PP>(wc);
         if (p.stats) epi_direct_stats<TC, WP, BN>(p, s1, s2, reinterpret_cast<float *>(smem_n16p), wp, wc, kg, l15, tid, c0, (size_t)patch);
         return;
     }
-    if constexpr (PP) {
-        if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
-    }
+    pp_leave<PP>(wc);
 
     // ---- staged epilogue (every other launch; conv_common.h), one patch row per iteration ----
     static_assert(PWD == 16 && 256 * BN * 4 <= SINK, "patch rows of 16 pixels; one pass");
@@ -295,14 +195,11 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_win_kernel(ConvArgs 
     constexpr int NW = WP * WC, NT = NW * 64, BM = 256;
     constexpr int NPMAX = 54;                                       // 8-row window pieces per buffer the LDS can hold twice (W <= 86)
     constexpr int XPW = (NPMAX + NW - 1) / NW;
-    constexpr int WSLICE = BN * 128, RING = 3;
-    static_assert(BN % (8 * NW) == 0, "weight-slice pieces are dealt round-robin to the waves");
-    constexpr int WQ = BN / (8 * NW);
     constexpr int TP = BM / (16 * WP), TC = BN / (16 * WC);
+    constexpr int WSLICE = BN * 128, RING = 3, WQ = BN / (8 * NW);     // weight slice bytes, ring slots, pieces per wave and step
     static_assert((XBUFS == 1 || XPW <= 9) && TP >= 2 && (XBUFS == 2 || !PP) && TC % 2 == 0, "geometry");
     static_assert(!PP || (WP == 4 && WC == 2 && (BN / 16) % 4 == 0), "ping-pong: waves w and w + 4 share a SIMD and split the couts");
     constexpr unsigned OOB = 0x80000000u;
-    constexpr int NGRP = 2 * TP;
     extern __shared__ __attribute__((aligned(16))) uint16_t smem_n16p[];
     unsigned char *smem = reinterpret_cast<unsigned char *>(smem_n16p);
     const int XBYTES = NP * 1024, WOFF = XBUFS * XBYTES, SINK = WOFF + RING * WSLICE;
@@ -313,12 +210,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_win_kernel(ConvArgs 
     const int wp = wave % WP, wc = wave / WP;
     const int kg = lane >> 4, l15 = lane & 15;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
     const int tile_m = (int)fdiv((unsigned)bid, geo.tiles_n), tile_n = bid - tile_m * p.tiles_n;
     const int m0 = tile_m * BM, c0 = tile_n * BN;
     const int cin_steps = p.cin_steps;
@@ -340,14 +232,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_win_kernel(ConvArgs 
     }
     unsigned w_off[WQ];
     int w_piece[WQ];
-#pragma unroll
-    for (int i = 0; i < WQ; ++i) {
-        // PP: the group's own cout half (BN / 16 pieces of 8 rows) dealt to its four waves; else all pieces over all waves
-        w_piece[i] = PP ? (wave >> 2) * (BN / 16) + (wave & 3) + 4 * i : wave + NW * i;
-        const int row = w_piece[i] * 8 + prow;                                          // LDS row of the slice
-        const int grow = row / (TC * 16) * (TC * 16) + epi_cout_of_row(row % (TC * 16));  // the cout it holds (conv_common.h)
-        w_off[i] = c0 + grow < p.Cout ? (unsigned)(((size_t)grow * p.Kpad + ((slot ^ ((row >> 1) & 7)) << 3)) * 2) : OOB;
-    }
+    n16_ring_assign<BN, NW, TC, PP>(p, wave, lane, c0, w_piece, w_off);
     // base of the window's first pixel; lanes whose pixel lies outside the tensor carry the out-of-range offset instead
     const char *xwin = reinterpret_cast<const char *>(p.x_hi) + (long long)wstart * p.x_ld * 2;
     const char *wpanel = reinterpret_cast<const char *>(p.w_hi) + (size_t)c0 * p.Kpad * 2;
@@ -358,16 +243,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_win_kernel(ConvArgs 
         unsigned char *dst = real ? smem + (XBUFS == 2 ? (cc & 1) * XBYTES : 0) + (wave + NW * i) * 1024 : smem + SINK;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (n_lds_ptr_t)dst, 16, (int)(real ? x_off[i] : OOB), 0, 0, 0);
     };
-    auto issue_w = [&](int cc, int tap, int ring) {
-        const bool real = cc < cin_steps;
-        const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<char *>(wpanel) + ((size_t)tap * p.Cin + (size_t)cc * 64) * 2, 0, (int)OOB, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < WQ; ++i) {
-            unsigned char *dst = real ? smem + WOFF + ring * WSLICE + w_piece[i] * 1024 : smem + SINK;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (n_lds_ptr_t)dst, 16, (int)(real ? w_off[i] : OOB), 0, 0, 0);
-        }
-    };
+    auto issue_w = [&](int cc, int tap, int ring) { n16_ring_issue<WSLICE>(p, wpanel, smem + WOFF, smem + SINK, w_piece, w_off, cc, tap, ring); };
 
     n_f32x4 acc[TC][TP];
 #pragma unroll
@@ -402,29 +278,13 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_win_kernel(ConvArgs 
     for (int i = 0; i < XPW; ++i) issue_x(i, 0);
     issue_w(0, 0, 0);
     issue_w(0, 1, 1);
-    if constexpr (PP) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WQ) : "memory");   // the window and slice 0 (slice 1 may still be in flight)
-        __builtin_amdgcn_s_barrier();
-        if (wc == 1) __builtin_amdgcn_s_barrier();                  // group 1 runs one phase behind group 0
-    }
+    pp_enter<PP, WQ>(wc);
 
     for (int cc = 0; cc < cin_steps; ++cc) {
         const int xcur = XBUFS == 2 ? (cc & 1) * XBYTES : 0;
         static_for<9>([&](auto T) {
             constexpr int tap = decltype(T)::v, kh = tap / 3, kw = tap % 3;
-            constexpr bool XWIN2 = XBUFS == 2;
-            if constexpr (!PP) {
-                constexpr int ptap = (tap + 8) % 9;
-                constexpr int pcnt = WQ + ((XWIN2 && ptap < XPW) ? 1 : 0);
-                if (cc == 0 && tap == 0) {
-                    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WQ) : "memory");
-                } else {
-                    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(pcnt) : "memory");
-                }
-                __builtin_amdgcn_s_barrier();
-            }
-            constexpr int ntap = (tap + 2) % 9, nring = (tap + 2) % 3;
-            const int ncc = cc + (tap + 2 >= 9 ? 1 : 0);
+            n16_step_top<tap, WQ, XPW, XBUFS == 2, PP, WQ>(cc);
             const unsigned char *Wr = smem + WOFF + (tap % 3) * WSLICE;
             const unsigned char *Xb = smem + xcur;
             const int toff = kh * p.W + kw;
@@ -436,61 +296,7 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_win_kernel(ConvArgs 
             }
             auto lda = [&](int a, int kk) { return *reinterpret_cast<const n_u32x4 *>(Wr + ((arow + a * 16 * 128) ^ (kk << 6))); };
             auto ldb = [&](int b, int kk) { return *reinterpret_cast<const n_u32x4 *>(Xb + (baddr[b] ^ (kk << 6))); };
-            if constexpr (PP) {
-                // ---- READ phase: every fragment of the step, then the step's DMA (slice of step + 2, a window piece) ----
-                n_u32x4 af[2][TC], bf[NGRP];
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-                    for (int a = 0; a < TC; ++a) af[kk][a] = lda(a, kk);
-#pragma unroll
-                for (int g = 0; g < NGRP; ++g) bf[g] = ldb(g % TP, g / TP);
-                issue_w(ncc, ntap, nring);
-                if constexpr (XWIN2 && tap < XPW) issue_x(tap, cc + 1);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-                // ---- MFMA phase ----
-#pragma unroll
-                for (int g = 0; g < NGRP; ++g)
-#pragma unroll
-                    for (int a = 0; a < TC; ++a) acc[a][g % TP] = mfma_n16<F16>(af[g / TP][a], bf[g], acc[a][g % TP]);
-                // everything this wave issued before this step's READ phase has landed (slice of step + 1, older window pieces)
-                constexpr int cnt = WQ + ((XWIN2 && tap < XPW) ? 1 : 0);
-                __builtin_amdgcn_sched_barrier(0);
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(cnt) : "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-            } else {
-            n_u32x4 af[2][TC], bf[NGRP];
-#pragma unroll
-            for (int a = 0; a < TC; ++a) af[0][a] = lda(a, 0);
-            bf[0] = ldb(0, 0);
-            bf[1] = ldb(1 % TP, 1 / TP);
-            static_for<NGRP>([&](auto G) {
-                constexpr int g = decltype(G)::v, kk = g / TP, b = g % TP;
-                if constexpr (g + 2 < NGRP) bf[g + 2] = ldb((g + 2) % TP, (g + 2) / TP);
-                if constexpr (g == 0) {
-#pragma unroll
-                    for (int a = 0; a < TC; ++a) af[1][a] = lda(a, 1);
-                }
-                if constexpr (g == 0) issue_w(ncc, ntap, nring);
-                if constexpr (g == 2 % NGRP && XWIN2 && tap < XPW) issue_x(tap, cc + 1);
-#pragma unroll
-                for (int a = 0; a < TC; ++a) acc[a][b] = mfma_n16<F16>(af[kk][a], bf[g], acc[a][b]);
-            });
-            __builtin_amdgcn_sched_group_barrier(0x100, TC + 2, 0);
-            static_for<NGRP>([&](auto G) {
-                constexpr int g = decltype(G)::v;
-                __builtin_amdgcn_sched_group_barrier(0x008, TC, 0);
-                constexpr int nread = (g + 2 < NGRP ? 1 : 0) + (g == 0 ? TC : 0);
-                if constexpr (nread > 0) __builtin_amdgcn_sched_group_barrier(0x100, nread, 0);
-                constexpr int npiece = (g == 0 ? WQ : 0) + ((g == 2 % NGRP && XWIN2 && tap < XPW) ? 1 : 0);
-                if constexpr (npiece > 0) __builtin_amdgcn_sched_group_barrier(0x010, npiece, 0);
-            });
-            }
+            n16_step<tap, TC, TP, WQ, XPW, XBUFS == 2, PP, F16>(acc, cc, lda, ldb, issue_w, issue_x);
         });
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -519,15 +325,11 @@ __global__ __launch_bounds__(WP * WC * 64, 2) void conv_n16_win_kernel(ConvArgs 
             constexpr int MODE = decltype(MODE_)::v;
             if constexpr (MODE != EPI_GENERIC) epi_direct_stores<MODE, NARROW, TC, TP>(p, acc, c0 + wc * TC * 16, kg, epx, s1, s2);
         });
-        if constexpr (PP) {
-            if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
-        }
+        pp_leave<PP>(wc);
         if (p.stats) epi_direct_stats<TC, WP, BN>(p, s1, s2, reinterpret_cast<float *>(smem_n16p), wp, wc, kg, l15, tid, c0, (size_t)tile_m);
         return;
     }
-    if constexpr (PP) {
-        if (wc == 0) __builtin_amdgcn_s_barrier();   // pairs with group 1's last phase boundary
-    }
+    pp_leave<PP>(wc);
 
     // ---- staged epilogue (every other launch; conv_common.h) over consecutive output pixels ----
     float *Ct = reinterpret_cast<float *>(smem_n16p);   // the launcher sizes the LDS for 256 * BN floats at least
@@ -554,17 +356,8 @@ static int launch_win(const ConvArgs &a, hipStream_t st) {
     if (lds < (size_t)256 * BN * 4) lds = (size_t)256 * BN * 4;   // the epilogue's accumulator tile
     const dim3 grid(a.tiles_m * a.tiles_n, 1, 1), block(WP * WC * 64);
     const WinGeo geo{make_fastdiv((unsigned)a.tiles_n), make_fastdiv((unsigned)(a.H * a.W)), make_fastdiv((unsigned)a.W)};
-    if (a.narrow == CER_STORE_F16) {
-        auto k = conv_n16_win_kernel<BN, WP, WC, true, PP, XBUFS>;
-        if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CER_LAUNCH(k, grid, block, lds, st, a, np, geo);
-    } else {
-        auto k = conv_n16_win_kernel<BN, WP, WC, false, PP, XBUFS>;
-        if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CER_LAUNCH(k, grid, block, lds, st, a, np, geo);
-    }
-    CER_HIP_CHECK(hipGetLastError());
-    return CER_OK;
+    return a.narrow == CER_STORE_F16 ? launch_lds(conv_n16_win_kernel<BN, WP, WC, true, PP, XBUFS>, grid, block, lds, st, a, np, geo)
+                                     : launch_lds(conv_n16_win_kernel<BN, WP, WC, false, PP, XBUFS>, grid, block, lds, st, a, np, geo);
 }
 
 bool conv_n16_win_ok(const ConvArgs &a) {
@@ -580,17 +373,8 @@ static int launch_patch(const ConvArgs &a, hipStream_t st) {
     const size_t lds = (size_t)XBUFS * XPIECES * 1024 + 3 * (size_t)BN * 128 + 1024;
     const dim3 grid(a.tiles_m * a.tiles_n, 1, 1), block(WP * WC * 64);
     const PatchGeo geo{make_fastdiv((unsigned)a.tiles_n), make_fastdiv((unsigned)(a.W / 16)), make_fastdiv((unsigned)(a.H / 16))};
-    if (a.narrow == CER_STORE_F16) {
-        auto k = conv_n16_patch_kernel<BN, WP, WC, XBUFS, true, PP>;
-        if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CER_LAUNCH(k, grid, block, lds, st, a, geo);
-    } else {
-        auto k = conv_n16_patch_kernel<BN, WP, WC, XBUFS, false, PP>;
-        if (lds > 64 * 1024) CER_HIP_CHECK(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CER_LAUNCH(k, grid, block, lds, st, a, geo);
-    }
-    CER_HIP_CHECK(hipGetLastError());
-    return CER_OK;
+    return a.narrow == CER_STORE_F16 ? launch_lds(conv_n16_patch_kernel<BN, WP, WC, XBUFS, true, PP>, grid, block, lds, st, a, geo)
+                                     : launch_lds(conv_n16_patch_kernel<BN, WP, WC, XBUFS, false, PP>, grid, block, lds, st, a, geo);
 }
 
 // tile ids: 71 = 16x16 patch x 64 couts, 4 waves, ONE window buffer (Cin == 64 only; 74 KiB of LDS -> two blocks per CU, so

@@ -31,12 +31,7 @@ __global__ __launch_bounds__(512, 2) void conv_n16_s2d_kernel(ConvArgs p, int NP
     const int wp = wave % WP, wc = wave / WP;
     const int kg = lane >> 4, l15 = lane & 15;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    int bid = blockIdx.x;
-    {   // XCD-aware remap (bijective)
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int bid = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
     const int tile_n = bid % p.tiles_n, tile_m = bid / p.tiles_n;
     const int m0 = tile_m * BM, c0 = tile_n * BN;
     const int cpp = p.cin_steps;                                  // 64-channel chunks per phase

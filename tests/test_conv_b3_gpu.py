@@ -215,6 +215,38 @@ def test_specialised_row_epilogues_on_every_kernel_family(kind, tile, hw):
     assert ((got - ref).abs() <= tol).all(), ((got - ref).abs() / tol).max().item()
 
 
+@pytest.mark.parametrize("cin", [32, 64])
+@pytest.mark.parametrize("kind", ["b9_prelu_direct", "plain_staged"])
+def test_patch_and_window_kernels_give_bit_equal_outputs(kind, cin):
+    """The 16x16-patch kernels (59, 58) and the 1-D window kernels (53, 56) run ONE step (csrc/conv_b3.h: b3_step), so per
+    accumulator the MFMA order is the same -- chunk, tap, lo*hi, hi*lo, hi*hi --, both read a zero-filled halo, and the bias9
+    border case is the same value whether it comes from coordinates or from the tap mask: the outputs are equal bit for bit.
+    Two patches per image, 256-pixel window tiles that end inside an image.  Cout = 64 with the encoder's PReLU + bias9
+    launch takes the direct epilogue, Cout = 60 (Cout & 7 != 0) with both outputs the staged one.  (The statistics rows are
+    per patch in one family and per tile in the other, so their sums associate differently: not compared.)"""
+    from feature_vs_text_compound_emotion_amd import ops
+    n, h, w = 2, 16, 32
+    tiles = (59, 58, 53, 56)
+    cout = 64 if kind == "b9_prelu_direct" else 60
+    g = torch.Generator().manual_seed(cin + cout + len(kind))
+    xs = ops.split_bf16(torch.randn(n, h, w, cin, generator=g).cuda())
+    wt = torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5
+    if kind == "b9_prelu_direct":
+        s1, t1 = torch.rand(cin, generator=g) + 0.5, torch.randn(cin, generator=g) * 0.5
+        alpha = torch.rand(cout, generator=g) * 0.3 + 0.1
+        ws, b9 = ops.fold_bn_3x3_packed(ops.pack_conv_weight(wt.cuda()), s1.cuda(), t1.cuda(), "split")
+        keys, kw = ("split",), dict(alpha=alpha.cuda(), act1=ops.ACT_PRELU, bias9=b9)
+    else:
+        ws, keys, kw = ops.split_bf16(ops.pack_conv_weight(wt.cuda())), ("split", "y"), dict(out_f32=True, out_split=True)
+    outs = {tile: ops.conv2d_b3(xs, ws, 3, 3, pad=(1, 1), tile=tile, **kw) for tile in tiles}
+    for tile in tiles[1:]:
+        for key in keys:
+            a, b = outs[tiles[0]][key], outs[tile][key]
+            planes = ((a.hi, b.hi), (a.lo, b.lo)) if key == "split" else ((a, b),)
+            for pa, pb in planes:
+                assert torch.equal(pa, pb), (tiles[0], tile, key, (pa.float() - pb.float()).abs().max().item())
+
+
 # ---- space-to-depth hand-over of the stride-2 units: producer layout, then the window-resident stride-2 kernel ----
 @pytest.mark.parametrize("n,cin,cout,h,w,tile", [(2, 64, 64, 32, 48, 59), (1, 64, 128, 16, 32, 58), (3, 64, 128, 20, 12, 56),
                                                  (5, 128, 40, 10, 6, 53), (12, 64, 64, 40, 40, 0)])

@@ -339,6 +339,36 @@ def test_persistent_patch_kernel_equals_the_one_patch_per_block_kernel(kind, n, 
         ops.conv2d_n16(x, wd, 3, 3, pad=(1, 1), tile=79, out_f32=True, out_n16=True)
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cin,tiles", [(64, (71, 72, 78, 73, 76, 77)), (128, (72, 78, 73, 76))])
+@pytest.mark.parametrize("kind", ["b9_prelu_direct", "plain_staged"])
+def test_patch_and_window_kernels_give_bit_equal_outputs(kind, cin, tiles, dtype):
+    """The 16x16-patch kernels (71, 72, 78) and the 1-D window kernels (73, 76, 77) run ONE step (csrc/conv_n16.h: n16_step),
+    so per accumulator the MFMA order is the same -- chunk, tap, the two 32-deep halves --, both read a zero-filled halo, and
+    the bias9 border case is the same value whether it comes from coordinates or from the tap mask: the outputs are equal bit
+    for bit.  Two patches per image, 256-pixel window tiles that end inside an image.  Cout = 64 with the encoder's PReLU +
+    bias9 launch takes the direct epilogue, Cout = 60 (Cout & 7 != 0) with both outputs the staged one.  (The statistics rows
+    are per patch in one family and per tile in the other, so their sums associate differently: not compared.)"""
+    from feature_vs_text_compound_emotion_amd import ops
+    n, h, w = 2, 16, 32
+    cout = 64 if kind == "b9_prelu_direct" else 60
+    g = torch.Generator().manual_seed(cin + cout + len(kind))
+    x = torch.randn(n, h, w, cin, generator=g).to(dtype).cuda()
+    wt = (torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5).to(dtype)
+    if kind == "b9_prelu_direct":
+        s1, t1 = torch.rand(cin, generator=g) + 0.5, torch.randn(cin, generator=g) * 0.5
+        alpha = torch.rand(cout, generator=g) * 0.3 + 0.1
+        wp, b9 = ops.fold_input_bn_3x3(wt.float().cuda(), s1.cuda(), t1.cuda())
+        wn, keys, kw = ops.to_n16(wp, dtype), ("n16",), dict(alpha=alpha.cuda(), act1=ops.ACT_PRELU, bias9=b9)
+    else:
+        wn, keys, kw = ops.to_n16(ops.pack_conv_weight(wt.float().cuda()), dtype), ("n16", "y"), dict(out_f32=True, out_n16=True)
+    outs = {tile: ops.conv2d_n16(x, wn, 3, 3, pad=(1, 1), tile=tile, **kw) for tile in tiles}
+    for tile in tiles[1:]:
+        for key in keys:
+            a, b = outs[tiles[0]][key], outs[tile][key]
+            assert torch.equal(a, b), (tiles[0], tile, key, (a.float() - b.float()).abs().max().item())
+
+
 # ---- space-to-depth hand-over of the stride-2 units (narrow twins of the bf16x3 tests) ----
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("n,cin,cout,h,w,tile", [(2, 64, 64, 32, 48, 71), (1, 128, 128, 16, 32, 72), (1, 128, 128, 16, 32, 78),
