@@ -23,6 +23,7 @@ struct WgradArgs {
     // (n, ho*stride - pad_t + kh, wo*stride - pad_l + kw) of the NHWC input, zero outside the image
     int H, W, Ho, Wo, KW, stride, pad_t, pad_l;
     int rows_per_split;  // multiple of WG_ROWS; blockIdx.z = tap + k * split, partial results in slabs of Cout * Cin * k floats
+    int dz_vec, x_vec;   // the operand's rows start on 16-byte boundaries (pitch % 4 == 0 and an aligned base): float4 loads
 };
 
 constexpr int WG_ROWS = 32;  // reduction rows per step
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(256) void conv1d_wgrad_kernel(WgradArgs p) {
             if (r < r_end) {
                 const int co = co0 + scol, ci = ci0 + scol;
                 const float *ap = p.dz + (size_t)r * p.dz_ld + co;
-                if (co + 3 < p.Cout && ((p.dz_ld & 3) == 0)) {
+                if (co + 3 < p.Cout && p.dz_vec) {
                     a = *reinterpret_cast<const float4 *>(ap);
                 } else {
                     if (co < p.Cout) a.x = ap[0];
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void conv1d_wgrad_kernel(WgradArgs p) {
                 }
                 if (src >= 0) {
                     const float *bp = p.x + (size_t)src * p.x_ld + ci;
-                    if (ci + 3 < p.Cin && ((p.x_ld & 3) == 0)) {
+                    if (ci + 3 < p.Cin && p.x_vec) {
                         b = *reinterpret_cast<const float4 *>(bp);
                     } else {
                         if (ci < p.Cin) b.x = bp[0];
@@ -150,6 +151,9 @@ static int wgrad_launch(WgradArgs a, float *dw, void *workspace, size_t workspac
     dim3 grid((a.Cout + WG_T - 1) / WG_T, (a.Cin + WG_T - 1) / WG_T, a.k);
     const size_t n = (size_t)a.Cout * a.Cin * a.k;
     int splits = wgrad_splits(a.R, (long long)grid.x * grid.y * grid.z);
+    // a column slice at an odd offset has a pitch that is a multiple of 4 and rows that are not 16-byte aligned: scalar loads
+    a.dz_vec = (a.dz_ld & 3) == 0 && ((uintptr_t)a.dz & 15) == 0;
+    a.x_vec = (a.x_ld & 3) == 0 && ((uintptr_t)a.x & 15) == 0;
     if (splits > 1 && (!workspace || workspace_bytes < (size_t)splits * n * sizeof(float))) splits = 1;   // no workspace: one pass
     a.rows_per_split = ((a.R + splits - 1) / splits + WG_ROWS - 1) / WG_ROWS * WG_ROWS;
     a.dw = splits > 1 ? (float *)workspace : dw;

@@ -952,7 +952,8 @@ def weight_norm_bwd(dw, v, g, norm):
 
 
 def conv1d_wgrad(dz, x, seq_len, k, dil):
-    """dW [Cout,Cin,k] from dz [R,Cout] and the layer input x [R,Cin] (both may be column slices)."""
+    """dW [Cout,Cin,k] from dz [R,Cout] and the layer input x [R,Cin] (both may be column slices, at any offset and pitch:
+    an operand whose rows do not start on 16-byte boundaries is read with scalar loads)."""
     r, cout, dz_ld = _rows(dz, "dz")
     r2, cin, x_ld = _rows(x, "x")
     if r != r2:

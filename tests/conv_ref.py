@@ -2,6 +2,7 @@
 
 Nothing here needs a GPU: ``tests/test_conv_ref_cpu.py`` checks the reference and every table on any machine,
 ``tests/test_conv_fp32_edges_gpu.py`` runs the tables on ``csrc/conv_igemm.hip`` and the epilogue of ``csrc/conv_common.h``.
+The second half of the file is the same for the backward convs (weight and data gradients; ``tests/test_conv_backward_edges_gpu.py``).
 
 The contract is the docstring of ``ops.conv2d``:
 
@@ -430,3 +431,292 @@ def erf_error(pre64, device="cpu"):
     """The error of ``torch.erf`` in fp32 on ``device`` against float64 over the arguments GELU hands it."""
     arg = (pre64 * 0.70710678118654752440).float()
     return (torch.erf(arg.to(device)).cpu().double() - torch.erf(arg.double())).abs().max().item()
+
+
+# ====================================================================================================================
+# The backward convs: the weight gradient (csrc/wgrad.hip, csrc/wgrad_b3.hip) and ``visual_backbone._conv_dgrad``.
+#
+#   dW[co][ci][kh][kw] = sum over output pixels r = (n, ho, wo) of dZ[r][co] X[n, ho s - pad_t + kh dil_h, wo s - pad_l + kw dil_w][ci]
+#
+# Three operand classes, all values multiples of 2^-8 and deterministic in the case name:
+#
+#   ints   dz and x integers in [-4, 4]
+#   x_lo   dz in {-1, 0, 1}, x = m / 256 with |m| <= 2047: twelve significant bits, so bf16(x) drops up to four and the ``lo``
+#          plane of x is nonzero for about two thirds of the values, while dz has lo == 0
+#   z_lo   the mirror image: dz twelve bits, x ternary
+#
+# In every class one operand of each product has lo == 0, so dz x = dz_hi x_hi + dz_hi x_lo (or + dz_lo x_hi) holds exactly and the
+# lo lo product the bf16x3 kernels drop is zero; hi and lo themselves are multiples of 2^-8 with |hi| + |lo| <= 2 |value|.  Every
+# product and every partial sum, in any order and over any subset of rows, taps, splits and planes, is therefore a multiple of 2^-8
+# of magnitude at most 2 mag (mag = sum |dz| |x|, the magnitude twin), and with 2^9 max(mag) < 2^24 (``wgrad_exact_margin``: a
+# condition, asserted on the CPU for every case) all of them are float32 numbers and every addition is exact.  The bf16x3 kernels
+# then owe the float64 gradient BIT FOR BIT like the fp32-MFMA kernel, whatever their tile, split or summation order, and a dropped,
+# doubled or misrouted row, tap, split, plane or tile shows as a nonzero difference.  The same holds for the data gradient with
+# (dy, w) in the place of (dz, x).
+OPERAND_CLASSES = ("ints", "x_lo", "z_lo")
+WGRAD_LIMIT = 2.0 ** 24
+
+
+def _lo12(g, shape):
+    return torch.randint(-2047, 2048, shape, generator=g).float() / 256.0
+
+
+def _ternary(g, shape):
+    return torch.randint(-1, 2, shape, generator=g).float()
+
+
+def _pair(g, cls, shape_z, shape_x):
+    """(z, x) of an operand class; z is drawn first."""
+    if cls == "ints":
+        return _ints(g, shape_z, 4), _ints(g, shape_x, 4)
+    if cls == "x_lo":
+        return _ternary(g, shape_z), _lo12(g, shape_x)
+    if cls == "z_lo":
+        return _lo12(g, shape_z), _ternary(g, shape_x)
+    if cls == "normal":
+        return torch.randn(shape_z, generator=g), torch.randn(shape_x, generator=g)
+    raise ValueError(cls)
+
+
+def wgrad_make(case, cls="ints"):
+    """(d, dz) of a weight-gradient case: d["x"] [N, H, W, Cin] and the output gradient dz [N, Ho, Wo, Cout], float32 on the CPU."""
+    g = torch.Generator().manual_seed(_seed(case) + 7 * (1 + (OPERAND_CLASSES + ("normal",)).index(cls)))
+    ho, wo = out_hw_of(case)
+    dz, x = _pair(g, cls, (case.n, ho, wo, case.cout), (case.n, case.h, case.w, case.cin))
+    return {"x": x}, dz
+
+
+def wgrad_reference(case, d, dz):
+    """float64 autograd gradient of the conv with respect to its WEIGHT for the output gradient dz, [Cout, Cin, KH, KW], and the
+    magnitude twin sum |dz| |x|."""
+    out = []
+    for f in (lambda t: t.double(), lambda t: t.double().abs()):
+        w = torch.zeros(case.cout, case.cin, case.kh, case.kw, dtype=torch.float64, requires_grad=True)
+        raw = _contract(f(d["x"]).permute(0, 3, 1, 2), w, case.stride, case.dil, case.pad[0], case.pad[1], case.out_hw)
+        out.append(torch.autograd.grad(raw, w, f(dz))[0])
+    return out
+
+
+def wgrad_exact_margin(case, d, dz):
+    """2^9 max(mag): 2^8 for the unit 2^-8 of the operand classes, 2 for |hi| + |lo| >= |value|.  Must stay below 2^24."""
+    return 2.0 ** 9 * wgrad_reference(case, d, dz)[1].max().item()
+
+
+def wgrad_loops(case, d, dz):
+    """The weight gradient as the kernels gather it, written out one product at a time (tiny shapes)."""
+    x, z = d["x"].double(), dz.double()
+    ho, wo = out_hw_of(case)
+    dw = torch.zeros(case.cout, case.cin, case.kh, case.kw, dtype=torch.float64)
+    for b in range(case.n):
+        for i in range(ho):
+            for j in range(wo):
+                for r in range(case.kh):
+                    for q in range(case.kw):
+                        hi, wi = i * case.stride - case.pad[0] + r * case.dil[0], j * case.stride - case.pad[1] + q * case.dil[1]
+                        if 0 <= hi < case.h and 0 <= wi < case.w:
+                            dw[:, :, r, q] += torch.outer(z[b, i, j], x[b, hi, wi])
+    return dw
+
+
+def bf16_hi(t):
+    """The hi plane of ``ops.split_bf16``: the value rounded to bfloat16."""
+    return t.to(torch.bfloat16).float()
+
+
+WGRAD_MUTANTS = ("hw_swap", "pad_swap", "tap_div_kh", "drop_last_step", "drop_lo", "tile_neighbour")
+
+
+def wgrad_rows(case, d, dz, dtype=torch.float32, mutant=None):
+    """The weight gradient as a float32 CPU GEMM per filter tap over the pixel rows r = (n, ho, wo): a correct contraction that is
+    not the code under test (``mutant`` None), or one with a deliberate mistake of the kind a kernel could make:
+
+      hw_swap         Ho written for Wo in the decomposition of r      pad_swap        pad_t and pad_l exchanged
+      tap_div_kh      kh = tap // KH instead of tap // KW              drop_last_step  the last partial 32-row step left out
+      drop_lo         the lo plane of x left out (x rounded to bf16)   tile_neighbour  the dz columns past a 128-wide tile edge
+                                                                                       taken from the tile before
+    """
+    assert mutant is None or mutant in WGRAD_MUTANTS
+    ho, wo = out_hw_of(case)
+    rows = case.n * ho * wo
+    x = d["x"].reshape(-1, case.cin).to(dtype)
+    z = dz.reshape(rows, case.cout).to(dtype)
+    if mutant == "drop_lo":
+        x = bf16_hi(x).to(dtype)
+    if mutant == "tile_neighbour" and case.cout > 128:
+        z = torch.cat([z[:, :128], z[:, :case.cout - 128]], 1)
+    if mutant == "drop_last_step":
+        rows = rows // 32 * 32
+    pad_t, pad_l = case.pad[::-1] if mutant == "pad_swap" else case.pad
+    r = torch.arange(rows)
+    n, q = r // (ho * wo), r % (ho * wo)
+    i, j = (q // ho, q % ho) if mutant == "hw_swap" else (q // wo, q % wo)
+    dw = torch.zeros(case.cout, case.cin, case.kh, case.kw, dtype=dtype)
+    for tap in range(case.kh * case.kw):
+        a = tap // (case.kh if mutant == "tap_div_kh" else case.kw)
+        b = tap - a * case.kw
+        hi, wi = i * case.stride - pad_t + a * case.dil[0], j * case.stride - pad_l + b * case.dil[1]
+        ok = (hi >= 0) & (hi < case.h) & (wi >= 0) & (wi < case.w)
+        src = ((n * case.h + hi) * case.w + wi).clamp(0, x.shape[0] - 1)
+        xg = torch.where(ok[:, None], x[src], torch.zeros((), dtype=dtype))
+        dw[:, :, tap // case.kw, tap % case.kw] = z[:rows].t() @ xg
+    return dw
+
+
+def assert_exact(got, ref, what):
+    """THE comparison of the exact backward tests: ``got`` (any float dtype, any device) equals the float64 ``ref`` bit for bit."""
+    got = got.detach().double().cpu()
+    assert got.shape == ref.shape, f"{what}: shape {tuple(got.shape)}, expected {tuple(ref.shape)}"
+    if not torch.equal(got, ref):
+        bad = got != ref
+        first = tuple(int(v) for v in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {ref.numel()} values differ, first at {first}: "
+                             f"{got[first].item()!r} for {ref[first].item()!r}")
+
+
+# ---- weight gradient, 2-D.  The name carries the geometry and the path ``wgrad_b3_tile`` / the dispatch of ``wgrad_b3_run`` send
+# the channel set to: t64 = the 64-wide tile (<64, *>), t128 = <128, false> with fp32 operands and the NON-DMA <128, true> with Split
+# operands (a channel count that is no multiple of 8), t128dma = <128, true, DMA> with Split operands, wide = the 256 x 256 kernel
+# with Split operands (<128, false> with fp32 operands); f32only = a channel count that is no multiple of 4 (csrc/wgrad.hip only).
+# split_b3 / split_f32: the launch is expected to take the row-split path of wgrad_b3.hip / wgrad.hip (the GPU test asserts it
+# through the workspace the library asks for); R = N Ho Wo in the comment.
+WCase = namedtuple("WCase", "case split_b3 split_f32")
+
+
+def _w(name, n, h, w, cin, cout, kh, kw, split_b3, split_f32, **kw_):
+    return WCase(C(name, n, h, w, cin, cout, kh, kw, **kw_), split_b3, split_f32)
+
+
+WGRAD_2D = [
+    # H != W under 3x3; R = 1500 = 5 x 256 + 220: six splits, the last one partial and ending in a 28-row step
+    _w("rect10x25_3x3_4to64_t64stem", 6, 10, 25, 4, 64, 3, 3, True, True, pad=(1, 1)),
+    _w("rect10x25_3x3_3to64_f32only_cin3", 6, 10, 25, 3, 64, 3, 3, None, True, pad=(1, 1)),
+    _w("rect10x25_3x3_40to7_f32only_cout7", 6, 10, 25, 40, 7, 3, 3, None, True, pad=(1, 1)),
+    _w("rect10x25_3x3_1to64_f32only_cin1", 6, 10, 25, 1, 64, 3, 3, None, True, pad=(1, 1)),          # the first VGGish conv's channels
+    # KH != KW, pad_t != pad_l with a pad of 0; R = 1440: six splits of 256 rows, 160 in the last
+    _w("rect10x25_3x2_pad1x0_72to132_t128", 6, 10, 25, 72, 132, 3, 2, True, True, pad=(1, 0)),
+    _w("rect10x25_3x2_pad1x0_200to40_t64ragged", 6, 10, 25, 200, 40, 3, 2, True, True, pad=(1, 0)),
+    # 1x3 with a pad of 2 under three taps and no padding above; R = 392 = 12 x 32 + 8
+    _w("rect7x12_1x3_pad0x2_72to200_t128dma_partial", 4, 7, 12, 72, 200, 1, 3, False, True, pad=(0, 2)),
+    # 3x3 with pad (2, 0): the output is taller than the input; R = 288
+    _w("rect6x11_3x3_pad2x0_128to256_t128dma_full", 4, 6, 11, 128, 256, 3, 3, False, True, pad=(2, 0)),
+    # 3x1, stride 2, (H, W) = (9, 8) of mixed parity; R = 600: two splits of 320 rows
+    _w("s2_9x8_3x1_pad1x0_128to256_t128dma_full", 30, 9, 8, 128, 256, 3, 1, True, True, stride=2, pad=(1, 0)),
+    # 3x3, stride 2, (7, 10) -> (4, 5); R = 200
+    _w("s2_7x10_3x3_200to40_t64ragged", 10, 7, 10, 200, 40, 3, 3, False, True, stride=2, pad=(1, 1)),
+    # 1x1, stride 2, pad 0; R = 600
+    _w("s2_7x10_1x1_256to512_wide", 30, 7, 10, 256, 512, 1, 1, True, True, stride=2),
+    # Ho Wo = 6 < 32: five images and more in one 32-row step; R = 300
+    _w("tiny3x5_n50_s2_3x3_72to132_t128", 50, 3, 5, 72, 132, 3, 3, False, True, stride=2, pad=(1, 1)),
+    _w("tiny3x5_n50_s2_3x3_72to200_t128dma_partial", 50, 3, 5, 72, 200, 3, 3, False, True, stride=2, pad=(1, 1)),
+    _w("tiny3x5_n50_s2_3x3_4to64_t64stem", 50, 3, 5, 4, 64, 3, 3, False, True, stride=2, pad=(1, 1)),
+    _w("tiny3x5_n50_s2_1x3_256to512_wide", 50, 3, 5, 256, 512, 1, 3, False, True, stride=2, pad=(0, 1)),
+    # Wo = 70 > 64 with Ho = 2: a step is less than one image row; R = 420
+    _w("row2x70_3x3_4to64_t64stem", 3, 2, 70, 4, 64, 3, 3, False, True, pad=(1, 1)),
+    _w("row2x70_3x3_128to256_t128dma_full", 3, 2, 70, 128, 256, 3, 3, False, True, pad=(1, 1)),
+    _w("row2x70_3x3_72to132_t128", 3, 2, 70, 72, 132, 3, 3, False, True, pad=(1, 1)),
+    _w("row2x70_1x3_pad0x1_256to512_wide", 3, 2, 70, 256, 512, 1, 3, False, True, pad=(0, 1)),
+    # Wo == 1; R = 63: one pass in every kernel
+    _w("col9x3_wo1_3x3_pad1x0_200to40_t64ragged", 7, 9, 3, 200, 40, 3, 3, False, False, pad=(1, 0)),
+    _w("col9x3_wo1_3x3_pad1x0_72to132_t128", 7, 9, 3, 72, 132, 3, 3, False, False, pad=(1, 0)),
+    _w("col9x3_wo1_3x3_pad1x0_72to200_t128dma_partial", 7, 9, 3, 72, 200, 3, 3, False, False, pad=(1, 0)),
+    _w("col9x3_wo1_3x3_pad1x0_256to512_wide", 7, 9, 3, 256, 512, 3, 3, False, False, pad=(1, 0)),
+]
+
+# ---- weight gradient, causal 1-D (ops.conv1d_wgrad and, through it, conv1d_wgrad_weight_norm_bwd): the ``causal_case`` geometry.
+# x_wide / dz_wide = (pitch, offset): the operand is columns offset .. of a pitch-wide NaN-filled buffer.
+W1Case = namedtuple("W1Case", "case x_wide dz_wide split_f32")
+
+
+def _w1(name, bsz, length, cin, cout, k, dil, x_wide=None, dz_wide=None, split=True):
+    return W1Case(causal_case(name, bsz, length, cin, cout, k, dil), x_wide, dz_wide, split)
+
+
+# R = 300 = 15 sequences of 20: three splits of 128, 128 and 44 rows, sequence boundaries inside steps and inside splits
+WGRAD_1D = [
+    _w1("w1_k5_d1_36to64", 15, 20, 36, 64, 5, 1),
+    _w1("w1_k5_d2_64to36", 15, 20, 64, 36, 5, 2),
+    _w1("w1_k5_d4_96to200", 15, 20, 96, 200, 5, 4),
+    _w1("w1_k5_d8_200to96_zero_taps", 15, 20, 200, 96, 5, 8),          # taps 0 and 1 shift by 32 and 24 >= L: zero slabs
+    _w1("w1_k5_d8_7to7", 15, 20, 7, 7, 5, 8),
+    _w1("w1_k1_200to7", 15, 20, 200, 7, 1, 1),
+    _w1("w1_k1_7to200", 15, 20, 7, 200, 1, 1),
+    _w1("w1_k5_d2_96to64_one_pass", 3, 20, 96, 64, 5, 2, split=False),           # R = 60
+    _w1("w1_k5_d2_96to64_slices_off4_off64", 15, 20, 96, 64, 5, 2, x_wide=(104, 4), dz_wide=(132, 64)),
+    _w1("w1_k1_200to36_slices_off64_off4", 15, 20, 200, 36, 1, 1, x_wide=(264, 64), dz_wide=(44, 4)),
+    _w1("w1_k5_d1_36to64_pitch_not_x4", 15, 20, 36, 64, 5, 1, x_wide=(39, 0), dz_wide=(67, 2)),
+    _w1("w1_k5_d1_36to64_slices_off1_pitch_x4", 15, 20, 36, 64, 5, 1, x_wide=(40, 1), dz_wide=(68, 1)),
+    _w1("w1_k1_96to7_slice_off1_pitch_x4", 15, 20, 96, 7, 1, 1, x_wide=(100, 1)),
+]
+
+# ---- data gradient (visual_backbone._conv_dgrad): 3x3 / pad 1 or 1x1 / pad 0, stride 1 or 2; (dy, w) classes "ints" and "x_lo"
+# (ternary dy, 12-bit weights)
+def _dg(name, n, h, w, cin, cout, k, stride):
+    return C(name, n, h, w, cin, cout, k, k, stride=stride, pad=(k // 2, k // 2))
+
+
+DGRAD_2D = [
+    _dg("dg_s1_3x3_5x12", 3, 5, 12, 32, 64, 3, 1),
+    _dg("dg_s1_1x1_5x12", 3, 5, 12, 64, 128, 1, 1),
+    _dg("dg_s1_3x3_16x32_n32_window", 32, 16, 32, 32, 64, 3, 1),        # 64 blocks of 256 pixels: the window-resident kernels
+    _dg("dg_s2_3x3_5x8", 3, 5, 8, 32, 64, 3, 2),
+    _dg("dg_s2_3x3_8x5", 3, 8, 5, 32, 64, 3, 2),
+    _dg("dg_s2_3x3_7x9", 3, 7, 9, 64, 128, 3, 2),
+    _dg("dg_s2_3x3_6x10", 3, 6, 10, 32, 64, 3, 2),
+    _dg("dg_s2_3x3_1x4", 3, 1, 4, 32, 64, 3, 2),                        # H = 1: the odd-row parities have no pixel
+    _dg("dg_s2_3x3_2x1", 3, 2, 1, 32, 64, 3, 2),
+    _dg("dg_s2_1x1_5x8", 3, 5, 8, 32, 64, 1, 2),
+    _dg("dg_s2_1x1_4x7", 3, 4, 7, 64, 128, 1, 2),
+]
+DGRAD_CLASSES = ("ints", "x_lo")
+
+
+def dgrad_make(case, cls="ints"):
+    """(d, dy) of a data-gradient case: d["w"] [Cout, Cin, KH, KW] and dy [N, Ho, Wo, Cout]."""
+    g = torch.Generator().manual_seed(_seed(case) + 11 * (1 + OPERAND_CLASSES.index(cls)))
+    ho, wo = out_hw_of(case)
+    dy, w = _pair(g, cls, (case.n, ho, wo, case.cout), (case.cout, case.cin, case.kh, case.kw))
+    return {"w": w}, dy
+
+
+# ---- rounding: standard-normal operands on rectangular, asymmetric geometry, one case per kernel family (the names say which)
+WGRAD_ROUNDING = [
+    _w("round_rect10x25_3x2_pad1x0_72to132_f32_and_t128", 6, 10, 25, 72, 132, 3, 2, True, True, pad=(1, 0)),
+    _w("round_s2_9x8_3x1_pad1x0_128to256_t128dma", 30, 9, 8, 128, 256, 3, 1, True, True, stride=2, pad=(1, 0)),
+    _w("round_rect10x25_3x2_pad1x0_200to40_t64", 6, 10, 25, 200, 40, 3, 2, True, True, pad=(1, 0)),
+    _w("round_s2_7x10_1x3_pad0x2_256to512_wide", 30, 7, 10, 256, 512, 1, 3, True, True, stride=2, pad=(0, 2)),
+]
+WGRAD_ROUNDING_1D = _w1("round_w1_k5_d2_96to200", 15, 20, 96, 200, 5, 2)
+
+
+def wgrad_rows_of(case):
+    ho, wo = out_hw_of(case)
+    return case.n * ho * wo
+
+
+def wgrad_bound_b3(case, mag):
+    """The project's bf16x3 bound (tests/test_head_release_gpu.py): every product drops lo lo and rounds both lo parts,
+    <= 2^-15 relative, plus fp32 accumulation over the R rows."""
+    return mag * (2.0 ** -15 + wgrad_rows_of(case) * 2.0 ** -24) + 1e-6
+
+
+def wgrad_bound_f32(case, mag, splits):
+    """The analogue of ``rounding_bound`` with the reduction length R: 1.01 u (R + splits + 8) mag."""
+    return 1.01 * U * (wgrad_rows_of(case) + splits + 8) * mag
+
+
+def weight_norm_bwd_bound(dw, v, g):
+    """Bounds (dv, dg) on the fp32 error of the weight-norm backward of w = g v / n, n = ||v|| per output channel over E elements:
+
+        dg = sum dw v / n,      dv = (g / n) (dw - v dg / n)
+
+    derived like ``rounding_bound``: E products and additions lose <= E u A with A = sum |dw| |v| / n, 8 covers the divisions and
+    the roundings outside the sum, and the fp32 norm the kernel is handed carries a relative error <= E u of its own, which
+    enters dg once (another E u A), the first term of dv once and the second twice."""
+    dw, v, g = dw.double(), v.double(), g.double().reshape(-1, 1, 1)
+    e = v[0].numel()
+    n = v.reshape(v.shape[0], -1).norm(dim=1).reshape(-1, 1, 1)
+    a = (dw.abs() * v.abs()).sum((1, 2), keepdim=True) / n
+    scale = (g / n).abs()
+    dg = 1.01 * U * (2 * e + 8) * a
+    dv = 1.01 * U * ((e + 8) * scale * dw.abs() + (4 * e + 16) * scale * v.abs() / n * a)
+    return dv, dg

@@ -6,6 +6,7 @@
 * torch's own fp32 CPU conv -- a correct fp32 contraction that is not the code under test -- reproduces every exact reference
   bit for bit and stays inside every rounding bound.
 """
+import functools
 import itertools
 
 import pytest
@@ -123,3 +124,184 @@ def test_torch_fp32_meets_the_rounding_bound(case):
     ratio = ((y32.double() - y).abs() / bound).max().item()
     print(f"{case.name}: torch fp32 worst error / bound = {ratio:.3f}" + (f", erf error {erf_err:.3e}" if erf_err is not None else ""))
     assert ratio < 1.0
+
+
+# ====================================================================================================================
+# The backward convs (tests/test_conv_backward_edges_gpu.py): the weight-gradient reference against a gather written out product
+# by product, the precondition of every exact case, torch's fp32 CPU GEMM as a correct contraction that is not the code under
+# test, and the SENSITIVITY of the comparison: contractions with one deliberate mistake each, of the kind a kernel could make,
+# are rejected by the assertion helper the GPU tests use.
+W2D = [w.case for w in cr.WGRAD_2D]
+W1D = [w.case for w in cr.WGRAD_1D]
+
+TINY_W = [
+    cr.C("tinyw_3x2_s2_pad2x0", 2, 4, 5, 3, 4, 3, 2, stride=2, pad=(2, 0)),
+    cr.C("tinyw_1x3_pad0x2", 2, 3, 4, 2, 5, 1, 3, pad=(0, 2)),
+    cr.C("tinyw_3x1_s2_pad1x0", 2, 5, 4, 2, 3, 3, 1, stride=2, pad=(1, 0)),
+    cr.causal_case("tinyw_causal_d2", 2, 5, 2, 3, 3, 2),
+    cr.causal_case("tinyw_causal_d4_past_L", 2, 3, 2, 3, 3, 4),
+]
+
+
+@functools.lru_cache(maxsize=None)
+def _wdata(case, cls):
+    return cr.wgrad_make(case, cls)
+
+
+@functools.lru_cache(maxsize=None)
+def _wref(case, cls):
+    return cr.wgrad_reference(case, *_wdata(case, cls))
+
+
+@pytest.mark.parametrize("cls", cr.OPERAND_CLASSES)
+@pytest.mark.parametrize("case", TINY_W, ids=_ids(TINY_W))
+def test_wgrad_reference_equals_the_gather_loop(case, cls):
+    d, dz = cr.wgrad_make(case, cls)
+    dw, mag = cr.wgrad_reference(case, d, dz)
+    assert dw.dtype == torch.float64 and tuple(dw.shape) == (case.cout, case.cin, case.kh, case.kw)
+    assert torch.equal(dw, cr.wgrad_loops(case, d, dz))
+    assert torch.equal(mag, cr.wgrad_loops(case, {"x": d["x"].abs()}, dz.abs()))
+    assert torch.equal(cr.wgrad_rows(case, d, dz, dtype=torch.float64), dw)
+    assert dw.abs().max().item() > 0
+
+
+def _is_class(cls, z, x):
+    """The structure the exactness argument rests on: multiples of 2^-8, and one operand of every product without a lo plane."""
+    for t in (z, x):
+        assert torch.equal(t * 256, (t * 256).round()) and t.abs().max().item() <= 8.0
+    if cls == "ints":
+        assert torch.equal(z, z.round()) and torch.equal(x, x.round())
+    z_lo, x_lo = z - cr.bf16_hi(z), x - cr.bf16_hi(x)
+    assert torch.equal(cr.bf16_hi(z_lo), z_lo) and torch.equal(cr.bf16_hi(x_lo), x_lo)        # hi + lo is the value
+    assert not (z_lo != 0).any() or not (x_lo != 0).any()
+    if cls != "ints":
+        frac = ((x_lo if cls == "x_lo" else z_lo) != 0).float().mean().item()
+        assert 0.5 < frac < 0.8, frac                                                          # the lo plane is exercised
+
+
+def _three_products(case, d, dz):
+    """float32 emulation of the bf16x3 kernels: hi hi + hi lo + lo hi, each a float32 GEMM, the lo lo product dropped."""
+    zh, xh = cr.bf16_hi(dz), cr.bf16_hi(d["x"])
+    zl, xl = dz - zh, d["x"] - xh
+    return cr.wgrad_rows(case, {"x": xh}, zl) + cr.wgrad_rows(case, {"x": xl}, zh) + cr.wgrad_rows(case, {"x": xh}, zh)
+
+
+@pytest.mark.parametrize("cls", cr.OPERAND_CLASSES)
+@pytest.mark.parametrize("case", W2D + W1D, ids=_ids(W2D + W1D))
+def test_wgrad_case_meets_its_precondition_and_torch_fp32_is_bit_exact(case, cls):
+    d, dz = _wdata(case, cls)
+    ho, wo = cr.out_hw_of(case)
+    assert tuple(dz.shape) == (case.n, ho, wo, case.cout) and tuple(d["x"].shape) == (case.n, case.h, case.w, case.cin)
+    assert case.n * ho * wo <= 2000 and max(case.cin, case.cout) <= 512
+    _is_class(cls, dz, d["x"])
+    assert cr.wgrad_exact_margin(case, d, dz) < cr.WGRAD_LIMIT
+    dw, _ = _wref(case, cls)
+    got = cr.wgrad_rows(case, d, dz)
+    assert got.dtype == torch.float32
+    cr.assert_exact(got, dw, case.name)
+    cr.assert_exact(_three_products(case, d, dz), dw, case.name + " (three products)")
+    assert dw.abs().max().item() > 0
+    if case.w == 1 and case.kw == 1:                  # causal: a tap whose shift reaches the sequence length sees no data at all
+        for j in range(case.kh):
+            if (case.kh - 1 - j) * case.dil[0] >= case.h:
+                assert not dw[:, :, j].any()
+
+
+def test_the_backward_tables_contain_what_they_are_for():
+    names = [c.name for c in W2D + W1D + cr.DGRAD_2D + [w.case for w in cr.WGRAD_ROUNDING] + [cr.WGRAD_ROUNDING_1D.case]]
+    assert len(names) == len(set(names))
+    geo = {(c.kh, c.kw, c.stride, c.pad) for c in W2D}
+    assert {(3, 2), (1, 3), (3, 1), (1, 1), (3, 3)} <= {(kh, kw) for kh, kw, _, _ in geo}
+    assert any(p == (0, 2) and kw == 3 for _, kw, _, p in geo) and any(p == (2, 0) and kh == 3 for kh, _, _, p in geo)
+    assert any(c.stride == 2 and (c.h + c.w) % 2 == 1 for c in W2D) and any(c.stride == 2 and c.kh == c.kw == 1 for c in W2D)
+    outs = [cr.out_hw_of(c) for c in W2D]
+    assert any(ho * wo < 32 and c.n >= 50 for c, (ho, wo) in zip(W2D, outs))
+    assert any(wo > 64 and ho == 2 for ho, wo in outs) and any(wo == 1 for _, wo in outs)
+    assert any(cr.wgrad_rows_of(c) % 32 for c in W2D)
+    chans = {(c.cin, c.cout) for c in W2D}
+    assert {(4, 64), (200, 40), (72, 132), (72, 200), (128, 256), (256, 512)} <= chans
+    assert any(ci == 3 for ci, _ in chans) and any(co == 7 for _, co in chans)
+    b3 = [w for w in cr.WGRAD_2D if w.split_b3 is not None]
+    assert all((w.split_b3 is None) == bool(w.case.cin % 4 or w.case.cout % 4) for w in cr.WGRAD_2D)
+    assert sum(w.split_b3 for w in b3) >= 3 and sum(w.split_f32 for w in cr.WGRAD_2D) >= 2
+    for path in ("t64", "t128_", "t128dma", "wide"):       # every kernel has a split and a single-pass case
+        mine = [w for w in b3 if path in w.case.name + "_"]
+        assert any(w.split_b3 for w in mine) and not all(w.split_b3 for w in mine), path
+    assert not all(w.split_f32 for w in cr.WGRAD_2D) and not all(w.split_f32 for w in cr.WGRAD_1D)
+    one = cr.WGRAD_1D
+    assert {w.case.dil[0] for w in one if w.case.kh == 5} == {1, 2, 4, 8} and any(w.case.kh == 1 for w in one)
+    assert {7, 36, 64, 96, 200} <= {w.case.cin for w in one} | {w.case.cout for w in one}
+    wides = [s for w in one for s in (w.x_wide, w.dz_wide) if s is not None]
+    assert {4, 64} <= {off for pitch, off in wides if pitch % 4 == 0}
+    assert any(pitch % 4 for pitch, _ in wides) and any(pitch % 4 == 0 and off == 1 for pitch, off in wides)
+
+
+# ---------------------------------------------------------------------------------------------- sensitivity
+def _rejected(case, cls, mutant):
+    d, dz = _wdata(case, cls)
+    try:
+        cr.assert_exact(cr.wgrad_rows(case, d, dz, mutant=mutant), _wref(case, cls)[0], f"{case.name} [{mutant}]")
+    except AssertionError:
+        return True
+    return False
+
+
+# mutant -> (operand class, the table cases that have to catch it)
+_CATCHERS = {
+    "hw_swap": ("ints", ["rect10x25_3x3_4to64_t64stem", "row2x70_3x3_128to256_t128dma_full", "tiny3x5_n50_s2_3x3_72to132_t128"]),
+    "pad_swap": ("ints", ["rect10x25_3x2_pad1x0_72to132_t128", "rect7x12_1x3_pad0x2_72to200_t128dma_partial",
+                          "rect6x11_3x3_pad2x0_128to256_t128dma_full"]),
+    "tap_div_kh": ("ints", ["rect10x25_3x2_pad1x0_72to132_t128", "rect7x12_1x3_pad0x2_72to200_t128dma_partial",
+                            "s2_9x8_3x1_pad1x0_128to256_t128dma_full"]),
+    "drop_last_step": ("ints", ["rect10x25_3x3_4to64_t64stem", "rect7x12_1x3_pad0x2_72to200_t128dma_partial",
+                                "w1_k5_d1_36to64"]),
+    "drop_lo": ("x_lo", ["rect10x25_3x2_pad1x0_72to132_t128", "s2_7x10_1x1_256to512_wide", "tiny3x5_n50_s2_3x3_4to64_t64stem"]),
+    "tile_neighbour": ("ints", ["rect7x12_1x3_pad0x2_72to200_t128dma_partial", "rect10x25_3x2_pad1x0_72to132_t128",
+                                "s2_7x10_1x1_256to512_wide"]),
+}
+
+
+@pytest.mark.parametrize("mutant", cr.WGRAD_MUTANTS)
+def test_a_wrong_contraction_is_rejected_by_the_comparison_the_gpu_tests_use(mutant):
+    cls, names = _CATCHERS[mutant]
+    table = cr.by_name(W2D + W1D)
+    for name in names:
+        assert _rejected(table[name], cls, mutant), f"{mutant} passes on {name}"
+        assert not _rejected(table[name], cls, None)
+    caught = [c.name for c in W2D if _rejected(c, cls, mutant)]
+    print(f"{mutant}: rejected on {len(caught)} of {len(W2D)} WGRAD_2D cases")
+
+
+def test_the_lo_plane_of_dz_is_needed_in_the_mirror_class():
+    case = cr.by_name(W2D)["rect10x25_3x2_pad1x0_72to132_t128"]
+    d, dz = _wdata(case, "z_lo")
+    with pytest.raises(AssertionError, match="values differ"):
+        cr.assert_exact(cr.wgrad_rows(case, d, cr.bf16_hi(dz)), _wref(case, "z_lo")[0], case.name)
+
+
+# ---------------------------------------------------------------------------------------------- data gradient
+@pytest.mark.parametrize("cls", cr.DGRAD_CLASSES)
+@pytest.mark.parametrize("case", cr.DGRAD_2D, ids=_ids(cr.DGRAD_2D))
+def test_dgrad_2d_case_meets_its_precondition_and_torch_fp32_is_bit_exact(case, cls):
+    d, dy = cr.dgrad_make(case, cls)
+    _is_class(cls, dy, d["w"])
+    dx, mag = cr.dgrad_reference(case, d, dy)
+    assert tuple(dx.shape) == (case.n, case.h, case.w, case.cin)
+    assert 2.0 ** 9 * mag.max().item() < cr.WGRAD_LIMIT
+    x = torch.zeros(case.n, case.h, case.w, case.cin, requires_grad=True)
+    raw = cr._contract(x.permute(0, 3, 1, 2), d["w"], case.stride, case.dil, case.pad[0], case.pad[1], None)
+    assert raw.dtype == torch.float32 and tuple(raw.shape) == tuple(dy.shape)
+    cr.assert_exact(torch.autograd.grad(raw, x, dy)[0], dx, case.name)
+    assert dx.abs().max().item() > 0
+
+
+# ---------------------------------------------------------------------------------------------- rounding cases
+@pytest.mark.parametrize("w", cr.WGRAD_ROUNDING + [cr.WGRAD_ROUNDING_1D], ids=lambda w: w.case.name)
+def test_torch_fp32_meets_the_weight_gradient_bounds(w):
+    case = w.case
+    d, dz = cr.wgrad_make(case, "normal")
+    dw, mag = cr.wgrad_reference(case, d, dz)
+    err = (cr.wgrad_rows(case, d, dz).double() - dw).abs()
+    r32, rb3 = (err / cr.wgrad_bound_f32(case, mag, 1)).max().item(), (err / cr.wgrad_bound_b3(case, mag)).max().item()
+    print(f"{case.name}: torch fp32 worst error / fp32 bound = {r32:.3f}, / bf16x3 bound = {rb3:.3f}")
+    assert r32 < 1.0 and rb3 < 1.0
