@@ -21,6 +21,9 @@ def __getattr__(name):
     if name == "AVStream":
         from . import live
         return live.AVStream
+    if name == "TextStream":
+        from . import text_stream
+        return text_stream.TextStream
     if name == "DecisionStream":
         from . import decisions
         return decisions.DecisionStream

@@ -81,6 +81,35 @@ class MultimodalFeatureExtractor(torch.nn.Module):
         return rows.view(bsz, 1, num_frames, hd)
 
     @torch.no_grad()
+    def paragraph_features(self, token_ids, attention_mask, sentence_counts, num_frames, attention_mask_cpu=None):
+        """ids/mask [N,S]: the padded sentences of B clips, clip b owning ``sentence_counts[b]`` consecutive rows (the
+        reference splits a transcript into sentences and runs BERT on each, speech.py:629-661) -> [B,1,L,768].  A clip's
+        surviving tokens (``exclude_padding`` per sentence) are concatenated in order and spread over its ``num_frames``; a
+        clip without a word gets zeros.  One BERT call on the ids as given, then one ``ops.text_spread_rows``."""
+        counts = [int(c) for c in sentence_counts]
+        n, s = token_ids.shape
+        if any(c < 0 for c in counts) or sum(counts) != n or not counts:
+            raise ValueError(f"sentence_counts {counts}: expected counts >= 0 that sum to the {n} rows of token_ids")
+        if num_frames < 1:
+            raise ValueError(f"num_frames = {num_frames}: must be >= 1")
+        mask_cpu = attention_mask_cpu if attention_mask_cpu is not None else attention_mask.cpu()
+        segments, row = [], 0
+        for b, c in enumerate(counts):
+            words = []
+            for k in range(row, row + c):
+                attended = torch.nonzero(mask_cpu[k] == 1).flatten().tolist()
+                if len(attended) == s:
+                    raise ValueError("The sentence is too long, enlarge the token number!")
+                words += [k * s + t for t in attended[1:-1]]   # drop [CLS] and the last attended token ([SEP])
+            segments.append((b * num_frames, num_frames, words))
+            row += c
+        tok = self.text(token_ids, attention_mask)
+        hd = tok.shape[2]
+        rows = ops.text_spread_rows(tok.view(n * s, hd), segments, len(counts) * num_frames,
+                                    out=torch.empty((len(counts) * num_frames, hd), device=tok.device))
+        return rows.view(len(counts), 1, num_frames, hd)
+
+    @torch.no_grad()
     def forward(self, frames, pcm_int16, token_ids, attention_mask, attention_mask_cpu=None, sample_rate=16000,
                 resample=None):
         """-> dict in the model's modality order {video, vggish, bert}."""

@@ -15,11 +15,12 @@ last row" of ``MultimodalFeatureExtractor.audio_features``.
 
 State.  Host: the three ints per stream.  Device: the ``FrameStream`` ring [S, Rf, crop, crop, 3] uint8; an example ring
 [S, Re, win * 64] float32; one ring [S, Rf, E_m] float32 per further modality (``bert`` rows that come with the frames and wait
-as long as they do).  The float rings are written with ``ops.tcn_stream_append_rows`` and read with ``ops.gather_rows``: no
-kernel of their own.  Rf = ``hold_ring(hold, max_new)``: at most ``hold`` frames wait when a push brings at most ``max_new``.
+as long as they do, or, with a text leg, the rows a ``TextStream`` made of finished sentences, see the class text).  The
+float rings are written with ``ops.tcn_stream_append_rows`` and read with ``ops.gather_rows``: no kernel of their own.
+Rf = ``hold_ring(hold, max_new)``: at most ``hold`` frames wait when a push brings at most ``max_new``.
 Re = ``hold_ring(lead, examples_per_step(...))``: at most ``lead`` examples wait when a push completes at most
-``examples_per_step`` new ones.  Example e sits in slot e mod Re; a stream's last example stays in its slot until the stream
-is reset.
+``examples_per_step`` new ones (``hold + lead`` with a text leg).  Example e sits in slot e mod Re; a stream's last example
+stays in its slot until the stream is reset.
 
 Examples per step.  A push (or one padding step of the audio stage's ``finish``) adds at most ``max_out`` 16 kHz samples to a
 stream (``max_samples``, or the resampler's ``max_outputs``), hence at most r = max_out // 160 + 1 STFT rows.  Example e
@@ -44,6 +45,26 @@ def pair_schedule(frames, examples, paired, final=None):
     if final is None:
         return [(i, i) for i in range(paired, min(frames, examples))]
     return [(i, min(i, final - 1)) for i in range(paired, frames)] if final > 0 else []
+
+
+def pair_schedule_text(frames, examples, text, paired, final=None):
+    """``pair_schedule`` for a session with a text leg: ``text`` is the number of frames whose text row is final.  Before the
+    end a frame is emitted once its example AND its text row exist: frames paired .. min(frames, examples, text) - 1.  At the
+    end (``final``) the session first advances the text to ``frames`` with zero rows (a frame whose sentence never came has no
+    word), so nothing waits for text any more and the pairs are ``pair_schedule``'s.  Python ints, no GPU."""
+    if final is None:
+        return pair_schedule(min(frames, text), examples, paired)
+    return pair_schedule(frames, examples, paired, final=final)
+
+
+def check_text_waiting(text_seen, new, paired, ring_frames):
+    """What ``AVStream.push_text`` refuses for one stream, as ints: the text rows of frames ``paired`` .. ``text_seen + new``
+    - 1 wait in a ring of ``ring_frames`` slots (slot = frame number masked), so text may not run further ahead of the pairing
+    than the ring holds.  Returns the rows that wait after the call, before pairing."""
+    waiting = text_seen + new - paired
+    if waiting > ring_frames:
+        raise ValueError(f"{text_seen - paired} text rows wait for their frames and {new} more exceed the ring of {ring_frames}")
+    return waiting
 
 
 def examples_per_step(max_out, hop_frames):
@@ -86,7 +107,9 @@ class AVStream:
             edge padding, the last example repeated, examples past the last frame dropped); those streams are reset.  A stream
             that received frames but never a sample emits nothing for them.
       reset(streams=None)    forget those streams.
-      frames_seen, examples_seen, paired   host lists, one int per stream.
+      push_text(sentences, upto=None)   with ``text=``: finished sentences with their frame spans, as ``TextStream.push`` takes
+            them -> (logits, counts) like ``push``: text arriving can release frames that were waiting for it.
+      frames_seen, examples_seen, paired   host lists, one int per stream; with ``text=`` also text_seen.
       decisions              with ``decisions=`` (a dict of ``DecisionStream`` keyword arguments, ``{}`` for the defaults): a
             ``DecisionStream`` the session owns and feeds every logit row it emits, in ``push`` and in ``finish``;
             ``av.decisions.decide()`` gives the running video-level decisions.  ``finish`` leaves a stream's decisions
@@ -99,13 +122,23 @@ class AVStream:
     the encoders inside the model, so a row's bits do not depend on how many frames a push paired.  The dict handed to the model
     stream is keyed in the model's own modality order.
 
+    The text leg.  ``text=TextStream(encoder, streams, ...)`` makes the session produce the ``bert`` rows itself: ``bert`` leaves
+    ``extra_keys`` (``extra`` for it is refused) and a frame is emitted once its example and its text row exist
+    (``pair_schedule_text``).  Text rows wait in the [S, Rf, 768] ring that ``extra`` rows use, slot = frame number masked with
+    Rf - 1, written at ``text_seen``; ``push_text`` refuses text that runs more than Rf rows ahead of the pairing
+    (``check_text_waiting``).  Frames now wait for their sentence as well, so ``hold`` has to cover an utterance (e.g. 512 at
+    30 fps), and a stream can have up to ``hold`` examples whose frames are unpaired plus ``lead`` ahead of the frames: the
+    example ring is ``hold_ring(hold + lead, examples_per_step)`` slots of win * 64 floats, 24.6 KB per example (1024
+    slots, 25 MB per stream, at hold = 512).  ``finish`` advances the stream's text to its last frame with zero rows first.
+    Tokenisation and speech recognition are the caller's, and spans are frame numbers.
+
     A push that would let more than ``hold`` frames or ``lead`` examples wait, and any argument one of the stages refuses,
     raises ValueError before any launch and changes no state, the stages' included.  A stream's counts above ``max_new`` in one
     call reach the model in several pushes, in time order."""
 
     def __init__(self, model, streams, fps, *, sample_rate=16000, channels=1, resample=None, size=48, crop=40, hold=64, lead=8,
                  max_new=32, max_samples=4096, encoder_batch=8, audio_backbone=None, decisions=None,
-                 max_side=1024, video_format="rgb24", video_matrix="bt601", video_range="limited"):
+                 max_side=1024, video_format="rgb24", video_matrix="bt601", video_range="limited", text=None):
         cls = CANStream if isinstance(model, CAN) else LFANStream
         if not isinstance(model, cls._model_class):
             raise TypeError(f"AVStream needs an LFAN or a CAN (JMT / MT attend over time and are not causal), got "
@@ -121,7 +154,16 @@ class AVStream:
         if isinstance(lead, bool) or int(lead) != lead or lead < 1:
             raise ValueError(f"lead = {lead!r}: must be an integer >= 1")
         self.audio_key = audio_keys[0]
-        self.extra_keys = [m for m in mods if m != "video" and m != self.audio_key]
+        self.text = text
+        if text is not None:
+            from .text_stream import TextStream
+            if not isinstance(text, TextStream):
+                raise TypeError(f"text: expected a TextStream, got {type(text).__name__}")
+            if "bert" not in mods:
+                raise ValueError(f"AVStream: a text leg needs a model with 'bert', got {mods}")
+            if text.streams != int(streams):
+                raise ValueError(f"text: a TextStream of {text.streams} streams for a session of {int(streams)}")
+        self.extra_keys = [m for m in mods if m != "video" and m != self.audio_key and not (m == "bert" and text is not None)]
         self.audio_backbone = None
         if self.audio_key == "vggish":
             spatial = getattr(model, "spatial", {})
@@ -139,9 +181,19 @@ class AVStream:
         max_out = max_samples if resample is None else self.audio_stream.max_outputs
         self.examples_per_step = examples_per_step(max_out, self.audio_stream.hop_frames)
         self.ring_frames = self.frame_stream.ring_frames
-        self.ring_examples = hold_ring(self.lead, self.examples_per_step)
+        # with a text leg the examples of up to ``hold`` unpaired frames wait too, not only the ``lead`` ahead of the frames
+        self.ring_examples = hold_ring(self.lead + (self.hold if text is not None else 0), self.examples_per_step)
         self.extra_dims = {m: self.model_stream.tcn[m].cin for m in self.extra_keys}
-        for m, e in self.extra_dims.items():
+        self._ring_dims = dict(self.extra_dims)   # every float ring of frame rows: the extra modalities and the text leg's
+        if text is not None:
+            self._ring_dims["bert"] = self.model_stream.tcn["bert"].cin
+            if text.hidden != self._ring_dims["bert"]:
+                raise ValueError(f"text: the encoder's hidden size {text.hidden} is not the model's 'bert' embedding dim "
+                                 f"{self._ring_dims['bert']}")
+            if text.device != device:
+                raise ValueError(f"text: the encoder is on {text.device}, the model on {device}")
+            text.reset()
+        for m, e in self._ring_dims.items():
             if e % 4:
                 raise ValueError(f"{m}: embedding dim {e} is not a multiple of 4 (the row gather moves float4)")
         self.frames_seen, self.examples_seen, self.paired = [0] * self.streams, [0] * self.streams, [0] * self.streams
@@ -179,7 +231,7 @@ class AVStream:
         if self._exring is None:
             self._exring = torch.zeros((self.streams, self.ring_examples, self.win * 64), device=self.device, dtype=torch.float32)
             self._extra = {m: torch.zeros((self.streams, self.ring_frames, e), device=self.device, dtype=torch.float32)
-                           for m, e in self.extra_dims.items()}
+                           for m, e in self._ring_dims.items()}
 
     def _hold_rows(self, rows, ring, positions, counts):
         row_stream, row_pos = ops.stream_row_table(positions, counts, self.device)
@@ -272,14 +324,53 @@ class AVStream:
             for m in self.extra_keys:
                 self._hold_rows(extra[m], self._extra[m], self.frames_seen, vcounts)
             self.frames_seen = [f + c for f, c in zip(self.frames_seen, vcounts)]
-        owed = [pair_schedule(f, e, p) for f, e, p in zip(self.frames_seen, self.examples_seen, self.paired)]
+        return self._emit_owed()
+
+    @property
+    def text_seen(self):
+        """Per stream, the frames whose text row is final (the ``TextStream``'s ``covered``); None without a text leg."""
+        return None if self.text is None else self.text.covered
+
+    def _emit_owed(self):
+        """Pair what every stream owes now and run it."""
+        if self.text is None:
+            owed = [pair_schedule(f, e, p) for f, e, p in zip(self.frames_seen, self.examples_seen, self.paired)]
+        else:
+            owed = [pair_schedule_text(f, e, t, p)
+                    for f, e, t, p in zip(self.frames_seen, self.examples_seen, self.text.covered, self.paired)]
         return self._emit(owed, lambda pairs: self._held_rows(self._exring, pairs))
+
+    def _hold_text(self, rows, counts, before):
+        """The new text rows of a ``TextStream`` call into their ring slots, at the frame numbers ``before`` (+ i)."""
+        if sum(counts):
+            self._hold_rows(rows, self._extra["bert"], before, counts)
+
+    @torch.no_grad()
+    def push_text(self, sentences, upto=None):
+        if self.text is None:
+            raise ValueError("push_text: the session has no text leg (AVStream(..., text=TextStream(...)))")
+        self.model_stream._check_keys(dict.fromkeys(self.model_stream.modalities))
+        plan = self.text.check_push(sentences, upto)
+        for s, new in enumerate(plan[2]):
+            try:
+                check_text_waiting(self.text.covered[s], new, self.paired[s], self.ring_frames)
+            except ValueError as err:
+                raise ValueError(f"stream {s}: {err}") from None
+        # nothing below refuses
+        self._alloc()
+        before = list(self.text.covered)
+        self._hold_text(*self.text._run(plan), before)
+        return self._emit_owed()
 
     @torch.no_grad()
     def finish(self, streams=None):
         idx = sorted(set(self._indices(streams)))
         self.model_stream._check_keys(dict.fromkeys(self.model_stream.modalities))
         self._alloc()
+        if self.text is not None:   # frames whose sentence never came have no word: zero rows, written over the slots' stale ones
+            upto = {s: self.frames_seen[s] for s in idx if self.text.covered[s] < self.frames_seen[s]}
+            plan, at = self.text.check_push([], upto), list(self.text.covered)
+            self._hold_text(*self.text._run(plan), at)
         before = list(self.examples_seen)
         last, got = self.audio_stream.finish(idx)   # every remaining example of those streams, stream-major
         first, at = {}, 0
@@ -291,8 +382,9 @@ class AVStream:
         re, tail = self.ring_examples, last.view(-1, self.win * 64)
 
         def example_rows(pairs):
-            # an example emitted before the end sits in its ring slot (only the last one can be asked for: the earlier ones
-            # were paired when they came, or belong to frames that never came); one the end produced is a row of ``last``
+            # an example emitted before the end sits in its ring slot (without a text leg only the last one can be asked for:
+            # the earlier ones were paired when they came, or belong to frames that never came; with one, any example from
+            # ``paired`` on, whose frame was still waiting for its text); one the end produced is a row of ``last``
             index = [s * re + (e & (re - 1)) if e < before[s] else self.streams * re + first[s] + e - before[s] for s, e in pairs]
             src = self._exring.view(-1, self.win * 64)
             if any(i < self.streams * re for i in index):
@@ -317,5 +409,7 @@ class AVStream:
         self.frame_stream.reset(idx)
         self.audio_stream.reset(idx)
         self.model_stream.reset(idx)
+        if self.text is not None:
+            self.text.reset(idx)
         for s in idx:
             self.frames_seen[s] = self.examples_seen[s] = self.paired[s] = 0

@@ -1820,6 +1820,69 @@ def tcn_stream_conv_rows(ring, row_stream, row_pos, max_count, w_packed, bias, k
                  out_ring, out_dense)
 
 
+# ------------------------------------------------------------------ token rows -> frame rows (csrc/text_spread.hip)
+def text_spread_tables(segments, out_rows, tok_rows):
+    """The two tables of one ``text_spread_rows`` as Python ints, checked: ``segments`` = (out_first, n_frames, token_rows) per
+    entry -> ([(out_first, n_frames, n_tokens, index_first)], the token rows of all segments in order).  Output ranges are
+    disjoint and inside [0, out_rows), every token row is inside [0, tok_rows).  No GPU."""
+    table, index, spans = [], [], []
+    for g, seg in enumerate(segments):
+        try:
+            first, frames, rows = seg
+            rows = list(rows)
+        except (TypeError, ValueError):
+            raise ValueError(f"text_spread_rows: segment {g}: expected (out_first, n_frames, token_rows), got {seg!r}") from None
+        for v in (first, frames, *rows):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"text_spread_rows: segment {g}: {v!r} is not an int")
+        first, frames = int(first), int(frames)
+        if frames < 1 or first < 0 or first + frames > out_rows:
+            raise ValueError(f"text_spread_rows: segment {g}: frames [{first}, {first + frames}) outside [0, {out_rows}) or empty")
+        for t in rows:
+            if not 0 <= t < tok_rows:
+                raise ValueError(f"text_spread_rows: segment {g}: token row {t} outside [0, {tok_rows})")
+        table.append((first, frames, len(rows), len(index)))
+        index += [int(t) for t in rows]
+        spans.append((first, first + frames, g))
+    if not table:
+        raise ValueError("text_spread_rows: no segment")
+    spans.sort()
+    for (_, end, a), (start, _, b) in zip(spans, spans[1:]):
+        if start < end:
+            raise ValueError(f"text_spread_rows: segments {a} and {b} overlap at output row {start}")
+    return table, index
+
+
+def text_spread_rows(tok, segments, out_rows, out=None):
+    """Token rows of one or more sentences -> the rows of spans of frames (speech.py:690-738), one launch.  ``tok`` [T, hidden]
+    fp32; ``segments``: (out_first, n_frames, token_rows) per entry, Python ints: frame i of the n_frames output rows from
+    out_first shows row ``token_rows[j(i)]`` of ``tok``, the frames divided into min(len(token_rows), n_frames) contiguous
+    blocks of which the first n_frames % n are one longer (``feature_extractor.align_tokens_to_frames``), or zeros when
+    ``token_rows`` is empty.  Returns ``out`` [out_rows, hidden]; rows no segment covers are zeros in a fresh ``out`` and stay
+    as they are in a caller's.  Both tables travel as one fresh int32 tensor per call [segments | index]."""
+    _dev_f32(tok, "tok")
+    out_rows = int(out_rows)
+    if tok.dim() != 2 or tok.shape[0] < 1 or tok.shape[1] % 4 or tok.shape[1] < 4:
+        raise ValueError(f"tok: expected [T >= 1, hidden] with hidden a multiple of 4, got {tuple(tok.shape)}")
+    if out_rows < 1:
+        raise ValueError(f"out_rows = {out_rows}: must be >= 1")
+    if out is not None:
+        _dev_f32(out, "out")
+        if tuple(out.shape) != (out_rows, tok.shape[1]) or out.device != tok.device:
+            raise ValueError(f"out: expected [{out_rows}, {tok.shape[1]}] on {tok.device}, got {tuple(out.shape)} on {out.device}")
+    table, index = text_spread_tables(segments, out_rows, tok.shape[0])
+    g = len(table)
+    host = np.zeros(4 * g + max(len(index), 1), np.int32)   # a lone 0 when no segment has a token: the entry wants n_index >= 1
+    host[:4 * g] = np.asarray(table, np.int64).ravel()
+    host[4 * g:4 * g + len(index)] = index
+    dev = torch.from_numpy(host).to(tok.device)
+    if out is None:
+        out = torch.zeros((out_rows, tok.shape[1]), device=tok.device, dtype=torch.float32)
+    check(_lib.load().cer_text_spread_rows(ptr(tok), tok.shape[0], tok.shape[1], ptr(dev[:4 * g]), g, ptr(dev[4 * g:]),
+                                           host.shape[0] - 4 * g, ptr(out), out_rows, current_stream()), "cer_text_spread_rows")
+    return out
+
+
 # ------------------------------------------------------------------ streaming log-mel (csrc/logmel_stream.hip)
 def logmel_stream_tables(segments, rows, examples, device):
     """The three tables of one streamed log-mel push, from Python ints, uploaded as ONE fresh int32 tensor (one H2D copy, no

@@ -461,6 +461,19 @@ int cer_adam_flat_amp(float *param, float *grad, float *exp_avg, float *exp_avg_
  * (base/preprocessing.py:992-1018); the index plan is host logic.  cols % 4 == 0. */
 int cer_gather_rows(const float *src, const int64_t *index, float *out, int n_out, int cols, int64_t n_src, void *stream);
 
+/* Token rows of one or more sentences -> the rows of spans of frames, the index plan formed in the kernel
+ * (speech.py:690-738, align_word_embedding_new).  tok [tok_rows][hidden]; segments [n_segments][4] int32 = (out_first,
+ * n_frames, n_tokens, index_first); tok_index [n_index] int32; out [out_rows][hidden]; all device pointers.  For segment g
+ * and 0 <= i < n_frames, with n = min(n_tokens, n_frames) and q, r = divmod(n_frames, n):
+ *   out[out_first + i][:] = tok[tok_index[index_first + j(i)]][:],  j(i) = i / (q + 1) if i < r (q + 1), else
+ *   r + (i - r (q + 1)) / q   (the first r tokens get one frame more; tokens beyond the frame count are dropped);
+ *   n <= 0: the row becomes zeros.  Rows of out that no segment covers are not written; the caller keeps the segments'
+ * output ranges disjoint.  The tables are never trusted with an address: output rows outside [0, out_rows) are skipped, the
+ * index position is clamped into [0, n_index) and the token row into [0, tok_rows).  Null pointers, sizes < 1,
+ * hidden % 4 != 0 and tok / out / segments not 16-byte aligned return CER_ERR_INVALID_ARG before any launch. */
+int cer_text_spread_rows(const float *tok, int64_t tok_rows, int hidden, const int32_t *segments, int n_segments,
+                         const int32_t *tok_index, int n_index, float *out, int64_t out_rows, void *stream);
+
 /* ------------------------------------------------------------------------
  * Audio / text encoder front ends and attention.
  * ---------------------------------------------------------------------- */
