@@ -61,6 +61,15 @@ class Yuv420Desc(Structure):
     _fields_ = [(n, c_int32) for n in ("layout", "cy", "crv", "cgu", "cgv", "cbu", "yoff")]
 
 
+SURFACE_PACKED, SURFACE_YUV420, SURFACE_YUV422 = 0, 1, 2   # cer_surface.format
+
+
+class SurfaceDesc(Structure):
+    """cer_surface (see include/cer_hip.h)."""
+    _fields_ = [(n, c_int32) for n in ("format", "cy", "crv", "cgu", "cgv", "cbu", "yoff")] + [
+        ("step", c_int32 * 2), ("pos", c_int32 * 3), ("frame_stride", c_int64), ("pitch", c_int64 * 2), ("offset", c_int64 * 3)]
+
+
 _SIGNATURES = {
     # name: (restype, argtypes)
     "cer_last_error": (c_char_p, []),
@@ -201,6 +210,12 @@ _SIGNATURES = {
     "cer_decision_stream_push": (c_int, [POINTER(DecisionStreamDesc), _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cer_decision_stream_read": (c_int, [POINTER(DecisionStreamDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
+
+# the _surface sibling of an RGB frame entry: its arguments with (frames_bytes, cer_surface) after ``frames``
+for _name in ("cer_frames_transform", "cer_frames_stream_append", "cer_frames_transform_boxes", "cer_frames_stream_append_boxes",
+              "cer_frames_transform_affine", "cer_frames_stream_append_affine"):
+    _res, _args = _SIGNATURES[_name]
+    _SIGNATURES[_name + "_surface"] = (_res, [_args[0], c_size_t, POINTER(SurfaceDesc)] + _args[1:])
 
 _lib = None
 

@@ -15,7 +15,8 @@
 // image, then vertically into the normalised fp32 output.
 //
 // cer_frames_transform_yuv is the same launch on NV12 / I420 frames: the band is converted to RGB bytes while it is staged
-// (px_yuv420, frames_kernel.h), and everything after that is the code above on the same bytes.
+// (px_yuv420, frames_kernel.h), and everything after that is the code above on the same bytes.  cer_frames_transform_surface
+// is the same launch again on frames read in place in any byte order and layout (px_surface, after surface_pixel's check).
 #include <stdint.h>
 
 #include "frames_kernel.h"
@@ -92,3 +93,15 @@ extern "C" int cer_frames_transform_yuv(const uint8_t *frames, const cer_yuv420 
 }
 
 extern "C" int cer_frames_band_rows(void) { return FR_BAND; }
+
+extern "C" int cer_frames_transform_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface, int n_frames,
+                                            int H, int W, const int32_t *hbounds, const int32_t *hcoef, int hksize,
+                                            const int32_t *vbounds, const int32_t *vcoef, int vksize, int size, int crop,
+                                            const int32_t *crop_xyf, int frames_per_group, int max_band_rows, float mean,
+                                            float stdv, float *out, uint8_t *out_u8, void *stream) {
+    px_surface pix;
+    const int rc = surface_pixel("frames_transform_surface", surface, frames_bytes, n_frames, H, W, &pix);
+    if (rc != CER_OK) return rc;
+    return frames_transform_launch(frames, n_frames, H, W, hbounds, hcoef, hksize, vbounds, vcoef, vksize, size, crop, crop_xyf,
+                                   frames_per_group, max_band_rows, mean, stdv, out, out_u8, stream, pix);
+}

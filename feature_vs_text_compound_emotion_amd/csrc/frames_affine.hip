@@ -26,7 +26,7 @@
 // One path, two ways to name a frame (Place) and two ways to read a pixel (Pixel), as in frames_box.hip:
 //   cer_frames_transform_affine       clip form        cer_frames_stream_append_affine       ring form
 // and their _yuv siblings for NV12 / I420: the four pixels are converted, then interpolated, which is what converting the
-// frame and then warping it gives.
+// frame and then warping it gives; the _surface siblings do the same on frames read in place (px_surface).
 //
 // Nothing here trusts a table with an address.  An affine row is six doubles that are only ever compared and multiplied: a
 // coordinate becomes an int after the positive-form inside test has passed (a NaN is outside), and every pixel is fetched at
@@ -100,7 +100,7 @@ __device__ __forceinline__ void fa_warp(const Pixel &pix, const uint8_t *img, in
 // Place:  int  source(int f)                                   the packed input frame that launch row f reads (any int)
 //         void entry(int f, int &x1, int &y1, int &flip)       its crop entry (any ints)
 //         void store(int f, int c, int yy, int xc, int v)      where byte v of channel c, cropped row yy, column xc goes
-// Pixel:  px_rgb24 or px_yuv420 (frames_kernel.h), asked at clamped indices only
+// Pixel:  px_rgb24, px_yuv420 or px_surface (frames_kernel.h), asked at clamped indices only
 template <class Place, class Pixel>
 __global__ __launch_bounds__(256) void frames_affine_kernel(FramesAffineArgs p, Place place, Pixel pix) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fa_smem[];
@@ -344,6 +344,33 @@ extern "C" int cer_frames_stream_append_affine_yuv(const uint8_t *frames, const 
     const char *name = "frames_stream_append_affine_yuv";
     px_yuv420 pix;
     const int rc = yuv420_pixel(name, yuv, H, W, &pix);
+    if (rc != CER_OK) return rc;
+    return fa_ring_launch(name, frames, n_frames, H, W, affines, bounds, coef, ksize, align_size, max_band_rows, size, crop, crop_xyf,
+                          row_stream, row_pos, num_rows, max_count, u8ring, S, Rf, stream, pix);
+}
+
+extern "C" int cer_frames_transform_affine_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface,
+                                                   int n_frames, int H, int W, const double *affines, const int32_t *bounds,
+                                                   const int32_t *coef, int ksize, int align_size, int max_band_rows, int size,
+                                                   int crop, const int32_t *crop_xyf, int frames_per_group, float mean,
+                                                   float stdv, float *out, uint8_t *out_u8, void *stream) {
+    const char *name = "frames_transform_affine_surface";
+    px_surface pix;
+    const int rc = surface_pixel(name, surface, frames_bytes, n_frames, H, W, &pix);
+    if (rc != CER_OK) return rc;
+    return fa_clip_launch(name, frames, n_frames, H, W, affines, bounds, coef, ksize, align_size, max_band_rows, size, crop, crop_xyf,
+                          frames_per_group, mean, stdv, out, out_u8, stream, pix);
+}
+
+extern "C" int cer_frames_stream_append_affine_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface,
+                                                       int n_frames, int H, int W, const double *affines, const int32_t *bounds,
+                                                       const int32_t *coef, int ksize, int align_size, int max_band_rows,
+                                                       int size, int crop, const int32_t *crop_xyf, const int32_t *row_stream,
+                                                       const int32_t *row_pos, int num_rows, int max_count, uint8_t *u8ring,
+                                                       int S, int Rf, void *stream) {
+    const char *name = "frames_stream_append_affine_surface";
+    px_surface pix;
+    const int rc = surface_pixel(name, surface, frames_bytes, n_frames, H, W, &pix);
     if (rc != CER_OK) return rc;
     return fa_ring_launch(name, frames, n_frames, H, W, affines, bounds, coef, ksize, align_size, max_band_rows, size, crop, crop_xyf,
                           row_stream, row_pos, num_rows, max_count, u8ring, S, Rf, stream, pix);

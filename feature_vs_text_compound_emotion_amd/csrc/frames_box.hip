@@ -15,7 +15,8 @@
 //   cer_frames_transform_boxes       clip form: fp32 NCHW (and the optional uint8 NHWC), a crop entry per clip.
 //   cer_frames_stream_append_boxes   ring form: the byte into u8ring at row_pos & (Rf - 1), row_stream clamped.
 // And two ways to read a pixel (Pixel, frames_kernel.h): the _yuv siblings of both take NV12 / I420 frames and convert the
-// pixels of the box, and nothing else, in registers.
+// pixels of the box, and nothing else, in registers; the _surface siblings read frames in place in any byte order and layout
+// (px_surface), after surface_pixel has checked the descriptor against the bytes the caller vouches for.
 //
 // LDS does not grow with the camera frame: the horizontal pass reads the frame from global memory (a band of a 1024-pixel box
 // would be 590 KB of staged rows) and writes an LDS tile [band rows][crop][3]; the coefficient rows of the block's columns and
@@ -54,7 +55,7 @@ inline size_t frames_box_lds_bytes(int max_rows, int crop, int max_ks) {
 // Place:  int  source(int f)                                   the packed input frame that launch row f reads (any int)
 //         void entry(int f, int &x1, int &y1, int &flip)       its crop entry (any ints)
 //         void store(int f, int c, int yy, int xc, int v)      where byte v of channel c, cropped row yy, column xc goes
-// Pixel:  px_rgb24 or px_yuv420 (frames_kernel.h), asked at the clamped (fx, fy) only
+// Pixel:  px_rgb24, px_yuv420 or px_surface (frames_kernel.h), asked at the clamped (fx, fy) only
 template <class Place, class Pixel>
 __global__ __launch_bounds__(256) void frames_box_kernel(FramesBoxArgs p, Place place, Pixel pix) {
     extern __shared__ __attribute__((aligned(16))) uint8_t fb_smem[];
@@ -286,6 +287,33 @@ extern "C" int cer_frames_stream_append_boxes_yuv(const uint8_t *frames, const c
     const char *name = "frames_stream_append_boxes_yuv";
     px_yuv420 pix;
     const int rc = yuv420_pixel(name, yuv, H, W, &pix);
+    if (rc != CER_OK) return rc;
+    return fb_ring_launch(name, frames, n_frames, H, W, boxes, box_meta, box_data, max_side, max_band_rows, max_ksize, size, crop,
+                          crop_xyf, row_stream, row_pos, num_rows, max_count, u8ring, S, Rf, stream, pix);
+}
+
+extern "C" int cer_frames_transform_boxes_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface,
+                                                  int n_frames, int H, int W, const int32_t *boxes, const int32_t *box_meta,
+                                                  const int32_t *box_data, int max_side, int max_band_rows, int max_ksize,
+                                                  int size, int crop, const int32_t *crop_xyf, int frames_per_group, float mean,
+                                                  float stdv, float *out, uint8_t *out_u8, void *stream) {
+    const char *name = "frames_transform_boxes_surface";
+    px_surface pix;
+    const int rc = surface_pixel(name, surface, frames_bytes, n_frames, H, W, &pix);
+    if (rc != CER_OK) return rc;
+    return fb_clip_launch(name, frames, n_frames, H, W, boxes, box_meta, box_data, max_side, max_band_rows, max_ksize, size, crop,
+                          crop_xyf, frames_per_group, mean, stdv, out, out_u8, stream, pix);
+}
+
+extern "C" int cer_frames_stream_append_boxes_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface,
+                                                      int n_frames, int H, int W, const int32_t *boxes, const int32_t *box_meta,
+                                                      const int32_t *box_data, int max_side, int max_band_rows, int max_ksize,
+                                                      int size, int crop, const int32_t *crop_xyf, const int32_t *row_stream,
+                                                      const int32_t *row_pos, int num_rows, int max_count, uint8_t *u8ring,
+                                                      int S, int Rf, void *stream) {
+    const char *name = "frames_stream_append_boxes_surface";
+    px_surface pix;
+    const int rc = surface_pixel(name, surface, frames_bytes, n_frames, H, W, &pix);
     if (rc != CER_OK) return rc;
     return fb_ring_launch(name, frames, n_frames, H, W, boxes, box_meta, box_data, max_side, max_band_rows, max_ksize, size, crop,
                           crop_xyf, row_stream, row_pos, num_rows, max_count, u8ring, S, Rf, stream, pix);

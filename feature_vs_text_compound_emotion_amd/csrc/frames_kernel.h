@@ -86,6 +86,103 @@ inline int yuv420_pixel(const char *name, const cer_yuv420 *d, int H, int W, px_
     return CER_OK;
 }
 
+// A surface (cer_surface, cer_hip.h): the three bytes of pixel (x, y) lie at
+//   a[y * pitch0 + x * s0 + o0],  b[(y >> ysh) * pitch1 + (x >> xsh) * s1 + o1],  c[(y >> ysh) * pitch1 + (x >> xsh) * s1 + o2]
+// from the plane offsets off0, off1, off2 of a frame of `stride` bytes.  One functor for the three cases -- packed 3 / 4 bytes
+// in any channel order (no shifts, the three planes are one), 4:2:0 with independent planes (NV12, NV21, I420, YV12), packed
+// 4:2:2 -- because the index arithmetic is the same expression for all of them; the only branch, `convert`, is uniform over
+// the launch.  Indices are 64-bit: x * 4 of a 2^29-pixel row does not fit an int.
+struct px_surface {
+    static constexpr bool packed_rgb = false;
+    int64_t stride, pitch0, pitch1, off0, off1, off2;
+    int s0, s1, o0, o1, o2, xsh, ysh, convert;
+    int cy, crv, cgu, cgv, cbu, yoff;
+    struct Row {
+        const uint8_t *a, *b, *c;
+    };
+    __device__ __forceinline__ size_t frame_bytes(int, int) const { return (size_t)stride; }
+    __device__ __forceinline__ Row row(const uint8_t *img, int, int y) const {
+        const uint8_t *c = img + (size_t)(y >> ysh) * (size_t)pitch1;
+        return Row{img + (size_t)off0 + (size_t)y * (size_t)pitch0, c + (size_t)off1, c + (size_t)off2};
+    }
+    __device__ __forceinline__ void get(const Row &r, int x, int (&px)[3]) const {
+        const size_t ci = (size_t)(x >> xsh) * s1;
+        const int a = r.a[(size_t)x * s0 + o0], b = r.b[ci + o1], c3 = r.c[ci + o2];
+        if (convert) {  // the expression of px_yuv420::get
+            const int c = cy * (a - yoff) + (1 << (CER_YUV_PREC - 1)), u = b - 128, v = c3 - 128;
+            px[0] = clip8((c + crv * v) >> CER_YUV_PREC);
+            px[1] = clip8((c + cgu * u + cgv * v) >> CER_YUV_PREC);
+            px[2] = clip8((c + cbu * u) >> CER_YUV_PREC);
+        } else {
+            px[0] = a; px[1] = b; px[2] = c3;
+        }
+    }
+};
+
+// What the _surface entries refuse about the descriptor, the picture and the extent of `frames`, and the functor of what they
+// accept.  Everything is compared or divided, never multiplied up, so no value can wrap: after this check
+// (n_frames - 1) * stride + the end of every plane <= frames_bytes, which is the bound of every address px_surface forms from
+// a frame below n_frames and a pixel inside the picture.
+inline int surface_pixel(const char *name, const cer_surface *d, size_t frames_bytes, int n_frames, int H, int W, px_surface *px) {
+#define SP_REFUSE(...) return cer_set_error(CER_ERR_INVALID_ARG, __VA_ARGS__)
+    if (!d) SP_REFUSE("%s: null pointer (surface)", name);
+    if (d->format != CER_SURFACE_PACKED && d->format != CER_SURFACE_YUV420 && d->format != CER_SURFACE_YUV422)
+        SP_REFUSE("%s: format = %d is not a CER_SURFACE_ format", name, d->format);
+    const int32_t k[5] = {d->cy, d->crv, d->cgu, d->cgv, d->cbu};
+    for (int i = 0; i < 5; ++i)
+        if (k[i] < -(1 << 20) || k[i] > (1 << 20))
+            SP_REFUSE("%s: a conversion coefficient of %d lies beyond +-2^20 (int32 sums)", name, k[i]);
+    if (d->yoff < 0 || d->yoff > 255) SP_REFUSE("%s: yoff = %d is outside 0 .. 255", name, d->yoff);
+    const bool p = d->format == CER_SURFACE_PACKED, c420 = d->format == CER_SURFACE_YUV420;
+    if (n_frames < 1 || H < 1 || W < 1) SP_REFUSE("%s: frames and the picture's H and W must be >= 1", name);
+    if (c420 ? ((H | W) & 1) != 0 : (!p && (W & 1)))
+        SP_REFUSE("%s: a %s picture needs even %s, got %d x %d", name, c420 ? "4:2:0" : "4:2:2", c420 ? "H and W" : "W", H, W);
+    if ((size_t)H * W > (size_t)1 << 29) SP_REFUSE("%s: a picture of %d x %d exceeds 2^29 pixels", name, H, W);
+    // the byte pattern of the format
+    const int32_t *s = d->step, *o = d->pos;
+    bool ok;
+    if (p) ok = (s[0] == 3 || s[0] == 4) && s[1] == s[0] && o[0] >= 0 && o[0] < s[0] && o[1] >= 0 && o[1] < s[0] && o[2] >= 0 && o[2] < s[0];
+    else if (c420) ok = s[0] == 1 && (s[1] == 1 || s[1] == 2) && o[0] == 0 && o[1] == 0 && o[2] == 0;
+    else ok = s[0] == 2 && s[1] == 4 && (o[0] == 0 || o[0] == 1) && o[1] >= 0 && o[1] < 4 && o[2] >= 0 && o[2] < 4;
+    if (!ok)
+        SP_REFUSE("%s: step = (%d, %d), pos = (%d, %d, %d) is not a byte pattern of format %d", name, s[0], s[1], o[0], o[1], o[2],
+                  d->format);
+    const int64_t lim = (int64_t)1 << 40;
+    const int64_t v[6] = {d->frame_stride, d->pitch[0], d->pitch[1], d->offset[0], d->offset[1], d->offset[2]};
+    for (int i = 0; i < 6; ++i) {
+        if (v[i] < 0) SP_REFUSE("%s: a negative offset, pitch or frame_stride (%lld)", name, (long long)v[i]);
+        if (v[i] >= lim) SP_REFUSE("%s: an offset, pitch or frame_stride of %lld is 2^40 or more", name, (long long)v[i]);
+    }
+    if (!c420 && (d->pitch[1] != d->pitch[0] || d->offset[1] != d->offset[0] || d->offset[2] != d->offset[0]))
+        SP_REFUSE("%s: a packed format has one plane: its pitches and its offsets must be equal", name);
+    // rows, nominal bytes of a row (what the pitch must cover) and bytes a row is read over, per plane
+    const int64_t rows[3] = {H, c420 ? H / 2 : H, c420 ? H / 2 : H};
+    const int64_t pitch[3] = {d->pitch[0], d->pitch[1], d->pitch[1]};
+    const int64_t need[3] = {(int64_t)W * s[0], c420 ? (int64_t)(W / 2) * s[1] : (int64_t)W * s[0], c420 ? (int64_t)(W / 2) * s[1] : (int64_t)W * s[0]};
+    const int64_t used[3] = {need[0], c420 ? (int64_t)(W / 2 - 1) * s[1] + 1 : need[0], c420 ? (int64_t)(W / 2 - 1) * s[1] + 1 : need[0]};
+    int64_t extent = 0;
+    for (int i = 0; i < 3; ++i) {
+        if (pitch[i] < need[i])
+            SP_REFUSE("%s: a pitch of %lld is below the %lld bytes of a row", name, (long long)pitch[i], (long long)need[i]);
+        // offset + (rows - 1) * pitch + used <= frame_stride, without forming the product
+        const int64_t room = d->frame_stride - d->offset[i] - used[i];
+        if (d->offset[i] > d->frame_stride || used[i] > d->frame_stride - d->offset[i] || (rows[i] > 1 && pitch[i] > room / (rows[i] - 1)))
+            SP_REFUSE("%s: the plane at offset %lld (%lld rows, pitch %lld) ends past frame_stride = %lld", name,
+                      (long long)d->offset[i], (long long)rows[i], (long long)pitch[i], (long long)d->frame_stride);
+        const int64_t end = d->offset[i] + (rows[i] - 1) * pitch[i] + used[i];  // <= frame_stride < 2^40
+        extent = end > extent ? end : extent;
+    }
+    if ((uint64_t)extent > (uint64_t)frames_bytes ||
+        (n_frames > 1 && (uint64_t)d->frame_stride > ((uint64_t)frames_bytes - (uint64_t)extent) / (uint64_t)(n_frames - 1)))
+        SP_REFUSE("%s: %d frames of stride %lld and extent %lld exceed frames_bytes = %zu", name, n_frames, (long long)d->frame_stride,
+                  (long long)extent, frames_bytes);
+#undef SP_REFUSE
+    *px = px_surface{d->frame_stride, d->pitch[0], d->pitch[1], d->offset[0], d->offset[1], d->offset[2],
+                     s[0], s[1], o[0], o[1], o[2], p ? 0 : 1, c420 ? 1 : 0, p ? 0 : 1,
+                     d->cy, d->crv, d->cgu, d->cgv, d->cbu, d->yoff};
+    return CER_OK;
+}
+
 // LDS of one block: the staged input rows, the horizontally resampled rows, the two coefficient tiles
 inline size_t frames_lds_bytes(int max_band_rows, int W, int crop) {
     return (((size_t)max_band_rows * W * 3 + 15) & ~(size_t)15) + (((size_t)max_band_rows * crop * 3 + 15) & ~(size_t)15) +

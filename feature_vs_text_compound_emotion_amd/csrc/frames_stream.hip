@@ -9,7 +9,8 @@
 //   cer_frames_stream_append   packed raw frames [n][H][W][3] -> GroupScale -> crop -> flip -> ring slot.  This is
 //                              frames_transform_kernel (frames_kernel.h) with the streamed way to name a frame: the same band
 //                              staging, dword fast path and generic path as cer_frames_transform, so the same bytes.
-//                              cer_frames_stream_append_yuv: the same on NV12 / I420 frames, as cer_frames_transform_yuv.
+//                              cer_frames_stream_append_yuv: the same on NV12 / I420 frames, as cer_frames_transform_yuv;
+//                              cer_frames_stream_append_surface: on frames read in place, as cer_frames_transform_surface.
 //   cer_frames_stream_gather   ring slots -> fp32 [M][3][crop][crop] = frame_px(byte), the tensor the visual backbone takes.
 //                              HBM-bound (3 crop^2 bytes in, 12 crop^2 out per frame); no LDS: a thread turns 16 pixels (three
 //                              16-byte loads) into four float4 stores per channel plane, and a block's stores of one plane
@@ -160,4 +161,18 @@ extern "C" int cer_frames_stream_gather(const uint8_t *u8ring, int S, int Rf, in
                row_stream, row_pos, out, S, Rf, npx, wide, mean, stdv);
     CER_HIP_CHECK(hipGetLastError());
     return CER_OK;
+}
+
+extern "C" int cer_frames_stream_append_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface,
+                                                int n_frames, int H, int W, const int32_t *hbounds, const int32_t *hcoef,
+                                                int hksize, const int32_t *vbounds, const int32_t *vcoef, int vksize, int size,
+                                                int crop, const int32_t *crop_xyf, int max_band_rows, const int32_t *row_stream,
+                                                const int32_t *row_pos, int num_rows, int max_count, uint8_t *u8ring, int S,
+                                                int Rf, void *stream) {
+    px_surface pix;
+    const int rc = surface_pixel("frames_stream_append_surface", surface, frames_bytes, n_frames, H, W, &pix);
+    if (rc != CER_OK) return rc;
+    return frames_stream_append_launch(frames, n_frames, H, W, hbounds, hcoef, hksize, vbounds, vcoef, vksize, size, crop,
+                                       crop_xyf, max_band_rows, row_stream, row_pos, num_rows, max_count, u8ring, S, Rf, stream,
+                                       pix);
 }

@@ -8,6 +8,8 @@ frames that are already resident in HBM.  The resize is bit-identical to ``PIL.I
 (``precompute_coeffs`` + ``normalize_coeffs_8bpc`` of Pillow's Resample.c, third-party, restated) once per
 geometry and the kernel does the two fixed-point passes.
 """
+import dataclasses
+import functools
 import math
 import random
 
@@ -310,7 +312,13 @@ def similarity_from_landmarks(landmarks, align_size=ALIGN_SIZE):
     return out
 
 
-PIXEL_FORMATS = ("rgb24", "nv12", "i420")
+PIXEL_FORMATS = ("rgb24", "nv12", "i420", "bgr24", "rgba32", "bgra32", "yuyv422", "uyvy422")
+PACKED_FORMATS = {"rgb24": (3, (0, 1, 2)), "bgr24": (3, (2, 1, 0)), "rgba32": (4, (0, 1, 2)), "bgra32": (4, (2, 1, 0))}
+"""Bytes per pixel and the byte of R, G, B inside one; a fourth byte is never read."""
+YUV422_FORMATS = {"yuyv422": (0, 1, 3), "uyvy422": (1, 0, 2)}
+"""The byte of Y0, U, V inside the four bytes of a pixel pair; Y1 is two after Y0."""
+SURFACE_MAX = 1 << 40       # every offset, pitch and stride of a layout is below this (csrc/frames_kernel.h)
+SURFACE_MAX_PIXELS = 1 << 29
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}                    # (kr, kb)
 YUV_RANGES = {"limited": (255.0 / 219.0, 255.0 / 224.0, 16), "full": (1.0, 1.0, 0)}      # (luma scale, chroma scale, yoff)
 
@@ -331,14 +339,227 @@ def yuv_coefficients(matrix="bt601", range="limited"):
 
 
 def yuv_desc(pixel_format="rgb24", matrix="bt601", range="limited"):
-    """What a stream or transform keeps of its pixel format: None for packed RGB, the ``cer_yuv420`` of the C entries for
-    ``nv12`` / ``i420``.  Unknown names raise ValueError, whatever the format."""
+    """What a stream or transform keeps of its pixel format for the 4:2:0 entries: the ``cer_yuv420`` for ``nv12`` / ``i420``,
+    None for ``rgb24`` (and for the formats that only the surface entries read).  Unknown names raise ValueError, whatever
+    the format."""
     if pixel_format not in PIXEL_FORMATS:
         raise ValueError(f"pixel_format = {pixel_format!r}: expected one of {list(PIXEL_FORMATS)}")
     coef = yuv_coefficients(matrix, range)
-    if pixel_format == "rgb24":
+    if pixel_format not in ("nv12", "i420"):
         return None
     return _lib.Yuv420Desc(_lib.YUV_NV12 if pixel_format == "nv12" else _lib.YUV_I420, *coef)
+
+
+def _layout_int(name, v, least=0):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"{name} = {v!r}: must be an integer")
+    if not least <= v < SURFACE_MAX:
+        raise ValueError(f"{name} = {v}: must be in {least} .. 2^40 - 1")
+    return int(v)
+
+
+@dataclasses.dataclass(frozen=True)
+class SurfaceLayout:
+    """Where the bytes of an H x W picture lie in a frame of ``frame_stride`` bytes: host ints only, checked when built
+    (``surface_layout`` is the spelling with keywords).  ``offsets`` are (plane 0,) for the packed formats, (Y, chroma) for
+    ``nv12`` and (Y, first chroma plane, second chroma plane) for ``i420``; ``chroma`` says whether U (``"uv"``) or V
+    (``"vu"``: NV21, YV12) is the first chroma byte or plane.  Nothing has to be aligned and planes may overlap."""
+    pixel_format: str
+    height: int
+    width: int
+    pitch: int = None
+    chroma_pitch: int = None
+    offsets: tuple = None
+    frame_stride: int = None
+    chroma: str = "uv"
+
+    def __post_init__(self):
+        fmt, put = self.pixel_format, lambda k, v: object.__setattr__(self, k, v)      # noqa: E731
+        if fmt not in PIXEL_FORMATS:
+            raise ValueError(f"pixel_format = {fmt!r}: expected one of {list(PIXEL_FORMATS)}")
+        h, w = _layout_int("height", self.height, 1), _layout_int("width", self.width, 1)
+        put("height", h), put("width", w)
+        planar = fmt in ("nv12", "i420")
+        if w % 2 and (planar or fmt in YUV422_FORMATS):
+            raise ValueError(f"width = {w}: a {fmt} picture needs an even width")
+        if h % 2 and planar:
+            raise ValueError(f"height = {h}: a {fmt} picture needs an even height")
+        if h * w > SURFACE_MAX_PIXELS:
+            raise ValueError(f"height = {h}, width = {w}: more than 2^29 pixels")
+        if self.chroma not in ("uv", "vu"):
+            raise ValueError(f"chroma = {self.chroma!r}: expected 'uv' or 'vu'")
+        if self.chroma == "vu" and not planar:
+            raise ValueError(f"chroma = 'vu': only nv12 and i420 have a chroma order to exchange, not {fmt}")
+        row = w * (1 if planar else 2 if fmt in YUV422_FORMATS else PACKED_FORMATS[fmt][0])
+        pitch = row if self.pitch is None else _layout_int("pitch", self.pitch)
+        if pitch < row:
+            raise ValueError(f"pitch = {pitch}: below the {row} bytes of a row")
+        put("pitch", pitch)
+        if not planar:
+            if self.chroma_pitch is not None:
+                raise ValueError(f"chroma_pitch = {self.chroma_pitch!r}: {fmt} has no chroma plane")
+            plane_rows = [(h, pitch, row)]
+        else:
+            crow = w if fmt == "nv12" else w // 2
+            if self.chroma_pitch is None:
+                if fmt == "i420" and pitch % 2:
+                    raise ValueError(f"pitch = {pitch}: odd, so i420 needs a chroma_pitch of its own")
+                cpitch = pitch if fmt == "nv12" else pitch // 2
+            else:
+                cpitch = _layout_int("chroma_pitch", self.chroma_pitch)
+            if cpitch < crow:
+                raise ValueError(f"chroma_pitch = {cpitch}: below the {crow} bytes of a chroma row")
+            put("chroma_pitch", cpitch)
+            plane_rows = [(h, pitch, row)] + [(h // 2, cpitch, crow)] * (1 if fmt == "nv12" else 2)
+        if self.offsets is None:
+            offsets, at = [], 0
+            for rows, p, _ in plane_rows:
+                offsets.append(at)
+                at += rows * p
+        else:
+            try:
+                offsets = list(self.offsets)
+            except TypeError:
+                raise ValueError(f"offsets = {self.offsets!r}: expected {len(plane_rows)} byte offsets") from None
+            if len(offsets) != len(plane_rows):
+                raise ValueError(f"offsets = {self.offsets!r}: {fmt} has {len(plane_rows)} plane offsets")
+        offsets = tuple(_layout_int(f"offsets[{i}]", v) for i, v in enumerate(offsets))
+        put("offsets", offsets)
+        ends = [o + rows * p for o, (rows, p, _) in zip(offsets, plane_rows)]
+        stride = max(ends) if self.frame_stride is None else _layout_int("frame_stride", self.frame_stride, 1)
+        _layout_int("frame_stride", stride, 1)
+        put("frame_stride", stride)
+        for i, (o, (rows, p, used)) in enumerate(zip(offsets, plane_rows)):
+            if o + (rows - 1) * p + used > stride:
+                raise ValueError(f"offsets[{i}] = {o}: the plane's last row ends at {o + (rows - 1) * p + used}, past frame_stride = "
+                                 f"{stride}")
+
+    def planes(self):
+        """(offset, pitch, rows, bytes of a row) of every plane, in the order of ``offsets``."""
+        fmt, h, w = self.pixel_format, self.height, self.width
+        if fmt == "nv12":
+            shapes = [(h, self.pitch, w), (h // 2, self.chroma_pitch, w)]
+        elif fmt == "i420":
+            shapes = [(h, self.pitch, w)] + [(h // 2, self.chroma_pitch, w // 2)] * 2
+        else:
+            shapes = [(h, self.pitch, w * (2 if fmt in YUV422_FORMATS else PACKED_FORMATS[fmt][0]))]
+        return [(o, p, rows, row) for o, (rows, p, row) in zip(self.offsets, shapes)]
+
+    @property
+    def extent(self):
+        """Bytes of a frame up to the end of the last row that is read."""
+        return max(o + (rows - 1) * p + row for o, p, rows, row in self.planes())
+
+    @classmethod
+    def of_view(cls, frames, pixel_format):
+        """The layout of a packed-format tensor [M, H, W, C] as its strides give it: the last two are (C, 1), the row stride is
+        the pitch, the frame stride the stride.  Any other stride pattern raises ValueError (such a view is copied)."""
+        chan = 2 if pixel_format in YUV422_FORMATS else PACKED_FORMATS.get(pixel_format, (None,))[0]
+        if chan is None:
+            raise ValueError(f"pixel_format = {pixel_format!r}: only the packed formats have a layout in their strides")
+        if not (torch.is_tensor(frames) and frames.dim() == 4 and frames.shape[3] == chan and min(frames.shape) >= 1):
+            raise ValueError(f"frames: expected a {pixel_format} tensor [M >= 1, H, W, {chan}], got "
+                             f"{tuple(frames.shape) if torch.is_tensor(frames) else type(frames)}")
+        return _layout_of_strides(pixel_format, chan, tuple(frames.shape), tuple(frames.stride()))
+
+    def fits_view(self, frames):
+        """Whether the strides of ``frames`` [M, H, W, C] are this layout (``of_view`` of it, or of frames sliced off it)."""
+        try:
+            got = SurfaceLayout.of_view(frames, self.pixel_format)
+        except ValueError:
+            return False
+        return (self.offsets == (0,) and (got.height, got.width) == (self.height, self.width) and
+                (got.height == 1 or got.pitch == self.pitch) and (frames.shape[0] == 1 or got.frame_stride == self.frame_stride))
+
+
+@functools.lru_cache(maxsize=256)
+def _layout_of_strides(pixel_format, chan, shape, strides):
+    """``SurfaceLayout.of_view`` on host ints; kept per (format, shape, strides), so a stream of equal frames builds one."""
+    (m, h, w, _), (sm, sh, sw, sc) = shape, strides
+    if (sw, sc) != (chan, 1) or (h > 1 and sh < w * chan) or (m > 1 and sm <= 0):
+        raise ValueError(f"frames: strides {strides} are not rows of {chan}-byte pixels")
+    pitch = sh if h > 1 else w * chan
+    extent = (h - 1) * pitch + w * chan
+    return SurfaceLayout(pixel_format, h, w, pitch=pitch, frame_stride=sm if m > 1 else max(sm, extent))
+
+
+def surface_layout(pixel_format, height, width, *, pitch=None, chroma_pitch=None, offsets=None, frame_stride=None, chroma="uv"):
+    """The ``SurfaceLayout`` of an H x W picture.  ``pitch``: bytes from one row of plane 0 to the next (default: tight);
+    ``chroma_pitch``: of the chroma planes (default ``pitch`` for nv12, ``pitch / 2`` for i420); ``offsets``: of every plane
+    inside a frame (default: tight after the pitches); ``frame_stride``: bytes from frame m to frame m + 1 (default: the end
+    of the last plane); ``chroma="vu"``: the V byte or plane comes first (NV21, YV12).  Refusals are ValueErrors that name
+    the argument."""
+    return SurfaceLayout(pixel_format, height, width, pitch, chroma_pitch, offsets, frame_stride, chroma)
+
+
+class Surface:
+    """What the ``surface=`` of the frame wrappers in ``ops`` is: a ``SurfaceLayout`` and the (cy, crv, cgu, cgv, cbu, yoff)
+    of ``yuv_coefficients``; ``desc()`` is the ``cer_surface`` of the C entries."""
+
+    def __init__(self, layout, coef=None):
+        if not isinstance(layout, SurfaceLayout):
+            raise ValueError(f"layout: expected a SurfaceLayout (frames.surface_layout), got {type(layout).__name__}")
+        self.layout, self.coef, self._desc = layout, tuple(yuv_coefficients() if coef is None else coef), None
+
+    def desc(self):
+        """The ``cer_surface``, built once: the entries only read it."""
+        if self._desc is None:
+            self._desc = self._build()
+        return self._desc
+
+    def _build(self):
+        lay, fmt = self.layout, self.layout.pixel_format
+        d = _lib.SurfaceDesc(0, *self.coef)
+        d.frame_stride = lay.frame_stride
+        if fmt in ("nv12", "i420"):
+            d.format, first = _lib.SURFACE_YUV420, 0 if lay.chroma == "uv" else 1
+            if fmt == "nv12":
+                y, c = lay.offsets
+                step, offset = (1, 2), (y, c + first, c + 1 - first)
+            else:
+                y, c1, c2 = lay.offsets
+                step, offset = (1, 1), (y, (c1, c2)[first], (c1, c2)[1 - first])
+            pos, pitch = (0, 0, 0), (lay.pitch, lay.chroma_pitch)
+        else:
+            if fmt in YUV422_FORMATS:
+                d.format, step, pos = _lib.SURFACE_YUV422, (2, 4), YUV422_FORMATS[fmt]
+            else:
+                d.format, step, pos = _lib.SURFACE_PACKED, (PACKED_FORMATS[fmt][0],) * 2, PACKED_FORMATS[fmt][1]
+            pitch, offset = (lay.pitch,) * 2, lay.offsets * 3
+        d.step[:], d.pos[:], d.pitch[:], d.offset[:] = step, pos, pitch, offset
+        return d
+
+
+class _Laid:
+    """Frames and the ``layout=`` they came with, as one argument."""
+    __slots__ = ("frames", "layout")
+
+    def __init__(self, frames, layout):
+        self.frames, self.layout = frames, layout
+
+
+def _unlaid(frames):
+    return (frames.frames, frames.layout) if isinstance(frames, _Laid) else (frames, None)
+
+
+def takes_layout(arg, key="layout"):
+    """Gives a method that takes frames as ``arg`` the keyword ``key``: the ``SurfaceLayout`` of those frames, which then
+    travel with it as one argument down to the check that looks at frames (``FrameTransform._source``).  One spelling of the
+    keyword for every call that takes frames; the methods' own signatures stay what they were."""
+    def wrap(method):
+        @functools.wraps(method)
+        def call(self, *args, **kw):
+            layout = kw.pop(key, None)
+            if layout is not None:
+                if args:
+                    args = (_Laid(args[0], layout),) + args[1:]
+                elif kw.get(arg) is not None:
+                    kw[arg] = _Laid(kw[arg], layout)
+                else:
+                    raise ValueError(f"{key} without {arg}")
+            return method(self, *args, **kw)
+        return call
+    return wrap
 
 
 def yuv_picture(rows, width):
@@ -370,6 +591,15 @@ class FrameTransform:
     [H / 2][W / 2] and the V plane.  Pixel (x, y) takes the chroma sample (x >> 1, y >> 1) -- nearest siting -- and the
     integers of ``yuv_coefficients(matrix, range)``; the result is the bits the RGB call gives the converted frames.  Boxes
     stay in luma pixels.  An odd H or W, a wrong rank and unknown names raise ValueError before any launch.
+
+    The other formats are read in place by the ``_surface`` entries: ``"bgr24"`` [B, L, H, W, 3], ``"rgba32"`` / ``"bgra32"``
+    [B, L, H, W, 4] (the fourth byte is never read), ``"yuyv422"`` / ``"uyvy422"`` [B, L, H, W, 2] with W even (a row is
+    ``Y0 U Y1 V`` / ``U Y0 V Y1``; pixel (x, y) takes its own Y and the chroma of pair x >> 1 of its row, the integers of
+    ``yuv_coefficients``).  A view of a packed format whose strides are rows of pixels is read through them, not copied.
+    ``layout=`` (keyword, on ``aligned`` too): the ``surface_layout`` of the frames -- row pitches, plane offsets, frame
+    stride, chroma order -- of any format, ``"rgb24"``, ``"nv12"`` and ``"i420"`` included; ``frames`` is then a contiguous
+    uint8 tensor [B, L, ...] with ``layout.frame_stride`` bytes per frame.  Either way the result is the bits the
+    ``"rgb24"`` call gives the converted, tightly packed frames.
     """
 
     def __init__(self, size=48, crop=40, train=True, mean=0.5, std=0.5, max_side=BOX_MAX_SIDE, pixel_format="rgb24",
@@ -377,6 +607,7 @@ class FrameTransform:
         self.size, self.crop, self.train, self.mean, self.std = size, crop, train, float(mean), float(std)
         self.pixel_format, self.matrix, self.range = pixel_format, matrix, range
         self.yuv = yuv_desc(pixel_format, matrix, range)
+        self._coef, self._surfaces = yuv_coefficients(matrix, range), {}
         if isinstance(max_side, bool) or int(max_side) != max_side or not 1 <= max_side <= BOX_COORD:
             raise ValueError(f"max_side = {max_side!r}: must be an integer in 1 .. {BOX_COORD}")
         self.max_side = int(max_side)
@@ -411,8 +642,77 @@ class FrameTransform:
                 out[i, 0] = out[i, 1] = int(round((self.size - self.crop) / 2.0))
         return out
 
+    def _source(self, frames, layout, lead, who="frames"):
+        """How frames that do not go through the RGB and 4:2:0 entries are read in place: None when they do go through
+        them -- a contiguous ``rgb24`` tensor, ``nv12`` / ``i420`` without a layout -- else (the frames with their ``lead``
+        leading dimensions flattened into one, those dimensions, H, W, the ``Surface``).  Under ``layout`` the frames are a
+        contiguous uint8 tensor with ``layout.frame_stride`` bytes per frame; without one they are [..., H, W, C] of a packed
+        format, and a view whose strides are rows of pixels is read through them (``SurfaceLayout.of_view``), any other is
+        copied.  Every refusal is a ValueError; the shape is looked at first, then the device."""
+        fmt, f = self.pixel_format, frames
+        if layout is not None:
+            if not isinstance(layout, SurfaceLayout):
+                raise ValueError(f"layout: expected a SurfaceLayout (frames.surface_layout), got {type(layout).__name__}")
+            if layout.pixel_format != fmt:
+                raise ValueError(f"layout: its pixel_format {layout.pixel_format!r} is not this one's, {fmt!r}")
+            if not (torch.is_tensor(f) and f.dtype == torch.uint8 and f.dim() > lead and f.is_contiguous()
+                    and int(np.prod(f.shape[lead:])) == layout.frame_stride):
+                raise ValueError(f"{who}: expected a contiguous uint8 tensor of layout.frame_stride = {layout.frame_stride} bytes per "
+                                 f"frame after {lead} leading dimension(s), got "
+                                 f"{(f.dtype, tuple(f.shape), f.is_contiguous()) if torch.is_tensor(f) else type(f)}")
+            if not f.is_cuda:
+                raise ValueError(f"{who}: on {f.device}; they must be on the GPU (there is no CPU fallback)")
+            return f.view(-1, layout.frame_stride), tuple(f.shape[:lead]), layout.height, layout.width, self._surface(layout)
+        if fmt in ("nv12", "i420"):
+            return None
+        chan, dims = 2 if fmt in YUV422_FORMATS else PACKED_FORMATS[fmt][0], (4,) if lead == 1 else (4, 5)
+        if fmt == "rgb24":      # what today's entries take, and what they refuse in their own words
+            if not (torch.is_tensor(f) and f.is_cuda and f.dtype == torch.uint8 and f.dim() in dims
+                    and f.shape[-1] == 3 and min(f.shape) >= 1 and not f.is_contiguous()):
+                return None
+        elif not (torch.is_tensor(f) and f.dtype == torch.uint8 and f.dim() in dims and f.shape[-1] == chan):
+            raise ValueError(f"{who}: expected raw {fmt} frames as a uint8 tensor [{'B, L' if lead == 2 else 'M'}, H, W, {chan}], got "
+                             f"{(f.dtype, tuple(f.shape)) if torch.is_tensor(f) else type(f)}")
+        if f.dim() == 4 and lead == 2:
+            f = f.unsqueeze(0)
+        h, w = f.shape[-3], f.shape[-2]
+        if fmt in YUV422_FORMATS and w % 2:
+            raise ValueError(f"{who}: a 4:2:2 picture needs an even W, got {w}")
+        if min(f.shape[:-3]) and (h < 1 or w < 1):
+            raise ValueError(f"{who}: empty images {tuple(f.shape)}")
+        if not f.is_cuda:
+            raise ValueError(f"{who}: on {f.device}; they must be on the GPU (there is no CPU fallback)")
+        shape, flat = tuple(f.shape[:lead]), f.flatten(0, lead - 1)
+        if not flat.numel():
+            return flat, shape, h, w, None
+        try:
+            layout = SurfaceLayout.of_view(flat, fmt)
+        except ValueError:
+            if fmt == "rgb24":
+                return None
+            flat = flat.contiguous()
+            layout = SurfaceLayout.of_view(flat, fmt)
+        return flat, shape, h, w, self._surface(layout)
+
+    def _surface(self, layout):
+        """The ``Surface`` of a layout under this transform's conversion, kept per layout."""
+        if layout not in self._surfaces:
+            if len(self._surfaces) >= 64:
+                self._surfaces.clear()
+            self._surfaces[layout] = Surface(layout, self._coef)
+        return self._surfaces[layout]
+
     def _clip(self, frames):
-        """The clip as a contiguous [B, L, ...] tensor and (B, L, H, W) of its pictures."""
+        """The clip as a contiguous [B, L, ...] tensor, (B, L, H, W) of its pictures, and None -- or, for frames read in place
+        (``_source``), the frames as [B * L, ...] and the ``Surface`` they are read through."""
+        frames, layout = _unlaid(frames)
+        src = self._source(frames, layout, 2, "FrameTransform: frames")
+        if src is not None:
+            flat, (b, l), h, w, surface = src
+            return flat, b, l, h, w, surface
+        return (*self._clip_packed(frames), None)
+
+    def _clip_packed(self, frames):
         if self.yuv is not None:      # the shape is looked at first, then the device
             if not (torch.is_tensor(frames) and frames.dtype == torch.uint8 and frames.dim() in (3, 4)):
                 raise ValueError(f"FrameTransform: {self.pixel_format} frames are a uint8 tensor [B, L, H * 3 / 2, W], got "
@@ -432,6 +732,7 @@ class FrameTransform:
             raise RuntimeError("FrameTransform: frames must be RGB, channels last")
         return frames.contiguous(), b, l, h, w
 
+    @takes_layout("frames")
     def __call__(self, frames, crop_xyf=None, return_u8=False, boxes=None):
         clip = self._clip(frames)
         if boxes is None:
@@ -449,7 +750,7 @@ class FrameTransform:
         65535 frames.  ``table(rows)``: the checked host table that comes with the frames (boxes, affines), or None;
         ``how(H, W, device)``: what ``call`` takes between the frames (and their table) and ``size`` -- ``_plain``, the box
         store, the affine geometry; ``call``: the ``ops.frames_transform*`` that runs one chunk."""
-        frames, b, l, h, w = clip
+        frames, b, l, h, w, surface = clip
         if crop_xyf is None:
             crop_xyf = self.draw(b)
         crop_xyf = np.ascontiguousarray(crop_xyf, dtype=np.int32).reshape(b, 3)
@@ -464,14 +765,16 @@ class FrameTransform:
         out = torch.empty((b, l, 3, self.crop, self.crop), dtype=torch.float32, device=frames.device)
         u8 = torch.empty((b, l, self.crop, self.crop, 3), dtype=torch.uint8, device=frames.device) if return_u8 else None
         n, step = b * l, 65535 // l * l
-        flat_in, flat_out = frames.view(n, *frames.shape[2:]), out.view(n, 3, self.crop, self.crop)
+        flat_in = frames if surface is not None else frames.view(n, *frames.shape[2:])
+        flat_out = out.view(n, 3, self.crop, self.crop)
         flat_u8 = u8.view(n, self.crop, self.crop, 3) if return_u8 else None
         for s in range(0, n, step):
             e = min(n, s + step)
             call(flat_in[s:e], *([] if rows is None else [rows[s:e]]), *how, self.size, cx[s // l:e // l], l, self.mean, self.std,
-                 flat_out[s:e], flat_u8[s:e] if return_u8 else None, yuv=self.yuv)
+                 flat_out[s:e], flat_u8[s:e] if return_u8 else None, **({"yuv": self.yuv} if surface is None else {"surface": surface}))
         return (out, u8) if return_u8 else out
 
+    @takes_layout("frames")
     def aligned(self, frames, affines, crop_xyf=None, return_u8=False, align_size=ALIGN_SIZE):
         """``__call__`` of full camera frames with one affine map per frame: ``affines`` [B, L, 6] or [B * L, 6] host
         float64, Pillow's coefficients (``similarity_from_landmarks`` makes them from five landmarks).  Frame f is first
@@ -523,7 +826,11 @@ class FrameStream:
 
     ``pixel_format`` / ``matrix`` / ``range``: as for ``FrameTransform``.  Under ``"nv12"`` or ``"i420"`` a push brings
     uint8 [M, H * 3 / 2, W], H and W even; everything else is as under ``"rgb24"``, and so are the ring's bytes for the
-    converted frames.  The format is the stream's, not a push's.
+    converted frames.  The format is the stream's, not a push's.  ``"bgr24"``, ``"rgba32"``, ``"bgra32"`` [M, H, W, 3 | 4]
+    and ``"yuyv422"``, ``"uyvy422"`` [M, H, W, 2] are read in place, as ``FrameTransform`` reads them, and so is a strided
+    view of a packed format.  ``layout=`` on ``push``, ``push_aligned`` and their checks is the ``surface_layout`` of that
+    push's frames, a contiguous uint8 tensor [M, ...] of ``layout.frame_stride`` bytes per frame (a pitched or padded
+    surface); it belongs to the push, as H and W do, and its ``pixel_format`` must be the stream's.
 
     A push that would leave more than ``hold`` untaken frames in a stream, bad counts, and a tensor that is not uint8 RGB on
     the GPU (or not a 4:2:0 frame of an even-sized picture, under those formats) raise ValueError before any launch and leave
@@ -577,10 +884,12 @@ class FrameStream:
         for s in self._indices(streams):
             self.frames_seen[s] = self.frames_taken[s] = 0
 
+    @takes_layout("frames_u8")
     def check_push(self, frames_u8, counts, boxes=None):
         """Everything ``push`` refuses, without a launch or a change of state.  Returns the counts as ints."""
         return self._check_push(frames_u8, counts, self._box_rows(boxes))[0]
 
+    @takes_layout("frames_u8")
     def check_push_aligned(self, frames_u8, counts, affines, align_size=ALIGN_SIZE):
         """Everything ``push_aligned`` refuses, without a launch or a change of state.  Returns the counts as ints."""
         return self._check_push(frames_u8, counts, self._affine_rows(affines, align_size))[0]
@@ -597,7 +906,8 @@ class FrameStream:
 
     def _check_push(self, frames_u8, counts, table):
         """The checks of every kind of push; ``table(rows)`` checks the per-frame table that comes with the frames (None: there
-        is none).  Returns (the counts as ints, that table as ``table`` returns it)."""
+        is none).  Returns (the counts as ints, that table as ``table`` returns it, how the frames are read: None or what
+        ``FrameTransform._source`` returns)."""
         try:
             counts = [int(c) for c in counts]
         except TypeError:
@@ -610,8 +920,11 @@ class FrameStream:
             if self.held[s] + c > self.hold:
                 raise ValueError(f"stream {s}: {self.held[s]} frames wait and {c} more exceed hold = {self.hold}; take some first")
         rows = None if table is None else table(sum(counts))
-        f = frames_u8
-        if self._xf.yuv is not None:      # the shape is looked at first, then the device
+        f, layout = _unlaid(frames_u8)
+        src = self._xf._source(f, layout, 1)
+        if src is not None:
+            f = src[0]
+        elif self._xf.yuv is not None:      # the shape is looked at first, then the device
             if not (torch.is_tensor(f) and f.dtype == torch.uint8 and f.dim() == 3):
                 raise ValueError(f"frames: expected raw {self.pixel_format} frames as a uint8 tensor [M, H * 3 / 2, W], got "
                                  f"{(f.dtype, tuple(f.shape)) if torch.is_tensor(f) else type(f)}")
@@ -626,9 +939,9 @@ class FrameStream:
             raise ValueError(f"frames: {f.shape[0]} frames for counts that sum to {sum(counts)}")
         if f.shape[0] > 65535:
             raise ValueError(f"frames: {f.shape[0]} frames in one push exceed 65535")
-        if f.shape[0] and (f.shape[1] < 1 or f.shape[2] < 1):
+        if src is None and f.shape[0] and (f.shape[1] < 1 or f.shape[2] < 1):
             raise ValueError(f"frames: empty images {tuple(f.shape)}")
-        return counts, rows
+        return counts, rows, src
 
     def _alloc(self):
         if self.ring is None:
@@ -641,24 +954,31 @@ class FrameStream:
         """The body of every kind of push.  ``table``: as for ``_check_push``; ``how``: as for ``FrameTransform._run``;
         ``upload``: the ``ops.stream_row_*table`` that takes what ``table`` returns; ``append``: the
         ``ops.frames_stream_append*`` of the one launch."""
-        counts, rows = self._check_push(frames_u8, counts, table)
+        counts, rows, src = self._check_push(frames_u8, counts, table)
         if not sum(counts):
             return
-        frames, yuv = frames_u8.contiguous(), self._xf.yuv
-        h, w = frames.shape[1:3] if yuv is None else yuv_picture(frames.shape[1], frames.shape[2])
+        if src is not None:
+            frames, _, h, w, surface = src
+            read = {"surface": surface}
+        else:
+            frames, yuv = frames_u8.contiguous(), self._xf.yuv
+            h, w = frames.shape[1:3] if yuv is None else yuv_picture(frames.shape[1], frames.shape[2])
+            read = {"yuv": yuv}
         how = how(h, w, frames.device)
         self._alloc()
         first = [b + n for b, n in zip(self._base, self.frames_seen)]
         row_stream, row_pos, *rows = upload(first, counts, *([] if rows is None else [rows]), self.device)
-        append(frames, *rows, *how, self.size, self._cx, row_stream, row_pos, max(counts), self.ring, yuv=yuv)
+        append(frames, *rows, *how, self.size, self._cx, row_stream, row_pos, max(counts), self.ring, **read)
         self.frames_seen = [n + c for n, c in zip(self.frames_seen, counts)]
 
+    @takes_layout("frames_u8")
     def push(self, frames_u8, counts, boxes=None):
         if boxes is None:
             return self._push(frames_u8, counts, None, self._xf._plain, ops.stream_row_table, ops.frames_stream_append)
         return self._push(frames_u8, counts, self._box_rows(boxes), lambda *_: (box_tables(self.size, self.max_side),),
                           ops.stream_row_box_table, ops.frames_stream_append_boxes)
 
+    @takes_layout("frames_u8")
     def push_aligned(self, frames_u8, counts, affines, align_size=ALIGN_SIZE):
         """``push`` of full camera frames with one affine map per packed frame: ``affines`` [M, 6] host float64, Pillow's
         coefficients (``similarity_from_landmarks`` makes them from five landmarks).  Frame m is warped to an

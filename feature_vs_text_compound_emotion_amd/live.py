@@ -31,7 +31,7 @@ import torch
 
 from . import ops
 from .audio_stream import ROW_HOP, LogMelStream
-from .frames import FrameStream, hold_ring
+from .frames import FrameStream, hold_ring, takes_layout
 from .fusion_heads import CAN
 from .streaming import CANStream, LFANStream
 
@@ -95,7 +95,11 @@ class AVStream:
             ``video_boxes`` [M, 4] host integers: ``video`` holds full camera frames and frame m is cropped to its face box
             (x0, y0, x1, y1) first, as ``FrameStream.push(..., boxes=)`` does (sides up to ``max_side``).  A session built
             with ``video_format="nv12"`` or ``"i420"`` (and ``video_matrix``, ``video_range``: ``FrameStream``'s
-            ``pixel_format``, ``matrix``, ``range``) takes the decoder's 4:2:0 frames instead, uint8 [M, H * 3 / 2, W].
+            ``pixel_format``, ``matrix``, ``range``) takes the decoder's 4:2:0 frames instead, uint8 [M, H * 3 / 2, W]; with
+            ``"bgr24"``, ``"rgba32"``, ``"bgra32"``, ``"yuyv422"`` or ``"uyvy422"`` what a capture API hands out, [M, H, W, C].
+            ``video_layout=`` (keyword, on ``push_aligned`` too): the ``frames.surface_layout`` of this push's frames, a
+            pitched or padded surface read in place as ``FrameStream.push(..., layout=)`` reads it; a refused layout changes
+            no stage's state.
             -> (logits [P, n_cls], counts): every frame that became paired in this call, stream-major, each stream's frames in
             time order (the row order of ``push_ragged``); counts[s] of them belong to stream s.  Nothing paired: an empty
             [0, n_cls] and no model launch.
@@ -277,6 +281,7 @@ class AVStream:
         return (torch.cat(flat) if len(flat) > 1 else flat[0]) if flat else self.model_stream._nothing(), counts
 
     # ------------------------------------------------------------------------------------------------ the session
+    @takes_layout("video", "video_layout")
     @torch.no_grad()
     def push(self, video=None, video_counts=None, audio=None, audio_counts=None, extra=None, video_boxes=None):
         if video is None and video_counts is None and video_boxes is not None:
@@ -284,6 +289,7 @@ class AVStream:
         fs = self.frame_stream
         return self._push(video, video_counts, audio, audio_counts, extra, fs.check_push, fs.push, (video_boxes,))
 
+    @takes_layout("video", "video_layout")
     @torch.no_grad()
     def push_aligned(self, video, video_counts, video_affines, audio=None, audio_counts=None, extra=None, align_size=256):
         """``push`` of full camera frames with one affine map per frame: ``video_affines`` [M, 6] host float64, Pillow's

@@ -2131,16 +2131,47 @@ def _yuv_frames(frames, yuv, like):
     return (frames.shape[0], *yuv_picture(frames.shape[1], frames.shape[2]))
 
 
-def _yuv_entry(name, yuv):
-    """The C entry ``name`` or its ``_yuv`` sibling, and the arguments the sibling takes after ``frames``."""
+def _surface_frames(frames, surface, like):
+    """The check of frames read in place that the ``surface=`` forms of the frame wrappers share: ``surface`` a
+    ``frames.Surface``; ``frames`` uint8 on the GPU of ``like``, either contiguous [n >= 1, ...] with
+    ``surface.layout.frame_stride`` bytes per frame, or a strided view [n, H, W, C] of a packed format whose strides are that
+    layout (``SurfaceLayout.of_view``).  Returns (n, H, W, the bytes from the first one the kernel may read)."""
+    from .frames import Surface
+    if not isinstance(surface, Surface):
+        raise ValueError(f"surface: expected a frames.Surface, got {type(surface).__name__}")
+    lay = surface.layout
+    if not (torch.is_tensor(frames) and frames.is_cuda and frames.device == like.device and frames.dtype == torch.uint8
+            and frames.dim() >= 2 and frames.shape[0] >= 1):
+        raise ValueError(f"frames: expected a uint8 [n >= 1, ...] tensor on the GPU ({like.device}), got "
+                         f"{(frames.dtype, frames.device, tuple(frames.shape)) if torch.is_tensor(frames) else type(frames)}")
+    n = frames.shape[0]
+    if frames.is_contiguous() and frames.numel() == n * lay.frame_stride:
+        return n, lay.height, lay.width, frames.numel()
+    if lay.fits_view(frames):
+        return n, lay.height, lay.width, (n - 1) * lay.frame_stride + lay.extent
+    raise ValueError(f"frames: shape {tuple(frames.shape)} with strides {tuple(frames.stride())} is neither contiguous with "
+                     f"frame_stride = {lay.frame_stride} bytes per frame nor a view with the layout's strides")
+
+
+def _yuv_entry(name, yuv, surface=None, nbytes=0):
+    """The C entry ``name``, its ``_yuv`` sibling or its ``_surface`` sibling, and the arguments the sibling takes after
+    ``frames``."""
+    if surface is not None:
+        if yuv is not None:
+            raise ValueError("yuv and surface exclude each other: a surface carries its own conversion")
+        return getattr(_lib.load(), name + "_surface"), (ctypes.c_size_t(nbytes), ctypes.byref(surface.desc()))
     return (getattr(_lib.load(), name), ()) if yuv is None else (getattr(_lib.load(), name + "_yuv"), (ctypes.byref(yuv),))
 
 
-def _frames_in(frames, like, yuv, rows=None):
+def _frames_in(frames, like, yuv, rows=None, surface=None):
     """The check of packed input frames that every frame wrapper shares: ``frames`` contiguous uint8 [n >= 1, H, W, 3] on
-    the GPU of ``like`` (the ring or ``out``), or 4:2:0 frames under ``yuv`` (``_yuv_frames``); ``rows``: the n that ``out``
-    has room for.  Returns (n, H, W)."""
-    if yuv is not None:
+    the GPU of ``like`` (the ring or ``out``), 4:2:0 frames under ``yuv`` (``_yuv_frames``), or frames read in place under
+    ``surface`` (``_surface_frames``); ``rows``: the n that ``out`` has room for.  Returns (n, H, W, the extent in bytes that
+    only the surface entries ask for)."""
+    nbytes = 0
+    if surface is not None:
+        n, h, w, nbytes = _surface_frames(frames, surface, like)
+    elif yuv is not None:
         n, h, w = _yuv_frames(frames, yuv, like)
     elif not (torch.is_tensor(frames) and frames.is_cuda and frames.device == like.device and frames.dtype == torch.uint8
               and frames.is_contiguous() and frames.dim() == 4 and frames.shape[0] >= 1 and frames.shape[3] == 3):
@@ -2150,7 +2181,7 @@ def _frames_in(frames, like, yuv, rows=None):
         n, h, w, _ = frames.shape
     if rows is not None and rows != n:
         raise ValueError(f"frames: {n} frames for the {rows} rows of out")
-    return n, h, w
+    return n, h, w, nbytes
 
 
 def _clip_out(out, out_u8, crop_xyf, frames_per_group):
@@ -2181,20 +2212,22 @@ def _resample_tables(tables, size, like):
     return hb, hk, vb, vk
 
 
-def frames_stream_append(frames, tables, span, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None):
+def frames_stream_append(frames, tables, span, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None, surface=None):
     """GroupScale(size) -> crop -> flip of the raw frames ``frames`` [n, H, W, 3] uint8 into the ring ``u8ring``
     [S, Rf, crop, crop, 3]: row m of the row table (``stream_row_table``) is frame m and lands in slot
     (row_stream[m], row_pos[m] % Rf).  ``tables``: (hbounds, hcoef, vbounds, vcoef) of ``frames.resample_tables`` for
     (W -> size, H -> size) as int32 GPU tensors; ``span``: the most input rows one band of output rows needs;
     ``crop_xyf`` int32 [S, 3]: (x1, y1, flip) per stream; ``max_count``: the most rows any one stream has in the table.
     The bytes are ``return_u8`` of ``FrameTransform`` for the same frame and crop entry.  ``yuv``: ``frames`` are 4:2:0
-    frames [n, H * 3 / 2, W] (``_yuv_frames``), converted where the kernel reads them; the tables stay those of H and W."""
+    frames [n, H * 3 / 2, W] (``_yuv_frames``), converted where the kernel reads them; the tables stay those of H and W.
+    ``surface``: a ``frames.Surface`` -- ``frames`` are read in place in its layout's byte order, pitches and offsets
+    (``_surface_frames``; a strided view is accepted), with the same result as the RGB call on the converted frames."""
     s, rf, crop = _u8_ring(u8ring)
-    n, h, w = _frames_in(frames, u8ring, yuv)
+    n, h, w, nbytes = _frames_in(frames, u8ring, yuv, None, surface)
     m = _row_table(row_stream, row_pos, u8ring)
     hb, hk, vb, vk = _resample_tables(tables, size, u8ring)
     _i32_table(crop_xyf, "crop_xyf", (s, 3), u8ring)
-    entry, how = _yuv_entry("cer_frames_stream_append", yuv)
+    entry, how = _yuv_entry("cer_frames_stream_append", yuv, surface, nbytes)
     check(entry(ptr(frames), *how, n, h, w, ptr(hb), ptr(hk), hk.shape[1], ptr(vb), ptr(vk), vk.shape[1], int(size), crop,
                 ptr(crop_xyf), int(span), ptr(row_stream), ptr(row_pos), m, int(max_count), ptr(u8ring), s, rf, current_stream()),
           entry.__name__)
@@ -2202,15 +2235,15 @@ def frames_stream_append(frames, tables, span, size, crop_xyf, row_stream, row_p
         STREAM_TRACE.append(("frames_append", 0))
 
 
-def frames_transform(frames, tables, span, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None, yuv=None):
+def frames_transform(frames, tables, span, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None, yuv=None, surface=None):
     """GroupScale(size) -> crop -> flip -> ToTensor -> Normalize of the raw frames ``frames`` [n, H, W, 3] uint8 into ``out``
     [n, 3, crop, crop] float32 (and ``out_u8`` [n, crop, crop, 3]), the clip form of ``frames_stream_append``: ``tables`` and
     ``span`` as there; ``crop_xyf`` int32 [groups, 3] on the GPU, one (x1, y1, flip) per ``frames_per_group`` frames.
-    ``yuv``: as there."""
+    ``yuv``, ``surface``: as there."""
     n, crop, g = _clip_out(out, out_u8, crop_xyf, frames_per_group)
-    h, w = _frames_in(frames, out, yuv, n)[1:]
+    _, h, w, nbytes = _frames_in(frames, out, yuv, n, surface)
     hb, hk, vb, vk = _resample_tables(tables, size, out)
-    entry, how = _yuv_entry("cer_frames_transform", yuv)
+    entry, how = _yuv_entry("cer_frames_transform", yuv, surface, nbytes)
     check(entry(ptr(frames), *how, n, h, w, ptr(hb), ptr(hk), hk.shape[1], ptr(vb), ptr(vk), vk.shape[1], int(size), crop,
                 ptr(crop_xyf), g, int(span), float(mean), float(std), ptr(out), ptr(out_u8), current_stream()), entry.__name__)
 
@@ -2234,66 +2267,67 @@ def stream_row_affine_table(positions, counts, affines, device):
     return row_stream, row_pos, words.view(torch.float64).view(-1, 6)
 
 
-def _transform_rows(frames, rows, geom, size, crop_xyf, frames_per_group, mean, std, out, out_u8, yuv):
+def _transform_rows(frames, rows, geom, size, crop_xyf, frames_per_group, mean, std, out, out_u8, yuv, surface):
     """The clip call of a per-frame table: ``frames_transform_boxes`` / ``frames_transform_affine``."""
     n, crop, g = _clip_out(out, out_u8, crop_xyf, frames_per_group)
-    h, w = _frames_in(frames, out, yuv, n)[1:]
+    _, h, w, nbytes = _frames_in(frames, out, yuv, n, surface)
     geom.check_rows(rows, n, size, crop, out)
     a, b, *ints = geom.entry_args(out.device)
-    entry, how = _yuv_entry("cer_frames_transform_" + geom.stem, yuv)
+    entry, how = _yuv_entry("cer_frames_transform_" + geom.stem, yuv, surface, nbytes)
     check(entry(ptr(frames), *how, n, h, w, ptr(rows), ptr(a), ptr(b), *ints, int(size), crop, ptr(crop_xyf), g, float(mean),
                 float(std), ptr(out), ptr(out_u8), current_stream()), entry.__name__)
 
 
-def _append_rows(frames, rows, geom, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv):
+def _append_rows(frames, rows, geom, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv, surface):
     """The ring call of a per-frame table: ``frames_stream_append_boxes`` / ``frames_stream_append_affine``."""
     s, rf, crop = _u8_ring(u8ring)
-    n, h, w = _frames_in(frames, u8ring, yuv)
+    n, h, w, nbytes = _frames_in(frames, u8ring, yuv, None, surface)
     m = _row_table(row_stream, row_pos, u8ring)
     geom.check_rows(rows, m, size, crop, u8ring)
     _i32_table(crop_xyf, "crop_xyf", (s, 3), u8ring)
     a, b, *ints = geom.entry_args(u8ring.device)
-    entry, how = _yuv_entry("cer_frames_stream_append_" + geom.stem, yuv)
+    entry, how = _yuv_entry("cer_frames_stream_append_" + geom.stem, yuv, surface, nbytes)
     check(entry(ptr(frames), *how, n, h, w, ptr(rows), ptr(a), ptr(b), *ints, int(size), crop, ptr(crop_xyf), ptr(row_stream),
                 ptr(row_pos), m, int(max_count), ptr(u8ring), s, rf, current_stream()), entry.__name__)
     if STREAM_TRACE is not None:
         STREAM_TRACE.append(("frames_append_" + geom.stem, 0))
 
 
-def frames_transform_boxes(frames, boxes, store, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None, yuv=None):
+def frames_transform_boxes(frames, boxes, store, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None, yuv=None, surface=None):
     """``Image.crop(boxes[f])`` -> GroupScale(size) -> crop -> flip -> ToTensor -> Normalize of full frames ``frames``
     [n, H, W, 3] uint8 into ``out`` [n, 3, crop, crop] float32 (and ``out_u8`` [n, crop, crop, 3]).  ``boxes`` int32 [n, 4]
     on the GPU = (x0, y0, x1, y1), right and lower exclusive, zero outside the frame; the kernel clamps what it is given
     (coordinates into +-2^20, sides into 1 .. ``store.max_side``), so a table nobody vetted gives wrong numbers and no
     access outside ``frames``.  ``store``: ``frames.box_tables(size, max_side)``; ``crop_xyf`` int32 [groups, 3] on the GPU,
     one entry per ``frames_per_group`` frames.  ``yuv``: ``frames`` are 4:2:0 frames [n, H * 3 / 2, W] (``_yuv_frames``); the
-    boxes stay in luma pixels and what lies outside the picture is RGB 0."""
-    _transform_rows(frames, boxes, store, size, crop_xyf, frames_per_group, mean, std, out, out_u8, yuv)
+    boxes stay in luma pixels and what lies outside the picture is RGB 0.  ``surface``: as in ``frames_stream_append``."""
+    _transform_rows(frames, boxes, store, size, crop_xyf, frames_per_group, mean, std, out, out_u8, yuv, surface)
 
 
-def frames_stream_append_boxes(frames, boxes, store, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None):
+def frames_stream_append_boxes(frames, boxes, store, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None, surface=None):
     """``frames_stream_append`` of full frames with one box per row: row m of the row table is packed frame m, cropped to
     ``boxes[m]`` as ``frames_transform_boxes`` does, and lands in slot (row_stream[m], row_pos[m] % Rf).  The bytes are
-    ``return_u8`` of ``FrameTransform(..., boxes=)`` for the same frame, box and crop entry.  ``yuv``: as there."""
-    _append_rows(frames, boxes, store, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv)
+    ``return_u8`` of ``FrameTransform(..., boxes=)`` for the same frame, box and crop entry.  ``yuv``, ``surface``: as there."""
+    _append_rows(frames, boxes, store, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv, surface)
 
 
-def frames_transform_affine(frames, affines, geom, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None, yuv=None):
+def frames_transform_affine(frames, affines, geom, size, crop_xyf, frames_per_group, mean, std, out, out_u8=None, yuv=None, surface=None):
     """``Image.transform((A, A), AFFINE, affines[f], BILINEAR)`` -> GroupScale(size) -> crop -> flip -> ToTensor -> Normalize
     of full frames ``frames`` [n, H, W, 3] uint8 into ``out`` [n, 3, crop, crop] float32 (and ``out_u8`` [n, crop, crop, 3]).
     ``affines`` float64 [n, 6] on the GPU, Pillow's coefficients (output pixel centre -> frame coordinate); the kernel only
     compares and multiplies them and fetches every pixel at a clamped index, so a table nobody vetted -- NaN, infinities,
     1e300 -- gives the all-zero picture and no access outside ``frames``.  ``geom``: ``frames.affine_geometry(A, size)``;
     ``crop_xyf`` int32 [groups, 3] on the GPU, one entry per ``frames_per_group`` frames.  ``yuv``: ``frames`` are 4:2:0
-    frames [n, H * 3 / 2, W] (``_yuv_frames``); the four pixels of a sample are converted, then interpolated."""
-    _transform_rows(frames, affines, geom, size, crop_xyf, frames_per_group, mean, std, out, out_u8, yuv)
+    frames [n, H * 3 / 2, W] (``_yuv_frames``); the four pixels of a sample are converted, then interpolated.  ``surface``: as
+    in ``frames_stream_append``."""
+    _transform_rows(frames, affines, geom, size, crop_xyf, frames_per_group, mean, std, out, out_u8, yuv, surface)
 
 
-def frames_stream_append_affine(frames, affines, geom, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None):
+def frames_stream_append_affine(frames, affines, geom, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv=None, surface=None):
     """``frames_stream_append`` of full frames with one affine per row: row m of the row table is packed frame m, warped by
     ``affines[m]`` as ``frames_transform_affine`` does, and lands in slot (row_stream[m], row_pos[m] % Rf).  The bytes are
-    ``return_u8`` of ``FrameTransform.aligned`` for the same frame, affine and crop entry.  ``yuv``: as there."""
-    _append_rows(frames, affines, geom, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv)
+    ``return_u8`` of ``FrameTransform.aligned`` for the same frame, affine and crop entry.  ``yuv``, ``surface``: as there."""
+    _append_rows(frames, affines, geom, size, crop_xyf, row_stream, row_pos, max_count, u8ring, yuv, surface)
 
 
 def frames_stream_gather(u8ring, row_stream, row_pos, mean=0.5, std=0.5):

@@ -962,6 +962,88 @@ int cer_frames_stream_append_affine_yuv(const uint8_t *frames, const cer_yuv420 
                                         uint8_t *u8ring, int S, int Rf, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Surfaces: frames read in place, in the byte order and with the row pitch a capture API or a decoder hands them out.
+ *
+ * A cer_surface says where the three bytes of pixel (x, y) of an H x W picture lie in frame m of `frames`.  With
+ * base = frames + m * frame_stride, xs = x >> xshift, ys = y >> yshift:
+ *   a = base[offset[0] + y  * pitch[0] + x  * step[0] + pos[0]]
+ *   b = base[offset[1] + ys * pitch[1] + xs * step[1] + pos[1]]
+ *   c = base[offset[2] + ys * pitch[1] + xs * step[1] + pos[2]]
+ * and the format fixes the shifts and says what (a, b, c) are:
+ *   CER_SURFACE_PACKED   (R, G, B) themselves; no shifts.  step[0] == step[1] = 3 or 4 bytes per pixel, pos[] = the byte of
+ *                        R, G, B inside a pixel (BGR: 2 1 0; RGBA: 0 1 2; BGRA: 2 1 0), the three offsets and the two pitches
+ *                        equal.  A fourth byte is never loaded.
+ *   CER_SURFACE_YUV420   (Y, U, V), xshift = yshift = 1: a luma plane and chroma at half resolution.  step[0] = 1, pos[] = 0;
+ *                        step[1] = 2 for interleaved chroma (NV12: offset[2] = offset[1] + 1; NV21: offset[1] = offset[2] + 1),
+ *                        1 for planes (I420: the U plane first; YV12: the V plane first).  No layout needs a format of its own.
+ *   CER_SURFACE_YUV422   (Y, U, V), xshift = 1, yshift = 0: one plane of 4-byte pairs.  step[0] = 2, step[1] = 4;
+ *                        YUYV: pos = 0 1 3; UYVY: pos = 1 0 2; the three offsets and the two pitches equal.
+ * (Y, U, V) become RGB through the expression of cer_yuv420 above, with this descriptor's cy .. yoff; PACKED ignores them
+ * but they are checked all the same.  Nothing has to be aligned and planes may overlap: they are only read.
+ *
+ * The six _surface entries are their RGB siblings with `frames_bytes`, the extent of `frames` the caller vouches for, and a
+ * cer_surface after `frames`; H and W stay the picture's, boxes stay in picture pixels.  Only the pixel fetch differs, so
+ * each gives the bits its sibling gives the converted, tightly packed RGB frames; what lies outside the picture is RGB 0.
+ *
+ * The descriptor is checked, not trusted.  Refused before any launch, with the entry's name at the head of cer_last_error()
+ * (CER_ERR_INVALID_ARG): a null descriptor; an unknown format; a coefficient beyond +-2^20 or yoff outside 0 .. 255; steps,
+ * positions, offsets or pitches that are not one of the patterns above; odd W (YUV422), odd H or W (YUV420); a picture
+ * above 2^29 pixels; a negative offset, pitch or stride, or one of 2^40 or more; a pitch below the bytes of a row (W * step[0]
+ * for plane 0, W / 2 * step[1] for 4:2:0 chroma); a plane whose last row ends past frame_stride; and
+ * (n_frames - 1) * frame_stride plus the used extent of a frame -- the largest end of a plane -- above frames_bytes, in
+ * arithmetic that cannot wrap (comparisons and one division of non-negative 64-bit values).  Then what the sibling refuses.
+ * After that check the kernels form a pixel address from a frame index below n_frames, 0 <= y < H and 0 <= x < W only (the
+ * clamped indices the siblings use): it is at least frames, and at most frames + (n_frames - 1) * frame_stride + the end of
+ * its plane - 1 < frames + frames_bytes.  So every load lies in [frames, frames + frames_bytes), and the box, affine and row
+ * tables are trusted exactly as little as by the siblings.
+ * ---------------------------------------------------------------------- */
+#define CER_SURFACE_PACKED 0
+#define CER_SURFACE_YUV420 1
+#define CER_SURFACE_YUV422 2
+
+typedef struct cer_surface {
+    int32_t format;                  /* CER_SURFACE_PACKED, CER_SURFACE_YUV420 or CER_SURFACE_YUV422 */
+    int32_t cy, crv, cgu, cgv, cbu;  /* as in cer_yuv420 */
+    int32_t yoff;
+    int32_t step[2];                 /* bytes from one sample to the next in a row: of a, and of b and c */
+    int32_t pos[3];                  /* byte of a, b, c inside its sample */
+    int64_t frame_stride;            /* bytes from frame m to frame m + 1 */
+    int64_t pitch[2];                /* bytes from one row to the next: of a, and of b and c */
+    int64_t offset[3];               /* byte offset of the planes of a, b, c inside a frame */
+} cer_surface;
+
+int cer_frames_transform_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface, int n_frames, int H,
+                                 int W, const int32_t *hbounds, const int32_t *hcoef, int hksize, const int32_t *vbounds,
+                                 const int32_t *vcoef, int vksize, int size, int crop, const int32_t *crop_xyf,
+                                 int frames_per_group, int max_band_rows, float mean, float stdv, float *out, uint8_t *out_u8,
+                                 void *stream);
+int cer_frames_stream_append_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface, int n_frames, int H,
+                                     int W, const int32_t *hbounds, const int32_t *hcoef, int hksize, const int32_t *vbounds,
+                                     const int32_t *vcoef, int vksize, int size, int crop, const int32_t *crop_xyf,
+                                     int max_band_rows, const int32_t *row_stream, const int32_t *row_pos, int num_rows,
+                                     int max_count, uint8_t *u8ring, int S, int Rf, void *stream);
+int cer_frames_transform_boxes_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface, int n_frames,
+                                       int H, int W, const int32_t *boxes, const int32_t *box_meta, const int32_t *box_data,
+                                       int max_side, int max_band_rows, int max_ksize, int size, int crop,
+                                       const int32_t *crop_xyf, int frames_per_group, float mean, float stdv, float *out,
+                                       uint8_t *out_u8, void *stream);
+int cer_frames_stream_append_boxes_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface, int n_frames,
+                                           int H, int W, const int32_t *boxes, const int32_t *box_meta, const int32_t *box_data,
+                                           int max_side, int max_band_rows, int max_ksize, int size, int crop,
+                                           const int32_t *crop_xyf, const int32_t *row_stream, const int32_t *row_pos,
+                                           int num_rows, int max_count, uint8_t *u8ring, int S, int Rf, void *stream);
+int cer_frames_transform_affine_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface, int n_frames,
+                                        int H, int W, const double *affines, const int32_t *bounds, const int32_t *coef,
+                                        int ksize, int align_size, int max_band_rows, int size, int crop,
+                                        const int32_t *crop_xyf, int frames_per_group, float mean, float stdv, float *out,
+                                        uint8_t *out_u8, void *stream);
+int cer_frames_stream_append_affine_surface(const uint8_t *frames, size_t frames_bytes, const cer_surface *surface, int n_frames,
+                                            int H, int W, const double *affines, const int32_t *bounds, const int32_t *coef,
+                                            int ksize, int align_size, int max_band_rows, int size, int crop,
+                                            const int32_t *crop_xyf, const int32_t *row_stream, const int32_t *row_pos,
+                                            int num_rows, int max_count, uint8_t *u8ring, int S, int Rf, void *stream);
+
+/* ------------------------------------------------------------------------
  * Running video-level decisions of S live streams (csrc/decision_stream.hip): logit rows in, the three decisions of
  * metrics.py:118-139 out -- majority vote over the frame predictions, argmax of the mean logits, argmax of the mean softmax
  * probabilities -- over the first nc = C - (drop_last ? 1 : 0) columns.
