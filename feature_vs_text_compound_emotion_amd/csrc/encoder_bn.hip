@@ -440,7 +440,7 @@ static int bn_apply_launch(const float *y, const float *scale, const float *shif
                            int Wo, int C, int res_stride, int Hr, int Wr, void *stream) {
     if (!y || !scale || !shift || (!out && !out_hi) || N <= 0 || Ho <= 0 || Wo <= 0 || C < 4 || C > 1024 || (C & 3) ||
         (256 % (C / 4)) != 0)
-        return cer_set_error(CER_ERR_INVALID_ARG, "bn_apply_nhwc: C must be 16..1024 with C/4 dividing 256");
+        return cer_set_error(CER_ERR_INVALID_ARG, "bn_apply_nhwc: C must be 4..1024 with C/4 dividing 256");
     if ((long long)N * Ho * Wo >= (1ll << 31)) return cer_set_error(CER_ERR_UNSUPPORTED, "bn_apply_nhwc: too many pixels");
     if ((res_hi == nullptr) != (res_lo == nullptr) || (out_hi == nullptr) != (out_lo == nullptr) || (res && res_hi))
         return cer_set_error(CER_ERR_INVALID_ARG, "bn_apply_nhwc: split tensors need both planes; residual is fp32 OR split");

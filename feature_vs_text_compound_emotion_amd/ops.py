@@ -468,11 +468,14 @@ def conv2d_n16(x, w, kh, kw, *, stride=1, dil=(1, 1), pad=(0, 0), out_hw=None, b
 
 
 def _bn_apply_args(y, scale, shift, alpha, res, res_scale, res_shift, mask, split=False, n16=None):
-    """What the three ``bn_apply`` wrappers check alike: the (C,) vectors and the mask; returns ``_res_kind(res)``."""
-    c = y.shape[3]
+    """What the three ``bn_apply`` wrappers check alike: the (C,) vectors, the mask and that the residual has the images and
+    channels of ``y`` (the kernel indexes it with both); returns ``_res_kind(res)``."""
+    n, c = y.shape[0], y.shape[3]
     for t, nme in ((scale, "scale"), (shift, "shift"), (alpha, "alpha"), (res_scale, "res_scale"), (res_shift, "res_shift")):
         _dev_f32(t, nme, shape=(c,))
     _dev_mask(mask, y)
+    if res is not None and (len(res.shape) != 4 or res.shape[0] != n or res.shape[3] != c):
+        raise ValueError(f"res shape {tuple(res.shape)} does not match N={n}, C={c}")
     return _res_kind(res, "res", split, n16)
 
 
@@ -666,7 +669,11 @@ def bn_finalize(partials, count, gamma, beta, running_mean=None, running_var=Non
     """[tiles,2,C] partial sums -> (scale, shift) of the batch-statistics BatchNorm; running stats
     are updated in place like torch does in train mode."""
     _dev_f32(partials, "partials")
+    if partials.dim() != 3 or partials.shape[1] != 2 or partials.shape[0] == 0 or partials.shape[2] == 0:
+        raise ValueError(f"partials: expected a [tiles, 2, C] tensor, got shape {tuple(partials.shape)}")
     tiles, _, c = partials.shape
+    for t, n in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _dev_f32(t, n, shape=(c,))
     scale, shift = _empty((c,), partials), _empty((c,), partials)
     lib = _lib.load()
     nbytes = lib.cer_bn_finalize_workspace_bytes(tiles, c)

@@ -13,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 import nonfinite_ref as nf
+from encoder_bn_ref import bn_apply_ref as _bn_apply_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -460,16 +461,6 @@ def _bn_apply_setup(dtype=None):
     bad = y.clone()
     bad.view(-1, c)[BN_APPLY_ROW] = nf.tiled_specials(c)
     return y, bad, res, scale, shift, alpha, rs, rt, mask
-
-
-def _bn_apply_ref(y, res, scale, shift, alpha, rs, rt, mask):
-    """(the float64 restatement rounded once to float32, the float32 error bound of its finite values): the kernel makes seven
-    roundings (y * scale + shift, the PReLU product, the mask product, res * rs + rt, the sum), each at most 2^-24 of a
-    magnitude that |mask| (|y| |scale| + |shift|) + |res| |rs| + |rt| bounds; 8 of them, plus the smallest denormal."""
-    v = y.double() * scale.double() + shift.double()
-    v = nf.prelu(v, alpha.double()) * mask.double()
-    mag = mask.double().abs() * (y.double().abs() * scale.double() + shift.double().abs()) + res.double().abs() * rs.double() + rt.double().abs()
-    return (v + (res.double() * rs.double() + rt.double())).float(), 8 * 2.0 ** -24 * mag + 2.0 ** -149
 
 
 def _check_bn_apply(run, ref_and_bound, what):
