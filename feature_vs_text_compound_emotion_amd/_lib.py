@@ -152,6 +152,7 @@ _SIGNATURES = {
     "cer_attention_bwd": (c_int, [_P] * 11 + [c_int] * 5 + [_P] * 8 + [c_float, _P]),
     "cer_window_stitch": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "cer_window_stitch_multi": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "cer_window_stitch_stream": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P]),
     "cer_eval_accumulate": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
     "cer_tanh_fwd": (c_int, [_P, _P, c_size_t, _P]),
     "cer_tanh_bwd": (c_int, [_P, _P, _P, c_size_t, _P]),

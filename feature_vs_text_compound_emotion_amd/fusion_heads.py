@@ -344,7 +344,6 @@ class _TailModel(nn.Module):
             self.dropout_seed += 1
         feats, bsz, length = {}, None, None
         for m in X:
-            i = self.modalities.index(m)               # dropout streams are tied to the model's modality order
             x = X[m]
             if m == "video":
                 bsz, length = x.shape[0], x.shape[1]
@@ -366,9 +365,19 @@ class _TailModel(nn.Module):
             else:
                 bsz, length = x.shape[0], x.shape[2]
                 rows = x.reshape(bsz * length, x.shape[-1])
-            t = self.temporal[m].forward_rows(rows, bsz, length, seed=self.dropout_seed * 16 + i)
-            feats[m] = batchnorm_rows(t, self.bn[m], self.training, self.bn_sync or LOCAL)
+            feats[m] = self._temporal_rows(m, rows, bsz, length)
         return feats, bsz, length
+
+    def _temporal_rows(self, m, rows, bsz, length):
+        """Modality m behind its encoder: rows [B * L, embedding dim] -> TCN (each of the B sequences from zero padding) ->
+        BatchNorm1d.  Dropout streams are tied to the model's modality order."""
+        t = self.temporal[m].forward_rows(rows, bsz, length, seed=self.dropout_seed * 16 + self.modalities.index(m))
+        return batchnorm_rows(t, self.bn[m], self.training, self.bn_sync or LOCAL)
+
+    def forward_rows(self, rows_in, bsz, length):
+        """``forward`` behind the encoders: ``rows_in[m]`` [B * L, embedding dim of m] (b-major rows), walked in the dict's own
+        key order like ``forward`` walks the caller's -> outputs [B, L, n_out]."""
+        return self._fuse_head({m: self._temporal_rows(m, rows, bsz, length) for m, rows in rows_in.items()}, bsz, length)
 
     def _head(self, c, bsz, length):
         c = linear(c, self.fc1)
@@ -400,6 +409,9 @@ class JMT(_TailModel):
 
     def forward(self, X):
         feats, bsz, length = self._front(X)
+        return self._fuse_head(feats, bsz, length)
+
+    def _fuse_head(self, feats, bsz, length):
         c = self.fuse.forward_rows(feats["video"], feats["vggish"], bsz, length)
         return self._head(c, bsz, length)
 
@@ -437,5 +449,8 @@ class CAN(_TailModel):
         feats, bsz, length = self._front(X)
         # model.py:558-560 pairs attn[i] with the i-th VALUE of the caller's dict: the caller's key order is part of the
         # contract here (another order meets other projection weights, or a shape error), exactly as in the reference
+        return self._fuse_head(feats, bsz, length)
+
+    def _fuse_head(self, feats, bsz, length):
         c = self.fuse.forward_rows(list(feats.values()))
         return self._head(c, bsz, length)

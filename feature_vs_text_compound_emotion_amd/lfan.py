@@ -270,7 +270,6 @@ class LFAN(nn.Module):
         for m in self.modality:
             if m not in X:
                 raise KeyError(m)                       # x[modal] in the fusion, transformer.py:137
-        mods = list(self.modality)
         if "visual" in self.spatial:
             self.spatial["visual"].backbone.check_sync_release()
         masks = self.test_masks or {}
@@ -301,6 +300,16 @@ class LFAN(nn.Module):
                 rows_in[m] = x.reshape(bsz * length, x.shape[-1])  # [B,1,L,C] -> rows
         if length != self.example_length:
             raise ValueError(f"clip length {length} != example_length {self.example_length} (model.py:521)")
+        out, feats = self.forward_rows(rows_in, bsz, length, masks)
+        for m, y in feats.items():                      # the reference's in-place dict updates (model.py:511-515)
+            X[m] = y.view(bsz, length, -1)
+        return out
+
+    def forward_rows(self, rows_in, bsz, length, masks=None):
+        """``forward`` behind the encoders: ``rows_in[m]`` [B * L, embedding_dim[m]] (b-major rows) for every modality of the
+        model -> (outputs [B, L, n_cls], {m: the BatchNorm output rows of m}).  ``length`` need not be ``example_length``:
+        every stage works on rows, and the TCN pads each of the B sequences with zeros on the left."""
+        mods, masks = list(self.modality), masks or {}
         t = []
         for i, m in enumerate(mods):
             t.append(self.temporal[m].forward_rows(rows_in[m], bsz, length, masks=(masks.get("tcn") or {}).get(m),
@@ -326,10 +335,8 @@ class LFAN(nn.Module):
         if self.training:
             for m in mods:
                 self.bn[m].num_batches_tracked += 1
-        for m, y in zip(mods, sink):                    # the reference's in-place dict updates (model.py:511-515)
-            X[m] = y.view(bsz, length, -1)
-        out = logits.view(bsz, self.example_length, -1)
+        out = logits.view(bsz, length, -1)
         if self.task == REGRESSION:
             from .fusion_heads import TanhFn   # fusion_heads imports this module
             out = TanhFn.apply(out)
-        return out
+        return out, dict(zip(mods, sink))

@@ -32,7 +32,8 @@ import torch
 from . import ops
 from .audio_stream import ROW_HOP, LogMelStream
 from .frames import FrameStream, hold_ring, takes_layout
-from .fusion_heads import CAN
+from .fusion_heads import CAN, JMT
+from .lfan import LFAN
 from .streaming import CANStream, LFANStream
 
 AUDIO_KEYS = ("logmel", "vggish")
@@ -113,7 +114,7 @@ class AVStream:
       reset(streams=None)    forget those streams.
       push_text(sentences, upto=None)   with ``text=``: finished sentences with their frame spans, as ``TextStream.push`` takes
             them -> (logits, counts) like ``push``: text arriving can release frames that were waiting for it.
-      frames_seen, examples_seen, paired   host lists, one int per stream; with ``text=`` also text_seen.
+      frames_seen, examples_seen, paired, emitted   host lists, one int per stream; with ``text=`` also text_seen.
       decisions              with ``decisions=`` (a dict of ``DecisionStream`` keyword arguments, ``{}`` for the defaults): a
             ``DecisionStream`` the session owns and feeds every logit row it emits, in ``push`` and in ``finish``;
             ``av.decisions.decide()`` gives the running video-level decisions.  ``finish`` leaves a stream's decisions
@@ -136,20 +137,35 @@ class AVStream:
     slots, 25 MB per stream, at hold = 512).  ``finish`` advances the stream's text to its last frame with zero rows first.
     Tokenisation and speech recognition are the caller's, and spans are frame numbers.
 
+    The window rule.  ``window=(window_length, hop_length)`` makes the model stage a ``WindowStream`` (window_stream.py): the
+    session then takes an LFAN, a CAN, a JMT or an MT, and a paired frame's logits come out once ``window_length`` more paired
+    frames of its stream have followed it (the evaluator's windows, overlaps averaged); ``finish`` flushes the stream's tail
+    window after its last pairs.  ``push`` / ``push_text`` / ``finish`` return the rows emitted and their counts, ``decisions``
+    receives exactly those rows, ``paired`` keeps its meaning (frames handed to the model) and ``emitted`` counts the rows that
+    came out.  Without ``window=`` every paired frame is emitted at once and ``emitted`` equals ``paired``.
+
     A push that would let more than ``hold`` frames or ``lead`` examples wait, and any argument one of the stages refuses,
     raises ValueError before any launch and changes no state, the stages' included.  A stream's counts above ``max_new`` in one
     call reach the model in several pushes, in time order."""
 
     def __init__(self, model, streams, fps, *, sample_rate=16000, channels=1, resample=None, size=48, crop=40, hold=64, lead=8,
                  max_new=32, max_samples=4096, encoder_batch=8, audio_backbone=None, decisions=None,
-                 max_side=1024, video_format="rgb24", video_matrix="bt601", video_range="limited", text=None):
+                 max_side=1024, video_format="rgb24", video_matrix="bt601", video_range="limited", text=None, window=None):
         cls = CANStream if isinstance(model, CAN) else LFANStream
-        if not isinstance(model, cls._model_class):
+        if window is not None:
+            from .window_stream import WindowStream
+            try:
+                window_length, hop_length = (int(v) for v in window)
+            except (TypeError, ValueError):
+                raise ValueError(f"window: expected (window_length, hop_length), got {window!r}") from None
+            if not isinstance(model, (LFAN, CAN, JMT)):
+                raise TypeError(f"AVStream(window=) needs an LFAN, a CAN, a JMT or an MT, got {type(model).__name__}")
+        elif not isinstance(model, cls._model_class):
             raise TypeError(f"AVStream needs an LFAN or a CAN (JMT / MT attend over time and are not causal), got "
                             f"{type(model).__name__}")
         if model.training:
             raise RuntimeError("AVStream: the model is in train mode; batch statistics are undefined frame by frame -- call .eval()")
-        mods = list(cls._modalities(model))
+        mods = list(model.modality if isinstance(model, LFAN) else model.modalities)
         audio_keys = [m for m in mods if m in AUDIO_KEYS]
         if "video" not in mods or len(audio_keys) != 1:
             raise ValueError(f"AVStream needs a model with 'video' and exactly one of {AUDIO_KEYS}, got {mods}")
@@ -180,17 +196,21 @@ class AVStream:
                                         max_side=max_side, pixel_format=video_format, matrix=video_matrix, range=video_range)
         self.audio_stream = LogMelStream(streams, 1.0 / fps, max_samples=max_samples, device=device, sample_rate=sample_rate,
                                          channels=channels, resample=resample)   # hop_sec: the expression of audio_features
-        self.model_stream = cls(model, streams, max_new=max_new, encoder_batch=encoder_batch)
+        self.window = None if window is None else (window_length, hop_length)
+        if window is None:
+            self.model_stream = cls(model, streams, max_new=max_new, encoder_batch=encoder_batch)
+        else:
+            self.model_stream = WindowStream(model, streams, window_length, hop_length, max_new=max_new, encoder_batch=encoder_batch)
         self.device, self.win = device, self.audio_stream.win
         max_out = max_samples if resample is None else self.audio_stream.max_outputs
         self.examples_per_step = examples_per_step(max_out, self.audio_stream.hop_frames)
         self.ring_frames = self.frame_stream.ring_frames
         # with a text leg the examples of up to ``hold`` unpaired frames wait too, not only the ``lead`` ahead of the frames
         self.ring_examples = hold_ring(self.lead + (self.hold if text is not None else 0), self.examples_per_step)
-        self.extra_dims = {m: self.model_stream.tcn[m].cin for m in self.extra_keys}
+        self.extra_dims = {m: self.model_stream._cin(m) for m in self.extra_keys}
         self._ring_dims = dict(self.extra_dims)   # every float ring of frame rows: the extra modalities and the text leg's
         if text is not None:
-            self._ring_dims["bert"] = self.model_stream.tcn["bert"].cin
+            self._ring_dims["bert"] = self.model_stream._cin("bert")
             if text.hidden != self._ring_dims["bert"]:
                 raise ValueError(f"text: the encoder's hidden size {text.hidden} is not the model's 'bert' embedding dim "
                                  f"{self._ring_dims['bert']}")
@@ -201,6 +221,7 @@ class AVStream:
             if e % 4:
                 raise ValueError(f"{m}: embedding dim {e} is not a multiple of 4 (the row gather moves float4)")
         self.frames_seen, self.examples_seen, self.paired = [0] * self.streams, [0] * self.streams, [0] * self.streams
+        self.emitted = [0] * self.streams
         self._exring, self._extra = None, {}   # allocated by the first push that needs them
         self.decisions, self._ended = None, set()   # _ended: finished streams whose decisions still stand
         if decisions is not None:
@@ -249,7 +270,8 @@ class AVStream:
 
     def _emit(self, owed, example_rows):
         """owed[s]: the (frame, example) pairs of stream s, in time order; ``example_rows``: (stream, example) list ->
-        [n, win * 64].  Takes the frames, runs the model ``max_new`` frames of a stream at a time -> (logits, counts)."""
+        [n, win * 64].  Takes the frames, runs the model ``max_new`` frames of a stream at a time -> parts[s]: the rows the
+        model stream emitted for stream s (every paired frame's; with ``window=`` those that became final), for ``_result``."""
         counts = [len(p) for p in owed]
         parts, at = [[] for _ in owed], [0] * self.streams
         while any(a < c for a, c in zip(at, counts)):
@@ -264,21 +286,44 @@ class AVStream:
                     X[m] = ex.transpose(1, 2) if m == "logmel" else self.model_stream._in_groups(self.audio_backbone, ex)
                 else:
                     X[m] = self._held_rows(self._extra[m], [(s, f) for s, f, _ in rows])
-            logits, k = self.model_stream.push_ragged(X, step), 0
-            if self.decisions is not None:
-                stale = [s for s in self._ended if step[s]]
-                self.decisions.reset(stale)
-                self._ended.difference_update(stale)
-                self.decisions.push_ragged(logits, step)
-            for s, c in enumerate(step):
-                if c:
-                    parts[s].append(logits[k:k + c])
-                    k += c
-                at[s] += c
+            logits = self.model_stream.push_ragged(X, step)
+            self._deliver(parts, *(logits if self.window is not None else (logits, step)))
+            at = [a + c for a, c in zip(at, step)]
         for s, c in enumerate(counts):
             self.paired[s] += c
+        return parts
+
+    def _deliver(self, parts, logits, got):
+        """The rows the model stream gave, ``got[s]`` of stream s: to the decisions and into ``parts[s]``."""
+        rows, k = [None] * self.streams, 0
+        for s, c in enumerate(got):
+            if c:
+                rows[s] = logits[k:k + c]
+                parts[s].append(rows[s])
+                k += c
+        if self.decisions is None or not k:
+            return
+        stale = [s for s in self._ended if got[s]]
+        self.decisions.reset(stale)
+        self._ended.difference_update(stale)
+        step, at = self.decisions.max_new, [0] * self.streams
+        if max(got) <= step:
+            self.decisions.push_ragged(logits, got)
+            return
+        while any(a < c for a, c in zip(at, got)):   # a finish can flush up to a window of rows per stream
+            take = [min(step, c - a) for a, c in zip(at, got)]
+            self.decisions.push_ragged(torch.cat([rows[s][at[s]:at[s] + t] for s, t in enumerate(take) if t]), take)
+            at = [a + t for a, t in zip(at, take)]
+
+    def _result(self, parts):
+        """parts[s]: the rows stream s emitted in this call, in time order -> (logits [P, n_out], counts), stream-major."""
+        counts = [sum(p.shape[0] for p in per) for per in parts]
+        for s, c in enumerate(counts):
+            self.emitted[s] += c
         flat = [p for per in parts for p in per]
-        return (torch.cat(flat) if len(flat) > 1 else flat[0]) if flat else self.model_stream._nothing(), counts
+        if not flat:
+            return torch.empty((0, self.model_stream._n_out()), device=self.device, dtype=torch.float32), counts
+        return (torch.cat(flat) if len(flat) > 1 else flat[0]), counts
 
     # ------------------------------------------------------------------------------------------------ the session
     @takes_layout("video", "video_layout")
@@ -344,7 +389,7 @@ class AVStream:
         else:
             owed = [pair_schedule_text(f, e, t, p)
                     for f, e, t, p in zip(self.frames_seen, self.examples_seen, self.text.covered, self.paired)]
-        return self._emit(owed, lambda pairs: self._held_rows(self._exring, pairs))
+        return self._result(self._emit(owed, lambda pairs: self._held_rows(self._exring, pairs)))
 
     def _hold_text(self, rows, counts, before):
         """The new text rows of a ``TextStream`` call into their ring slots, at the frame numbers ``before`` (+ i)."""
@@ -399,7 +444,10 @@ class AVStream:
                 src, index = tail, [i - self.streams * re for i in index]
             return ops.gather_rows(src.contiguous(), torch.tensor(index, dtype=torch.int64, device=self.device))
 
-        out = self._emit(owed, example_rows)
+        parts = self._emit(owed, example_rows)
+        if self.window is not None:   # the frames still waiting for their window: the tail or the short window
+            self._deliver(parts, *self.model_stream.finish(idx))
+        out = self._result(parts)
         self._reset_stages(idx)
         self._ended.update(idx)
         return out
@@ -418,4 +466,4 @@ class AVStream:
         if self.text is not None:
             self.text.reset(idx)
         for s in idx:
-            self.frames_seen[s] = self.examples_seen[s] = self.paired[s] = 0
+            self.frames_seen[s] = self.examples_seen[s] = self.paired[s] = self.emitted[s] = 0

@@ -1890,6 +1890,67 @@ def text_spread_rows(tok, segments, out_rows, out=None):
     return out
 
 
+# ------------------------------------------------------------------ the window rule on live streams (csrc/window_stream.hip)
+def window_stitch_tables(rows, done, tail, streams, slots, window, hop):
+    """The tables of one ``window_stitch_stream`` as Python ints, checked: ``rows`` = (stream, frame) per output row, ``done``
+    [S] the regular windows each stream has run, ``tail`` [S] the start of its tail (or short) window, -1 for none ->
+    (row streams, row frames).  Every row's stream is inside [0, S) and its frame inside [0, 2^31 - W); no regular window that
+    covers a row has left the ring (windows done - (slots - 1) .. done - 1 are in it) and at least one live window covers it.
+    No GPU."""
+    done, tail = [int(d) for d in done], [int(t) for t in tail]
+    if len(done) != streams or len(tail) != streams:
+        raise ValueError(f"window_stitch_stream: expected {streams} window counts and tail starts, got {len(done)} and {len(tail)}")
+    for s, (d, t) in enumerate(zip(done, tail)):
+        if d < 0 or t < -1 or max(d * hop, t) >= (1 << 31) - window:
+            raise ValueError(f"window_stitch_stream: stream {s}: {d} windows done, tail start {t}")
+    if not rows:
+        raise ValueError("window_stitch_stream: no row")
+    rs, rf = [], []
+    for p, (s, f) in enumerate(rows):
+        s, f = int(s), int(f)
+        if not 0 <= s < streams or not 0 <= f < (1 << 31) - window:
+            raise ValueError(f"window_stitch_stream: row {p}: frame {f} of stream {s} ({streams} streams)")
+        first = max((f - window) // hop + 1, 0)         # the lowest regular window that covers f
+        if first < done[s] - (slots - 1):
+            raise ValueError(f"window_stitch_stream: row {p}: window {first} of stream {s} covers frame {f} and has left the "
+                             f"ring of {slots - 1} regular slots ({done[s]} windows done)")
+        if not (first < done[s] or 0 <= f - tail[s] < window and tail[s] >= 0):
+            raise ValueError(f"window_stitch_stream: row {p}: no live window of stream {s} covers frame {f}")
+        rs.append(s)
+        rf.append(f)
+    return rs, rf
+
+
+def window_stitch_stream(wring, hop, rows, done, tail, out=None):
+    """The frames ``rows`` = [(stream, frame)] stitched from the ring ``wring`` [S, K, W, C] of each stream's last window
+    outputs (regular window i in slot i % (K - 1), the tail or short window in slot K - 1): ``out`` [P, C], each element the
+    bits ``eval_device.stitch_windows`` gives the same window outputs (a float32 sum from 0 in ascending window start, the
+    tail last, one division by the count).  ``done`` / ``tail``: per stream, the regular windows run so far and the tail's
+    start (-1: none).  All four tables are Python ints, checked on the host (``window_stitch_tables``) and uploaded as ONE
+    fresh int32 tensor [row streams | row frames | done | tail]."""
+    _dev_f32(wring, "wring")
+    if wring.dim() != 4 or min(wring.shape) < 1 or wring.shape[1] < 2:
+        raise ValueError(f"wring: expected [S, K >= 2, W, C], got {tuple(wring.shape)}")
+    s, k, w, c = wring.shape
+    hop = int(hop)
+    if not 1 <= hop <= w:
+        raise ValueError(f"hop = {hop}: must be in 1 .. W = {w}")
+    rs, rf = window_stitch_tables(rows, done, tail, s, k, w, hop)
+    p = len(rs)
+    if out is None:
+        out = torch.empty((p, c), device=wring.device, dtype=torch.float32)
+    else:
+        _dev_f32(out, "out", shape=(p, c))
+        if out.device != wring.device:
+            raise ValueError(f"out: on {out.device}, the ring on {wring.device}")
+    host = np.asarray(rs + rf + [int(d) for d in done] + [int(t) for t in tail], np.int32)
+    dev = torch.from_numpy(host).to(wring.device)
+    check(_lib.load().cer_window_stitch_stream(ptr(wring), s, k, w, c, hop, ptr(dev[:p]), ptr(dev[p:2 * p]), p,
+                                               ptr(dev[2 * p:2 * p + s]), ptr(dev[2 * p + s:]), ptr(out), current_stream()),
+          "cer_window_stitch_stream")
+    return out
+
+
 # ------------------------------------------------------------------ streaming log-mel (csrc/logmel_stream.hip)
 def logmel_stream_tables(segments, rows, examples, device):
     """The three tables of one streamed log-mel push, from Python ints, uploaded as ONE fresh int32 tensor (one H2D copy, no

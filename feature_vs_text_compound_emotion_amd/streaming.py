@@ -4,7 +4,8 @@ top.
 Everything in LFAN is causal or per frame (the TCN pads left only, eval BatchNorm1d is a per-row affine, the cross-modal
 attention mixes modalities and not time, LayerNorm and the regressor are per row), so frame t's output is a function of frames
 <= t: pushing the frames of a sequence in any chunking returns what the whole-sequence forward returns.  The same holds for CAN
-(the same TCN front; AttentionFusion, fc1, eval bn1 and fc2 work row by row).  JMT / MT attend over time and cannot stream.
+(the same TCN front; AttentionFusion, fc1, eval bn1 and fc2 work row by row).  JMT / MT attend over time and cannot stream
+this way; ``window_stream.WindowStream`` runs them, and the evaluator's window rule for all four heads, on live streams.
 
 State of one ``TemporalBlock`` for S streams (csrc/tcn_stream.hip): ``xring`` [S, R, Cin] holds its past inputs and ``hring``
 [S, R, Cout] its past first-conv activations, fp32 channels-last, R the power of two >= (k - 1) d + max_new.  Each stream
@@ -261,6 +262,10 @@ class _ModelStream:
         for t in self.tcn.values():
             t.reset(streams)
 
+    def _cin(self, m):
+        """The embedding dim of modality m: what its TCN takes."""
+        return self.tcn[m].cin
+
     def _check_keys(self, X):
         model = self.model
         if model.training:
@@ -283,7 +288,7 @@ class _ModelStream:
             ok, c = x.dim() == 4 and x.shape[0] == s and x.shape[1] == 64 and x.shape[3] == 96, x.shape[2] if x.dim() == 4 else 0
             want = f"[{s}, 64, c, 96]"
         else:
-            e = self.tcn[m].cin
+            e = self._cin(m)
             ok, c = x.dim() == 4 and x.shape[0] == s and x.shape[1] == 1 and x.shape[3] == e, x.shape[2] if x.dim() == 4 else 0
             want = f"[{s}, 1, c, {e}]"
         if not ok or c < 1:
@@ -297,7 +302,7 @@ class _ModelStream:
         elif m == "logmel":
             _check_packed(x, m, rows, (64, 96))
         else:
-            _check_packed(x, m, rows, (self.tcn[m].cin,))
+            _check_packed(x, m, rows, (self._cin(m),))
 
     @staticmethod
     def _one_count(cs):
@@ -372,7 +377,7 @@ class _ModelStream:
         -> logits [S, c, n_cls].  Skips the encoders."""
         self._check_keys(F)
         for m in F:
-            _check_rows(F[m], m, self.streams, self.tcn[m].cin)
+            _check_rows(F[m], m, self.streams, self._cin(m))
         c = self._one_count({m: F[m].shape[1] for m in F})
         return self._run({m: F[m].contiguous().view(self.streams * c, -1) for m in F}, c=c)
 
@@ -395,7 +400,7 @@ class _ModelStream:
         self._check_keys(F)
         counts = _check_counts(counts, self.streams, self.max_new)
         for m in F:
-            _check_packed(F[m], m, sum(counts), (self.tcn[m].cin,))
+            _check_packed(F[m], m, sum(counts), (self._cin(m),))
         if not sum(counts):
             return self._nothing()
         return self._run({m: F[m].contiguous() for m in F}, counts=counts)

@@ -557,6 +557,20 @@ int cer_window_stitch(const float *win_out, const int *starts, int nw, int Lw, i
 int cer_window_stitch_multi(const float *win_out, const int *win_start, const int *win_offsets, const int *frame_offsets,
                             int V, int nw, int Lw, int C, int R, float *out, void *stream);
 
+/* cer_window_stitch on live streams: the frames that became final, stitched from a ring of each stream's last window outputs.
+ * wring [S][K][W][C] fp32: regular window i of a stream (frames [i H, i H + W)) sits in slot i % (K - 1), slot K - 1 holds
+ * its tail window [n - W, n) or its single short window [0, n), n < W.  row_stream / row_frame [P] (device int32): row p of
+ * out [P][C] is frame row_frame[p] of stream row_stream[p]; win_done / tail_start [S] (device int32): the stream's regular
+ * windows done so far and the start of its tail window (-1: none).  Per element the regular windows still in the ring
+ * (win_done - (K - 1) .. win_done - 1) are walked in ascending start, then the tail: a float sum from 0.f and one division by
+ * (float)count, the bits of cer_window_stitch on the same window outputs; a frame no live window covers is written as 0.
+ * The tables are never trusted with an address: the stream is clamped into [0, S), slots are remainders modulo K - 1, window
+ * rows outside [0, W) are skipped.  Null pointers, S, W, C, H or P < 1, K < 2, H > W and buffers that are not 4-byte aligned
+ * return CER_ERR_INVALID_ARG before any launch. */
+int cer_window_stitch_stream(const float *wring, int S, int K, int W, int C, int H, const int32_t *row_stream,
+                             const int32_t *row_frame, int P, const int32_t *win_done, const int32_t *tail_start, float *out,
+                             void *stream);
+
 /* Accumulate (+=) the confusion counts of a batch of V videos: logits [R][C] (the videos' frames concatenated), labels [R]
  * (float class ids), video_offsets [V+1] (device int32 row offsets; the caller makes them rise strictly from 0 to R, the
  * kernels read rows [video_offsets[v], video_offsets[v+1]) unchecked).  Every argmax is numpy.argmax: the first NaN if
