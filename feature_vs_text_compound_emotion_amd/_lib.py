@@ -181,6 +181,8 @@ _SIGNATURES = {
                                   c_int64, _P, _P, _P, _P]),
     "cer_gather_rows": (c_int, [_P, _P, _P, c_int, c_int, c_uint64, _P]),
     "cer_text_spread_rows": (c_int, [_P, c_int64, c_int, _P, c_int, _P, c_int, _P, c_int64, _P]),
+    "cer_feature_moments_update": (c_int, [_P, c_int64, c_int, _P, _P]),
+    "cer_standardize_rows": (c_int, [_P, c_int64, c_int, _P, _P, _P, _P]),
     "cer_frames_band_rows": (c_int, []),
     "cer_frames_transform": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int,
                                      c_int, c_float, c_float, _P, _P, _P]),

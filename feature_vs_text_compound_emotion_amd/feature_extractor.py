@@ -11,11 +11,17 @@ base/speech.py:185-251,690-738).  This module fuses that offline stage into the 
   text  : token ids (one padded sentence per clip) -> BERT sum-of-last-4 -> drop [CLS]/[SEP]/pad ->
           spread the tokens over the frames in contiguous blocks (align_word_embedding_new)
   video : frames pass through (IR-50 lives inside the model).
+
+With ``mean_std=`` the ``vggish`` and ``bert`` rows leave standardised, ``(row - mean) / std`` per component
+(``feature_stats.FeatureStandardizer``): the reference's ``transforms.Normalize`` around these two modalities
+(base/dataset.py:516-539).  It runs last, after the repetition and the spreading, as ``Normalize`` runs on the aligned
+``.npy`` rows: a frame without a word becomes ``(0 - mean) / std``.
 """
 import torch
 
 from . import ops
 from .audio_backbone import AudioBackbone
+from .feature_stats import as_standardizer
 from .text_encoder import BertEncoderHIP
 
 
@@ -35,11 +41,24 @@ def align_tokens_to_frames(num_tokens, num_frames):
 
 
 class MultimodalFeatureExtractor(torch.nn.Module):
-    def __init__(self, audio=None, text=None, fps=32):
+    def __init__(self, audio=None, text=None, fps=32, mean_std=None):
+        """``mean_std``: None (raw rows, the default), or {feature: {"mean", "std"}} / a ``FeatureStandardizer`` for
+        ``vggish`` [128] and / or ``bert`` [hidden]; a modality it lacks stays raw."""
         super().__init__()
         self.audio = audio if audio is not None else AudioBackbone()
         self.text = text if text is not None else BertEncoderHIP()
         self.fps = fps
+        dims = {"vggish": 128}
+        if isinstance(getattr(self.text, "hidden", None), int):
+            dims["bert"] = self.text.hidden
+        self.standardizer = as_standardizer(mean_std, dims=dims, allowed=("vggish", "bert"),
+                                            who="MultimodalFeatureExtractor(mean_std=)")
+
+    def _standardized(self, feature, rows):
+        """``rows`` [..., C] contiguous and this module's own: standardised in place when ``feature`` has statistics."""
+        if self.standardizer is not None and feature in self.standardizer:
+            self.standardizer(feature, rows, out=rows)
+        return rows
 
     @torch.no_grad()
     def audio_features(self, pcm_int16, num_frames, sample_rate=16000, resample=None):
@@ -51,7 +70,7 @@ class MultimodalFeatureExtractor(torch.nn.Module):
         emb = self.audio(ex[:, :use].reshape(b * use, 96, 64)).view(b, use, 128)
         if use < num_frames:  # compact_audio_feature: repeat the last row
             emb = torch.cat([emb, emb[:, -1:].expand(b, num_frames - use, 128)], dim=1)
-        return emb.reshape(b, 1, num_frames, 128).contiguous()
+        return self._standardized("vggish", emb.reshape(b, 1, num_frames, 128).contiguous())
 
     @staticmethod
     def frame_token_index(attention_mask_cpu, num_frames):
@@ -78,7 +97,7 @@ class MultimodalFeatureExtractor(torch.nn.Module):
         mask_cpu = attention_mask_cpu if attention_mask_cpu is not None else attention_mask.cpu()
         plan = self.frame_token_index(mask_cpu, num_frames).to(tok.device)
         rows = ops.gather_rows(tok.view(bsz * s, hd), plan.view(-1).contiguous())  # frames without a token (-1) stay zero
-        return rows.view(bsz, 1, num_frames, hd)
+        return self._standardized("bert", rows).view(bsz, 1, num_frames, hd)
 
     @torch.no_grad()
     def paragraph_features(self, token_ids, attention_mask, sentence_counts, num_frames, attention_mask_cpu=None):
@@ -107,7 +126,7 @@ class MultimodalFeatureExtractor(torch.nn.Module):
         hd = tok.shape[2]
         rows = ops.text_spread_rows(tok.view(n * s, hd), segments, len(counts) * num_frames,
                                     out=torch.empty((len(counts) * num_frames, hd), device=tok.device))
-        return rows.view(len(counts), 1, num_frames, hd)
+        return self._standardized("bert", rows).view(len(counts), 1, num_frames, hd)
 
     @torch.no_grad()
     def forward(self, frames, pcm_int16, token_ids, attention_mask, attention_mask_cpu=None, sample_rate=16000,

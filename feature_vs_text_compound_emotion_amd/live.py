@@ -31,6 +31,7 @@ import torch
 
 from . import ops
 from .audio_stream import ROW_HOP, LogMelStream
+from .feature_stats import as_standardizer
 from .frames import FrameStream, hold_ring, takes_layout
 from .fusion_heads import CAN, JMT
 from .lfan import LFAN
@@ -144,13 +145,21 @@ class AVStream:
     receives exactly those rows, ``paired`` keeps its meaning (frames handed to the model) and ``emitted`` counts the rows that
     came out.  Without ``window=`` every paired frame is emitted at once and ``emitted`` equals ``paired``.
 
+    Standardised rows.  ``mean_std=`` ({feature: {"mean", "std"}} or a ``feature_stats.FeatureStandardizer``) makes the session
+    hand the model ``(row - mean) / std`` per component, the reference's ``transforms.Normalize`` (base/dataset.py:516-539),
+    for the rows it produces itself: ``vggish`` from its audio backbone and ``bert`` from its text leg (a frame without a word
+    becomes ``(0 - mean) / std``).  One in-place launch per such modality where the model's input is formed; the rings hold
+    raw rows.  A key for ``video``, ``logmel``, a modality the model lacks or one that arrives through ``extra=`` (the
+    caller's finished rows) is a ValueError at construction; a modality without a key stays raw.
+
     A push that would let more than ``hold`` frames or ``lead`` examples wait, and any argument one of the stages refuses,
     raises ValueError before any launch and changes no state, the stages' included.  A stream's counts above ``max_new`` in one
     call reach the model in several pushes, in time order."""
 
     def __init__(self, model, streams, fps, *, sample_rate=16000, channels=1, resample=None, size=48, crop=40, hold=64, lead=8,
                  max_new=32, max_samples=4096, encoder_batch=8, audio_backbone=None, decisions=None,
-                 max_side=1024, video_format="rgb24", video_matrix="bt601", video_range="limited", text=None, window=None):
+                 max_side=1024, video_format="rgb24", video_matrix="bt601", video_range="limited", text=None, window=None,
+                 mean_std=None):
         cls = CANStream if isinstance(model, CAN) else LFANStream
         if window is not None:
             from .window_stream import WindowStream
@@ -184,6 +193,15 @@ class AVStream:
             if text.streams != int(streams):
                 raise ValueError(f"text: a TextStream of {text.streams} streams for a session of {int(streams)}")
         self.extra_keys = [m for m in mods if m != "video" and m != self.audio_key and not (m == "bert" and text is not None)]
+        # standardised are the rows the session makes itself: vggish from its audio backbone, bert from its text leg
+        own = {m: 128 if m == "vggish" else text.hidden for m in mods if m == "vggish" or (m == "bert" and text is not None)}
+        if mean_std is not None:
+            for m in getattr(mean_std, "keys", lambda: ())():
+                if m in self.extra_keys:
+                    raise ValueError(f"AVStream(mean_std=): {m!r} arrives through extra=, which takes the caller's finished rows")
+                if m not in mods:
+                    raise ValueError(f"AVStream(mean_std=): the model has no {m!r} (its modalities: {mods})")
+        self.standardizer = as_standardizer(mean_std, dims=own, allowed=tuple(own), who="AVStream(mean_std=)")
         self.audio_backbone = None
         if self.audio_key == "vggish":
             spatial = getattr(model, "spatial", {})
@@ -220,6 +238,12 @@ class AVStream:
         for m, e in self._ring_dims.items():
             if e % 4:
                 raise ValueError(f"{m}: embedding dim {e} is not a multiple of 4 (the row gather moves float4)")
+        if self.standardizer is not None:
+            for m in self.standardizer.keys():
+                if self.standardizer.dim(m) != self.model_stream._cin(m):
+                    raise ValueError(f"AVStream(mean_std=): {m!r} has {self.standardizer.dim(m)} components, the model's "
+                                     f"embedding dim is {self.model_stream._cin(m)}")
+            self.standardizer.to(device)
         self.frames_seen, self.examples_seen, self.paired = [0] * self.streams, [0] * self.streams, [0] * self.streams
         self.emitted = [0] * self.streams
         self._exring, self._extra = None, {}   # allocated by the first push that needs them
@@ -286,6 +310,8 @@ class AVStream:
                     X[m] = ex.transpose(1, 2) if m == "logmel" else self.model_stream._in_groups(self.audio_backbone, ex)
                 else:
                     X[m] = self._held_rows(self._extra[m], [(s, f) for s, f, _ in rows])
+                if self.standardizer is not None and m in self.standardizer:   # fresh rows of this call: in place
+                    self.standardizer(m, X[m], out=X[m])
             logits = self.model_stream.push_ragged(X, step)
             self._deliver(parts, *(logits if self.window is not None else (logits, step)))
             at = [a + c for a, c in zip(at, step)]

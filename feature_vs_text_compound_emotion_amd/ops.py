@@ -1890,6 +1890,63 @@ def text_spread_rows(tok, segments, out_rows, out=None):
     return out
 
 
+# ------------------------------------------------------------------ standardised vggish / bert rows (csrc/feature_norm.hip)
+FEATURE_NORM_MAX_C = 1 << 20
+
+
+def _feature_rows(t, name):
+    """A dense [M >= 1, C] float32 GPU tensor with C in the kernels' range and M * C < 2^31.  Returns (M, C)."""
+    if not torch.is_tensor(t):
+        raise ValueError(f"{name}: expected a tensor, got {type(t).__name__}")
+    _dev_f32(t, name)
+    if t.dim() != 2 or t.shape[0] < 1 or not 1 <= t.shape[1] <= FEATURE_NORM_MAX_C or t.numel() >= (1 << 31):
+        raise ValueError(f"{name}: expected [M >= 1, 1 <= C <= {FEATURE_NORM_MAX_C}] with M * C < 2^31, got {tuple(t.shape)}")
+    return t.shape[0], t.shape[1]
+
+
+def feature_moments_update(rows, acc):
+    """acc[0] += rows.sum(0), acc[1] += (rows ** 2).sum(0) in float64, the adds of a column in row order: ``rows`` [M, C]
+    float32, ``acc`` [2, C] float64 on the same GPU, updated in place.  The bits of ``acc`` depend on the sequence of rows
+    only, not on how it was split over calls.  Returns ``acc``."""
+    m, c = _feature_rows(rows, "rows")
+    if not (torch.is_tensor(acc) and acc.is_cuda and acc.dtype == torch.float64 and acc.is_contiguous()
+            and tuple(acc.shape) == (2, c) and acc.device == rows.device):
+        raise ValueError(f"acc: expected a contiguous float64 [2, {c}] on {rows.device}, got "
+                         f"{(acc.dtype, acc.device, tuple(acc.shape)) if torch.is_tensor(acc) else type(acc)}")
+    check(_lib.load().cer_feature_moments_update(ptr(rows), m, c, ptr(acc), current_stream()), "cer_feature_moments_update")
+    return acc
+
+
+def standardize_rows(x, mean, std, out=None):
+    """(x - mean) / std per column in float32, one subtraction and one correctly rounded division: ``torch.equal`` with
+    ``x.sub(mean).div(std)`` (torchvision's Normalize).  ``x`` [M, C] float32 with C % 4 == 0; ``mean``, ``std`` [C] float32 on
+    the same GPU; ``out``: where to write, ``x`` itself for in place, a fresh tensor by default.  Returns ``out``."""
+    m, c = _feature_rows(x, "x")
+    if c % 4:
+        raise ValueError(f"x: C = {c} is not a multiple of 4 (the rows move as float4)")
+    for t, n in ((mean, "mean"), (std, "std")):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{n}: expected a tensor, got {type(t).__name__}")
+        _dev_f32(t, n, shape=(c,))
+        if t.device != x.device:
+            raise ValueError(f"{n}: on {t.device}, x on {x.device}")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        if not torch.is_tensor(out):
+            raise ValueError(f"out: expected a tensor, got {type(out).__name__}")
+        _dev_f32(out, "out", shape=(m, c))
+        if out.device != x.device:
+            raise ValueError(f"out: on {out.device}, x on {x.device}")
+        if out.data_ptr() != x.data_ptr() and out.data_ptr() < x.data_ptr() + 4 * m * c and x.data_ptr() < out.data_ptr() + 4 * m * c:
+            raise ValueError("out: overlaps x without being x")
+    for t, n in ((x, "x"), (mean, "mean"), (std, "std"), (out, "out")):
+        if t.data_ptr() % 16:
+            raise ValueError(f"{n}: storage is not 16-byte aligned (the rows move as float4)")
+    check(_lib.load().cer_standardize_rows(ptr(x), m, c, ptr(mean), ptr(std), ptr(out), current_stream()), "cer_standardize_rows")
+    return out
+
+
 # ------------------------------------------------------------------ the window rule on live streams (csrc/window_stream.hip)
 def window_stitch_tables(rows, done, tail, streams, slots, window, hop):
     """The tables of one ``window_stitch_stream`` as Python ints, checked: ``rows`` = (stream, frame) per output row, ``done``

@@ -474,6 +474,23 @@ int cer_gather_rows(const float *src, const int64_t *index, float *out, int n_ou
 int cer_text_spread_rows(const float *tok, int64_t tok_rows, int hidden, const int32_t *segments, int n_segments,
                          const int32_t *tok_index, int n_index, float *out, int64_t out_rows, void *stream);
 
+/* The reference's standardisation of the vggish and bert rows (base/dataset.py:516-539 wraps them in
+ * transforms.Normalize(mean, std); the statistics are base/dataset.py:272-325), csrc/feature_norm.hip.
+ *
+ * cer_feature_moments_update: rows [M][C] fp32 dense, acc [2][C] float64, both device memory:
+ *   acc[0][c] += sum_m rows[m][c],  acc[1][c] += sum_m rows[m][c]^2,
+ * float64 adds in ascending row order per column, nothing else: the bits of acc depend on the sequence of rows only, not
+ * on how it was split over calls (the calls of one stream are ordered).  No atomics.  NaN / Inf propagate per column.
+ *
+ * cer_standardize_rows: out[m][c] = (x[m][c] - mean[c]) / std[c] in fp32, one subtraction and one correctly rounded
+ * division (tensor.sub_(mean).div_(std)); mean, std [C] fp32; out == x is allowed; C % 4 == 0, float4 moves.
+ *
+ * Both refuse with CER_ERR_INVALID_ARG before any launch, the entry's name at the head of cer_last_error(): a null pointer,
+ * M < 1, C outside [1, 2^20] (standardize: [4, 2^20] and C % 4 != 0), M * C >= 2^31, rows not 4-byte / acc not 8-byte aligned
+ * (standardize: x, mean, std, out not 16-byte aligned). */
+int cer_feature_moments_update(const float *rows, int64_t M, int C, double *acc, void *stream);
+int cer_standardize_rows(const float *x, int64_t M, int C, const float *mean, const float *std, float *out, void *stream);
+
 /* ------------------------------------------------------------------------
  * Audio / text encoder front ends and attention.
  * ---------------------------------------------------------------------- */
